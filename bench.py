@@ -14,9 +14,13 @@ edges / 1 250 000 collision edges, 30-60-90 tile set (tile_count 2 -> Fx 3), T =
 north_star "100k-node/1M-edge 30-60-90 super-graph").  At N GPUs the graph has N x 100 000
 nodes, node-range sharded (weak scaling); value = all nodes scored / max-over-ranks time.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, measured with HIP events on the
-launch stream in a second instrumented pass) and `cpu_baseline` (the CPU oracle = a port of the
-reference's op sequence, timed on this box's host cores on a bounded sample).
+Prints ONE JSON line (rank 0): metric, value, unit, higher_is_better, dtype, ms_per_step (the
+median time of one timed step).  A plain run sets up, warms up, times the K steps and prints it.
+--full adds the side measurements: `roofline` (dominant kernel, measured with HIP events on the
+launch stream in a second instrumented pass), `cpu_baseline` (the CPU oracle = a port of the
+reference's op sequence, timed on this box's host cores on a bounded sample), the other sizes and
+configurations, the greedy solve, the training step and the per-op parity probe.
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (float32).
 """
 import argparse
 import ctypes as C
@@ -286,6 +290,22 @@ def kernel_roofline(class_ms, n, ea, ec, n_types, edge_groups=True):
     return out
 
 
+DUMP_BYTES_PER_OUTPUT = 30_000_000       # two outputs: under 64 MB in all
+
+
+def dump_outputs(out_dir, tensors):
+    """DIR/<name>.npy, float32, for every output; one larger than DUMP_BYTES_PER_OUTPUT as the rows of a fixed, seeded sample
+    (the same rows for the same shape, run after run), DIR/<name>_sample.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in tensors.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > DUMP_BYTES_PER_OUTPUT:
+            rows = max(1, DUMP_BYTES_PER_OUTPUT // max(1, a[:1].nbytes))
+            idx = np.sort(np.random.default_rng(0).choice(a.shape[0], size=rows, replace=False))
+            a, name = a[idx], name + "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def self_launch(args) -> int:
     """`python bench.py --gpus N` without a launcher around it: N ranks of this script through torch.distributed.run (one per
     GPU, rendezvous on 127.0.0.1, a free port), their stdout -- rank 0's ONE JSON line -- passed through.  Fails loudly, and
@@ -358,7 +378,15 @@ def main():
                     help="the launcher alone: every rank joins a gloo group on the CPU, all-reduces a one, rank 0 prints "
                          '{"launcher_selftest": true, "ranks_seen": N}; needs no GPU')
     ap.add_argument("--launch-timeout", type=float, default=1800.0, help="seconds after which a self-launched run is killed")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (cached layout, roofline and kernel classes, larger layouts, configs 0 / 2 / 3, "
+                         "loss, greedy round and solve, training step, CPU baseline, parity probe); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32; an output over 30 MB as the rows of a fixed, seeded "
+                         "sample, DIR/<name>_sample.npy); with several ranks each writes its own, DIR/<name>_rank<r>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.spawn):
         raise SystemExit(self_launch(args))
@@ -416,12 +444,15 @@ def main():
         x, adj, adj_attr, col, col_attr = sg.to_torch(dev)
 
         def step():
-            return net(x=x, adj_e_index=adj, adj_e_features=adj_attr, col_e_idx=col, col_e_features=col_attr)[0]
+            # (probabilities, adj_e_features passed through): what a caller of TilinGNN.forward receives
+            return net(x=x, adj_e_index=adj, adj_e_features=adj_attr, col_e_idx=col, col_e_features=col_attr)
         n_local, ea_local, ec_local = n_total, ea_total, ec_total
     else:
         from tilingnn_amd.dist import ShardedTilinGNN
         shard_runner = ShardedTilinGNN(net, sg, rank, world, dev)
-        step = shard_runner.step
+
+        def step():
+            return (shard_runner.step(),)           # this rank's probabilities
         n_local, ea_local, ec_local = shard_runner.n_local, shard_runner.ea_local, shard_runner.ec_local
 
     def barrier():
@@ -446,10 +477,15 @@ def main():
     t0 = time.perf_counter()
     evs[0].record()
     for k in range(args.steps):
-        out = step()
+        outs = step()
         evs[k + 1].record()
     barrier()
     dt = time.perf_counter() - t0
+    out = outs[0]
+    if args.dump_outputs:
+        names = ("probs", "adj_e_features")
+        suffix = f"_rank{rank}" if world > 1 else ""
+        dump_outputs(args.dump_outputs, {name + suffix: t for name, t in zip(names, outs)})
     per_step_ms = sorted(evs[k].elapsed_time(evs[k + 1]) for k in range(args.steps))
     median_ms = per_step_ms[len(per_step_ms) // 2] if args.steps % 2 else \
         0.5 * (per_step_ms[args.steps // 2 - 1] + per_step_ms[args.steps // 2])
@@ -463,9 +499,12 @@ def main():
     ms_per_step = median_ms
     value = n_total / (median_ms * 1e-3)
 
+    # ---- the side measurements (--full): everything below up to the result line
+    side = args.full and not sharded
+
     # ---- cached-layout variant (prep amortised, e.g. repeated predict on one BrickLayout)
     cached_ms = None
-    if not sharded:
+    if side:
         net.cache_graph = True
         for _ in range(2):
             step()
@@ -479,7 +518,7 @@ def main():
 
     # ---- roofline of the dominant kernel: second, instrumented pass (HIP events on the launch stream)
     roofline, class_ms = None, None
-    if not sharded:
+    if side:
         class_ms, n_types_seen = profiled_classes(net, x, adj, adj_attr, col, args.steps)
         dom = max(("nnconv", "gin", "dense_final"), key=lambda k: class_ms[k]["ms_per_forward"])
         from tilingnn_amd import ops as _ops
@@ -585,7 +624,7 @@ def main():
     # ---- larger single-GPU layouts (BASELINE configs 4 / 5 are 500k / 2M nodes over 4 / 8 GPUs; here on ONE GPU, drawn
     #      on the device): step time with graph preparation, kernel classes, fractions of the HBM bound per kernel
     extras = None
-    if not sharded and not args.no_extra_sizes:
+    if side and not args.no_extra_sizes:
         from tilingnn_amd.synth import make_super_graph_on_device
         extras = []
         for n_big, seed in ((500_000, 3), (2_000_000, 4)):
@@ -617,7 +656,7 @@ def main():
     # ---- BASELINE config 3: 30-60-90 + equilateral (tile_count 4), the same 100k / 1M / 1.25M graph shape, network_width 64,
     #      bf16 activation storage (csrc/bf16_path.hip); fp32 accumulate, fp64 BatchNorm sums.  Step = forward incl. graph prep.
     config3 = None
-    if not sharded and not args.no_extra_sizes:
+    if side and not args.no_extra_sizes:
         sg3 = make_super_graph(args.nodes_per_gpu, int(ADJ_PER_GPU * scale), int(COL_PER_GPU * scale), tile_count=4,
                                n_edge_types=N_TYPES, seed=2)
         x3, adj3, attr3, col3, _ = sg3.to_torch(dev)
@@ -657,7 +696,7 @@ def main():
     #      what a greedy round scores.  Small layouts run the forward as one persistent kernel (csrc/forward_small.hip); the
     #      general launch schedule is timed beside it (tgnn_set_small_layout_limit(0)).
     real_layout = None
-    if not sharded and not args.no_extra_sizes:
+    if side and not args.no_extra_sizes:
         try:
             from tests.golden_util import graph_tensors, load_labyrinth_graph
             from tilingnn_amd import _lib
@@ -697,7 +736,7 @@ def main():
     #      general launch schedule is timed beside it (tgnn_set_mid_layout_limit(0)).  Also 20 000 and 50 000 nodes of the
     #      headline generator (what a greedy round of a large solve, or a rank of a strong-scaled 100k layout, scores).
     config2 = None
-    if not sharded and not args.no_extra_sizes:
+    if side and not args.no_extra_sizes:
         from tilingnn_amd import _lib
         from tilingnn_amd.graph_networks import _graph_cache
         mid0 = _lib.lib.tgnn_get_mid_layout_limit()
@@ -739,7 +778,7 @@ def main():
 
     # ---- the loss ML_Solver.predict evaluates on the probabilities: two launches, HBM bound
     loss_info = None
-    if not sharded:
+    if side:
         from tilingnn_amd.solver.ml_solver.losses import Losses
         p1 = torch.rand(n_total, 1, device=dev)
         for _ in range(3):
@@ -762,7 +801,7 @@ def main():
     #      half of the nodes still unlabelled; the CPU figure is the numpy restatement of compute_sub_layout (the
     #      reference itself runs Python comprehensions with dict look-ups over all edges)
     sub_info = None
-    if not sharded:
+    if side:
         from tilingnn_amd.util.algorithms import DeviceLayout, SubLayoutBuilder
         rng = np.random.default_rng(0)
         alive_h = (rng.uniform(size=n_total) < 0.5).astype(np.int32)
@@ -815,7 +854,7 @@ def main():
     # ---- one training step at the same shape: forward keeping activations, loss, backward through the
     #      adjoint kernels, Adam (torch's, the caller's optimizer in the reference: network_train.py)
     train_info = None
-    if not sharded and not args.no_train_step:
+    if side and not args.no_train_step:
         from tilingnn_amd.solver.ml_solver.losses import Losses
         net.cache_graph = True              # the transposed CSR is built once per layout, like the forward structures
         net.autograd = True
@@ -895,7 +934,7 @@ def main():
             import torch.distributed as dist
             line["collectives"] = {"backend": dist.get_backend(), "ranks_seen": ranks_seen,
                                    "per_forward": shard_runner.collectives_per_forward}
-        if not args.no_cpu_baseline and world == 1:           # the CPU leg is a 1-GPU (rank 0, N = 1) measurement
+        if args.full and not args.no_cpu_baseline and world == 1:    # the CPU leg is a 1-GPU (rank 0, N = 1) measurement
             line["cpu_baseline"] = cpu_baseline()
             # GPU and CPU at the SAME configuration (BASELINE config 2, graph preparation included on the GPU side); the headline's
             # nodes/s (100 000-node layout) over the CPU's nodes/s at 10 000 nodes is quoted beside it under its own name

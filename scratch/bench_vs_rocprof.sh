@@ -2,12 +2,12 @@
 # the bench line's roofline.avg_launch_us (device-stamped, in the production forward) beside rocprofv3's average for the same command
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp; mkdir -p gpurun_out
 rm -rf /tmp/bvr
-timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/bvr -- python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-train-step --no-extra-sizes > gpurun_out/bvr_bench.json 2> /tmp/bvr.err
+timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/bvr -- python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-train-step --no-extra-sizes > /tmp/bvr_bench.json 2> /tmp/bvr.err
 f=$(find /tmp/bvr -name "*kernel_stats.csv" | head -1)
 python scratch/kstats.py "$f" 12
 python - <<'PY'
 import json
-for l in open('gpurun_out/bvr_bench.json'):
+for l in open('/tmp/bvr_bench.json'):
     l = l.strip()
     if l.startswith('{"metric"'):
         r = json.loads(l)["roofline"]

@@ -19,7 +19,7 @@ echo "== forward wall time, median of 30, A/B on this box (python scratch/time_e
 python scratch/time_eg_fwd.py 2>&1 | grep -v amdgpu.ids >> $S
 echo "== bench.py headline (graph preparation inside the step), type columns (TGNN_GROUPS=0) then edge groups" >> $S
 for g in 0 1; do
-  TGNN_GROUPS=$g python bench.py --no-cpu-baseline --no-train-step --no-extra-sizes 2>/dev/null | python -c "
+  TGNN_GROUPS=$g python bench.py --full --no-cpu-baseline --no-train-step --no-extra-sizes 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d['roofline']
 print('TGNN_GROUPS=$g: ms_per_step %.4f  value %.3e  cached %.4f  roofline: %s | avg_launch_us %.2f frac %.4f single-stream %.2f us gather_bound.frac %.3f' % (

@@ -4,9 +4,9 @@
 # timeout), preparation, sharded step, split modes, side-by-side small layouts.  Output: gpurun_out/r03/ (copied to profiles/r03_*).
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 O=gpurun_out/r03; mkdir -p $O
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err
 rm -rf $O/ks
-timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -o r03 -- python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-train-step --no-extra-sizes > $O/ks_bench.json 2> $O/ks.err
+timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -o r03 -- python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-train-step --no-extra-sizes > $O/ks_bench.json 2> $O/ks.err
 cp $(find $O/ks -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv
 python scratch/kstats.py $O/kernel_stats.csv 40 > $O/kernel_stats_summary.txt
 # the production forward alone (cached layout, two chains): what the kernels cost INSIDE the schedule
@@ -42,7 +42,7 @@ timeout 200 python scratch/test_cols_f16.py >> $O/split_modes.txt 2>&1
 MASTER_ADDR=127.0.0.1 MASTER_PORT=29555 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 300 python scratch/time_sharded.py 2>&1 | grep two_streams > $O/sharded.txt
 TGNN_LIBRARY_RCCL=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29556 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 300 python scratch/time_sharded.py 2>&1 | grep two_streams | sed 's/^/host callbacks into torch.distributed: /' >> $O/sharded.txt
 bash scratch/sharded_trace.sh 2>&1 | grep -v "^$" >> $O/sharded.txt
-MASTER_ADDR=127.0.0.1 MASTER_PORT=29577 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 400 python bench.py --force-sharded --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_sharded_world1.json
+MASTER_ADDR=127.0.0.1 MASTER_PORT=29577 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 400 python bench.py --full --force-sharded --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_sharded_world1.json
 # small layouts: side by side, the persistent kernel's times
 timeout 200 python scratch/time_many.py > $O/forward_many.txt 2>&1
 timeout 300 python scratch/time_small.py 300 1254 2500 4096 > $O/small_layout_times.txt 2>&1

@@ -5,7 +5,7 @@
 # the greedy solve, the sharded step at world 1.  Output: gpurun_out/r04/ (copied to profiles/r04_*).
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 O=gpurun_out/r04; mkdir -p $O
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err
 rm -rf /tmp/r04_fw; timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r04_fw -- python scratch/run_fwd_mode.py 1 20 > /tmp/r04_fw.log 2>&1
 python scratch/kstats.py $(find /tmp/r04_fw -name "*kernel_stats.csv" | head -1) 26 > $O/forward_kernel_stats.txt
 timeout 200 python scratch/run_stamped.py > $O/stamped_nnconv.txt 2>&1
@@ -42,6 +42,6 @@ timeout 200 python scratch/time_config3.py 2>&1 | grep bfloat16 >> $O/config3_ke
 bash scratch/pmc_config3.sh > $O/config3_pmc.txt 2>&1
 # greedy solve (host sweep against the device rounds), sharded step at world 1
 timeout 600 python scratch/time_solve.py > $O/greedy_solve.txt 2>&1
-MASTER_ADDR=127.0.0.1 MASTER_PORT=29577 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 400 python bench.py --force-sharded --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_sharded_world1.json
-MASTER_ADDR=127.0.0.1 MASTER_PORT=29578 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 400 python bench.py --force-sharded --scaling strong --config 4 --steps 10 --warmup 3 2>/dev/null | tail -1 > $O/bench_strong_config4_world1.json
+MASTER_ADDR=127.0.0.1 MASTER_PORT=29577 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 400 python bench.py --full --force-sharded --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_sharded_world1.json
+MASTER_ADDR=127.0.0.1 MASTER_PORT=29578 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 400 python bench.py --full --force-sharded --scaling strong --config 4 --steps 10 --warmup 3 2>/dev/null | tail -1 > $O/bench_strong_config4_world1.json
 ls -la $O

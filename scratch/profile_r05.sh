@@ -5,8 +5,8 @@
 # world 1.  Output: gpurun_out/r05/ (copied to profiles/r05_*).  The studies of the round have their own scripts (profiles/README.md).
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 O=gpurun_out/r05; mkdir -p $O
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err
-rm -rf /tmp/r05_ks; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r05_ks -- python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-train-step --no-extra-sizes > /tmp/r05_ks.log 2>&1
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err
+rm -rf /tmp/r05_ks; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r05_ks -- python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-train-step --no-extra-sizes > /tmp/r05_ks.log 2>&1
 f=$(find /tmp/r05_ks -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && { cp $f $O/kernel_stats.csv; python scratch/kstats.py $f 30 > $O/kernel_stats_summary.txt; }
 rm -rf /tmp/r05_fw; timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r05_fw -- python scratch/run_fwd_mode.py 1 20 > /tmp/r05_fw.log 2>&1
 python scratch/kstats.py $(find /tmp/r05_fw -name "*kernel_stats.csv" | head -1) 26 > $O/forward_kernel_stats.txt
@@ -33,5 +33,5 @@ bash scratch/mid_trace.sh 10000 > /dev/null 2>&1; cp gpurun_out/mid_trace_10000/
 timeout 300 python scratch/time_mid.py > $O/mid_sizes.txt 2>&1
 bash scratch/kstats3.sh r05_config3 > $O/config3_kernel_stats.txt 2>&1
 timeout 200 python scratch/time_config3.py 2>&1 | grep bfloat16 >> $O/config3_kernel_stats.txt
-MASTER_ADDR=127.0.0.1 MASTER_PORT=29577 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 400 python bench.py --force-sharded --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_sharded_world1.json
+MASTER_ADDR=127.0.0.1 MASTER_PORT=29577 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 400 python bench.py --full --force-sharded --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_sharded_world1.json
 ls -la $O

@@ -5,8 +5,8 @@
 # the final MLP's kernels, mid sizes, the sharded step at world 1 (bench + timeline).  Output: gpurun_out/r06/ (copied to profiles/r06_*).
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 O=gpurun_out/r06; mkdir -p $O
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err
-rm -rf /tmp/r06_ks; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r06_ks -- python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-train-step --no-extra-sizes > /tmp/r06_ks.log 2>&1
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err
+rm -rf /tmp/r06_ks; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r06_ks -- python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-train-step --no-extra-sizes > /tmp/r06_ks.log 2>&1
 f=$(find /tmp/r06_ks -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && { cp $f $O/kernel_stats.csv; python scratch/kstats.py $f 34 > $O/kernel_stats_summary.txt; }
 rm -rf /tmp/r06_fw; timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r06_fw -- python scratch/run_fwd_mode.py 1 20 > /tmp/r06_fw.log 2>&1
 python scratch/kstats.py $(find /tmp/r06_fw -name "*kernel_stats.csv" | head -1) 26 > $O/forward_kernel_stats.txt
@@ -36,6 +36,6 @@ bash scratch/mid_trace.sh 10000 > /dev/null 2>&1; cp gpurun_out/mid_trace_10000/
 timeout 300 python scratch/time_mid.py > $O/mid_sizes.txt 2>&1
 AB_REPS=6 timeout 600 python scratch/ab_head.py 100000 0,3 2>&1 | grep -v amdgpu > $O/head_ab.txt
 AB_REPS=6 timeout 600 python scratch/ab_tail.py 100000 0,2 2>&1 | grep -v amdgpu > $O/tail_ab.txt
-MASTER_ADDR=127.0.0.1 MASTER_PORT=29577 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 400 python bench.py --force-sharded --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_sharded_world1.json
+MASTER_ADDR=127.0.0.1 MASTER_PORT=29577 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 400 python bench.py --full --force-sharded --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_sharded_world1.json
 bash scratch/sharded_trace.sh > $O/sharded_trace.txt 2>&1
 ls -la $O

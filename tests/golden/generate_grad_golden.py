@@ -7,7 +7,7 @@ One training step of `Trainer.train` (solver/ml_solver/trainer.py:68-84) without
 `Losses.calculate_unsupervised_loss` (solver/ml_solver/losses.py:48-116, imported unchanged), `loss.backward()`.
 Everything in float64, single thread.
 
-Stored (ref_grads.npz)
+Stored (ref_grads.npz, written in parts under 1 MiB each -- ref_grads.part<k>.npz -- that tests/golden_util.load_npz merges)
   small.*   256-node induced sub-graph of the labyrinth graph, depth 3 (the residual skip is live at layer 2), width 32:
             probs, loss, d loss / d probs, and the gradient of EVERY parameter (rounded once to float32).
   laby.*    the full labyrinth graph, depth 20: probs, loss, d loss / d probs; for every parameter the triple
@@ -113,9 +113,9 @@ def main():
             out[f"tiny.grad.{k}"] = v.astype(np.float32)
     fp32_spread(out, "tiny", TilinGNN2, Losses, tg, tiny["adj_attr"].shape[1], 3, 3, 3, grads)
     print("tiny: loss", loss)
-    path = os.path.join(HERE, "ref_grads.npz")
-    np.savez_compressed(path, **out)
-    print(f"ref_grads.npz: {os.path.getsize(path) / 1024:.1f} KiB")
+    from tests.golden_util import save_npz_parts
+    for path in save_npz_parts("ref_grads.npz", out):
+        print(f"{os.path.basename(path)}: {os.path.getsize(path) / 1024:.1f} KiB")
 
 
 if __name__ == "__main__":

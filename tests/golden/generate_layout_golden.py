@@ -20,11 +20,15 @@ Stored
                            with edge lists (`small.direct.*`).
   complete_graph_small.pkl the first 150 tiles of data/labyrinth/complete_graph_ring9.pkl and the edges among them,
                            written by the reference's own save_current_state (same schema, same classes by name).
+  complete_graph_ring9.pkl.gz
+                           data/labyrinth/complete_graph_ring9.pkl itself, gzipped (what the producer tests on the full graph load).
   layout_with_features.pkl / layout_reindex_only.pkl
                            written by the reference's write_brick_layout_data for the 200-tile super set.
 """
+import gzip
 import os
 import pickle
+import shutil
 import struct
 import sys
 import types
@@ -148,6 +152,9 @@ def main():
     for key, arr in (("x", x), ("col", ci), ("col_attr", cf), ("adj", ai), ("adj_attr", af)):
         out[f"small.direct.{key}"] = np.asarray(arr)
     np.savez_compressed(os.path.join(HERE, "ref_layouts.npz"), **out)
+    with open(os.path.join(REF, "data/labyrinth/complete_graph_ring9.pkl"), "rb") as src, \
+            gzip.GzipFile(os.path.join(HERE, "complete_graph_ring9.pkl.gz"), "wb", mtime=0) as dst:
+        shutil.copyfileobj(src, dst)
 
     # --- brick-layout files, written by the reference's own writer
     tiles = cases["first200"]

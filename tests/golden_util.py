@@ -1,4 +1,5 @@
 """Loaders for the committed golden fixtures (tests/golden/*.npz, made by generate_golden.py)."""
+import glob
 import os
 
 import numpy as np
@@ -30,5 +31,49 @@ def graph_tensors(g, dtype=torch.float32, device="cpu"):
             torch.from_numpy(np.asarray(g["col_attr"])).to(dtype).to(device))
 
 
+class _NpzParts(dict):
+    """The members of a fixture stored in parts, merged; `files` as np.load's NpzFile has it."""
+
+    @property
+    def files(self):
+        return list(self)
+
+
+def part_paths(name):
+    stem = os.path.join(GOLDEN, name[:-len(".npz")])
+    return sorted(glob.glob(stem + ".part*.npz"), key=lambda p: int(p[len(stem) + len(".part"):-len(".npz")]))
+
+
+def save_npz_parts(name, arrays, limit=900 * 1024):
+    """np.savez_compressed of `arrays` as contiguous runs of its members of at most `limit` bytes each, <stem>.part<k>.npz (no
+    committed file may exceed 1 MiB); load_npz(name) merges them again."""
+    for p in part_paths(name):
+        os.remove(p)
+    runs, size = [[]], 0
+    for key, a in arrays.items():
+        cost = np.asarray(a).nbytes + 512 + 2 * len(key)          # (+ the member's .npy header and zip directory entries)
+        if runs[-1] and size + cost > limit:
+            runs.append([])
+            size = 0
+        runs[-1].append(key)
+        size += cost
+    paths = []
+    for k, run in enumerate(runs):
+        paths.append(os.path.join(GOLDEN, f"{name[:-len('.npz')]}.part{k}.npz"))
+        np.savez_compressed(paths[-1], **{key: arrays[key] for key in run})
+        assert os.path.getsize(paths[-1]) < 2 ** 20, (paths[-1], run)
+    return paths
+
+
 def load_npz(name):
-    return np.load(os.path.join(GOLDEN, name))
+    path = os.path.join(GOLDEN, name)
+    if os.path.exists(path):
+        return np.load(path)
+    parts = part_paths(name)
+    if not parts:
+        raise FileNotFoundError(path)
+    merged = _NpzParts()
+    for p in parts:
+        with np.load(p) as z:
+            merged.update((k, z[k]) for k in z.files)
+    return merged

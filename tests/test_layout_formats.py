@@ -3,6 +3,7 @@
 Expected values come from the REFERENCE's own code (tests/golden/generate_layout_golden.py): its loader, its
 producer, its writer.  Everything here is exact: same values, same dtypes, same shapes.
 """
+import gzip
 import os
 import pickle
 import pickletools
@@ -19,7 +20,7 @@ from tilingnn_amd.tiling.tile_graph import TileGraph
 from tilingnn_amd.util import data_util as du
 
 SMALL = os.path.join(GOLDEN, "complete_graph_small.pkl")
-FULL = "/root/reference/data/labyrinth/complete_graph_ring9.pkl"      # build container only
+FULL = os.path.join(GOLDEN, "complete_graph_ring9.pkl.gz")      # data/labyrinth/complete_graph_ring9.pkl of the reference, gzipped
 KEYS = ("x", "col", "col_attr", "adj", "adj_attr")
 
 
@@ -112,11 +113,18 @@ def test_generate_brick_layout_data_with_edge_lists():
         du.generate_brick_layout_data(g, list(range(80)), [(0, 1)], [(0, 0)])      # (0, 0) is not an edge of the graph
 
 
-@pytest.mark.skipif(not os.path.exists(FULL), reason="the full labyrinth pickle lives in /root/reference")
+@pytest.fixture(scope="module")
+def full_pickle(tmp_path_factory):
+    path = str(tmp_path_factory.mktemp("labyrinth") / "complete_graph_ring9.pkl")
+    with gzip.open(FULL, "rb") as src, open(path, "wb") as dst:
+        shutil.copyfileobj(src, dst)
+    return path
+
+
 @pytest.mark.parametrize("case", ["first200", "random400", "all", "isolated", "shuffled60"])
-def test_producer_matches_reference_on_the_full_graph(case):
+def test_producer_matches_reference_on_the_full_graph(case, full_pickle):
     g = TileGraph(2)
-    g.load_graph_state(FULL, sidecar=False)
+    g.load_graph_state(full_pickle, sidecar=False)
     ref = load_npz("ref_layouts.npz")
     assert len(g.tiles) == int(ref["n_tiles"]) and len(g.adj_edges) == int(ref["n_adj_edges"])
     _same(g.arrays.tile_areas, ref["tile_areas"], "areas")
