@@ -773,8 +773,8 @@ int tgnn_transpose(const float *w, int32_t rows, int32_t cols, float *out, tgnn_
  * product of NNConv: the T type matrices and, behind them, the root matrix) */
 int tgnn_swap_leading(const float *in, int32_t da, int32_t db, int32_t dc, float *out, int32_t out_da,
                       tgnn_stream_t stream);
-/* z = (1 + eps) BN_in(a) + sum over the row's CSR slots of BN_in(a)[src] (width 32): the input of GINConv's MLP; on the
- * transposed collision graph, the adjoint of that aggregation. */
+/* z = (1 + eps) BN_in(a) + sum over the row's CSR slots of BN_in(a)[src] (width c = 32 or 64; z has rows of c floats): the
+ * input of GINConv's MLP; on the transposed collision graph, the adjoint of that aggregation. */
 int tgnn_gin_aggregate(const float *a, int64_t lda, const float *in_stat, const int32_t *rowptr, const int32_t *col_src,
                        const float *eps, int64_t n_nodes, int32_t c, float *z, tgnn_stream_t stream);
 /* out = d * t * (1 - t): derivative of torch.nn.Sigmoid given its output t (layers/util.py:34) */
@@ -782,7 +782,8 @@ int tgnn_sigmoid_bwd(const float *d, int64_t ld_d, const float *t, int64_t ld_t,
                      int64_t ld_o, tgnn_stream_t stream);
 int tgnn_add_into(const float *src, int64_t ld_s, int64_t n_rows, int32_t c, float *dst, int64_t ld_d,
                   tgnn_stream_t stream);
-/* scratch for tgnn_colsum / tgnn_bn_bwd_reduce / tgnn_merge_bwd_reduce on matrices of `width` columns */
+/* scratch for tgnn_colsum / tgnn_bn_bwd_reduce / tgnn_merge_bwd_reduce on matrices of `width` columns (the merge's six
+ * column-sum sets: 6 * width doubles per partial row) */
 size_t tgnn_reduce_workspace_bytes(int32_t width);
 /* out[c] = sum_r x[r][c]: the bias gradient of a Linear (layers/util.py:32) */
 int tgnn_colsum(const float *x, int64_t ld, int64_t n_rows, int32_t c, float *out, void *ws, size_t ws_bytes,
@@ -799,8 +800,9 @@ int tgnn_bn_bwd_apply(const float *dy, int64_t ld_dy, const float *a, int64_t ld
                       int64_t n_rows, int32_t f, int32_t act, float *dz, int64_t ld_dz, const float *row_scale,
                       float *scaled, int64_t ld_scaled, tgnn_stream_t stream);
 /* Backward of the branch merge h = BN1(a1) * BN2(a2) (+ resid) (TilinGNN.py:64-71) and the reductions of both
- * BatchNorms behind it (width 32):  dy1 = dh * BN2(a2);  dy2 = dh * BN1(a1) (+ carry: the gradient arriving at
- * BN2(a2) from the next CollConv, TilinGNN.py:63);  resid_grad (may be NULL) += dh. */
+ * BatchNorms behind it (width c = 32 or 64; a1, a2, carry, dy1, dy2 rows of c floats):  dy1 = dh * BN2(a2);
+ * dy2 = dh * BN1(a1) (+ carry: the gradient arriving at BN2(a2) from the next CollConv, TilinGNN.py:63);
+ * resid_grad (may be NULL) += dh.  coef1 / coef2: float [2][c]. */
 int tgnn_merge_bwd_reduce(const float *dh, int64_t ld_dh, const float *a1, const float *stat1, const float *a2,
                           const float *stat2, const float *carry, int64_t n_rows, int32_t c, float eps1, float eps2,
                           float *dy1, float *dy2, float *resid_grad, int64_t ld_resid, float *coef1, float *dgamma1,
@@ -813,6 +815,12 @@ int tgnn_merge_bwd_reduce(const float *dh, int64_t ld_dh, const float *a1, const
 size_t tgnn_wgrad_workspace_bytes(int64_t n_rows, int32_t cout, int32_t cin);
 int tgnn_wgrad(const float *dz, int64_t ld_dz, const float *x, int64_t ld_x, int64_t x_kblock_stride, int64_t n_rows,
                int32_t cout, int32_t cin, float *out, float *dbias, void *ws, size_t ws_bytes, tgnn_stream_t stream);
+/* The same over a SLOT-MAJOR x [S][n_rows][slot_width] read as the concatenation of its S slots (the skip-connection
+ * buffer, TilinGNN.py:74; cin = S * slot_width): feature k of row r at
+ * x[(k / slot_width) * slot_stride + r * slot_width + k % slot_width]; slot_width 32 or 64 (the network width).
+ * Workspace: tgnn_wgrad_workspace_bytes(n_rows, cout, cin). */
+int tgnn_wgrad_slots(const float *dz, int64_t ld_dz, const float *x, int32_t slot_width, int64_t slot_stride, int64_t n_rows,
+                     int32_t cout, int32_t cin, float *out, float *dbias, void *ws, size_t ws_bytes, tgnn_stream_t stream);
 /* Backward of a 3-layer sigmoid MLP without BatchNorm (GraphConv's edge MLP, edge_conv.py:17-18; GINConv's MLP,
  * coll_conv.py:14-18) in one call: hidden activations re-derived from x [n, d0]; per layer dpre = d t (1 - t),
  * dW = dpre^T . in, db, d_in = dpre . W.  w_k [d_k, d_{k-1}]; t3 = the MLP's output [n, d3]; d_out: gradient at t3;
@@ -823,7 +831,8 @@ int tgnn_sigmoid_mlp_bwd(const float *x, int64_t n_rows, int32_t d0, int32_t d1,
                          const float *d_out, int64_t ld_dout, float *dw1, float *db1, float *dw2, float *db2, float *dw3,
                          float *db3, float *dx, void *ws, size_t ws_bytes, tgnn_stream_t stream);
 /* NNConv backward building block (edge_conv.py:25; PyG NNConv: message = x_j . W_e, mean, + x . root):
- * out [n_nodes][(n_types + 1) * 32]: slot t < n_types = sum over the row's CSR slots of type t of rows[src];
+ * out [n_nodes][(n_types + 1) * c], c = 32 or 64 (the network width; n_types <= 63): slot t < n_types = sum over the
+ * row's CSR slots of type t of rows[src];
  * slot n_types = own[j] * root_scale[j] (NULL: 1).  Run over the TRANSPOSED adjacency CSR on g = dz / deg (root slot = dz) it
  * makes both adjoints dense products:  d x = slots . [W_t^T; root^T]  and  [d W_t; d root] = x^T . slots. */
 int tgnn_nnconv_type_sum(const float *rows, int64_t ld_rows, const float *own, int64_t ld_own, const float *root_scale,

@@ -188,6 +188,7 @@ def _load() -> C.CDLL:
                                             p, sz, p]),
         "tgnn_wgrad_workspace_bytes": (sz, [i64, i32, i32]),
         "tgnn_wgrad": (C.c_int, [p, i64, p, i64, i64, i64, i32, i32, p, p, p, sz, p]),
+        "tgnn_wgrad_slots": (C.c_int, [p, i64, p, i32, i64, i64, i32, i32, p, p, p, sz, p]),
         "tgnn_sigmoid_mlp_bwd_workspace_bytes": (sz, [i64, i32, i32, i32, i32]),
         "tgnn_sigmoid_mlp_bwd": (C.c_int, [p, i64, i32, i32, i32, i32, p, p, p, p, p, p, p, i64, p, p, p, p, p, p, p, p, sz,
                                            p]),
@@ -245,7 +246,7 @@ EXPORTED_SYMBOLS = (
     "tgnn_rows_gather", "tgnn_rows_scatter", "tgnn_unsupervised_loss_workspace_bytes", "tgnn_unsupervised_loss", "tgnn_solution_score_sums",
     "tgnn_sublayout_workspace_bytes", "tgnn_sublayout_compact", "tgnn_greedy_round_workspace_bytes", "tgnn_greedy_round", "tgnn_greedy_finish_max_nodes", "tgnn_greedy_finish", "tgnn_shard_alive_rows",
     "tgnn_transpose", "tgnn_swap_leading", "tgnn_gin_aggregate", "tgnn_sigmoid_bwd", "tgnn_add_into", "tgnn_reduce_workspace_bytes", "tgnn_colsum",
-    "tgnn_bn_bwd_reduce", "tgnn_bn_bwd_apply", "tgnn_merge_bwd_reduce", "tgnn_wgrad_workspace_bytes", "tgnn_wgrad",
+    "tgnn_bn_bwd_reduce", "tgnn_bn_bwd_apply", "tgnn_merge_bwd_reduce", "tgnn_wgrad_workspace_bytes", "tgnn_wgrad", "tgnn_wgrad_slots",
     "tgnn_sigmoid_mlp_bwd_workspace_bytes", "tgnn_sigmoid_mlp_bwd",
     "tgnn_nnconv_type_sum", "tgnn_csr_degree", "tgnn_unsupervised_loss_bwd",
     "tgnn_f32_to_bf16", "tgnn_nnconv64_image_elems", "tgnn_nnconv64_bf16_fwd", "tgnn_nnconv64_bf16_eg_fwd", "tgnn_gin64_bf16_fwd", "tgnn_collconv64_bf16_fwd", "tgnn_merge_bf16_fwd",

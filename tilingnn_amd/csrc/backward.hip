@@ -220,33 +220,36 @@ __global__ void bn_bwd_apply_kernel(const float *__restrict__ dy, int64_t ld_dy,
 // ------------------------------------------------------------------------------------------------ merge backward
 // h_out = BN1(a1) * BN2(a2) (+ resid).  Given dh (row stride ld_dh):  dy1 = dh y2, dy2 = dh y1 (+ carry),
 // resid_grad (may be NULL, row stride ld_r) += dh, and the six column sums the two BatchNorm backward passes need:
-// partial [P][2][3][32].  Width 32: 8 threads x float4 per row.
+// partial [P][2][3][C].  C / 4 threads x float4 per row (width 32: 8, width 64: 16), 256 / (C / 4) row lanes per block.
+template <int C>
 __global__ __launch_bounds__(256) void merge_bwd_reduce_kernel(
     const float *__restrict__ dh, int64_t ld_dh, const float *__restrict__ a1, const float *__restrict__ stat1,
     const float *__restrict__ a2, const float *__restrict__ stat2, const float *__restrict__ carry, int64_t n,
     int64_t rows_per_block, float *__restrict__ dy1, float *__restrict__ dy2, float *__restrict__ resid_grad,
     int64_t ld_r, double *__restrict__ partial) {
-    const int cg = threadIdx.x & 7, rl = threadIdx.x >> 3;          // channels 4 cg .. 4 cg + 3, row lane 0..31
+    constexpr int CG = C / 4, RL = 256 / CG;
+    static_assert(CG <= 64 && (CG & (CG - 1)) == 0, "C / 4 threads per row, a power of two within one wave");
+    const int cg = threadIdx.x % CG, rl = threadIdx.x / CG;      // channels 4 cg .. 4 cg + 3, row lane 0 .. RL - 1
     const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
     const int64_t r1 = r0 + rows_per_block < n ? r0 + rows_per_block : n;
     float m1h[4], m1l[4], g1[4], b1[4], m2h[4], m2l[4], g2[4], b2[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int ch = 4 * cg + k;
-        m1h[k] = stat1[ch]; m1l[k] = stat1[32 + ch]; g1[k] = stat1[64 + ch]; b1[k] = stat1[96 + ch];
-        m2h[k] = stat2[ch]; m2l[k] = stat2[32 + ch]; g2[k] = stat2[64 + ch]; b2[k] = stat2[96 + ch];
+        m1h[k] = stat1[ch]; m1l[k] = stat1[C + ch]; g1[k] = stat1[2 * C + ch]; b1[k] = stat1[3 * C + ch];
+        m2h[k] = stat2[ch]; m2l[k] = stat2[C + ch]; g2[k] = stat2[2 * C + ch]; b2[k] = stat2[3 * C + ch];
     }
     double s[6][4];
 #pragma unroll
     for (int q = 0; q < 6; ++q)
 #pragma unroll
         for (int k = 0; k < 4; ++k) s[q][k] = 0.0;
-    for (int64_t r = r0 + rl; r < r1; r += 32) {
+    for (int64_t r = r0 + rl; r < r1; r += RL) {
         const float4 d4 = *reinterpret_cast<const float4 *>(dh + r * ld_dh + 4 * cg);
-        const float4 x1 = *reinterpret_cast<const float4 *>(a1 + r * 32 + 4 * cg);
-        const float4 x2 = *reinterpret_cast<const float4 *>(a2 + r * 32 + 4 * cg);
+        const float4 x1 = *reinterpret_cast<const float4 *>(a1 + r * C + 4 * cg);
+        const float4 x2 = *reinterpret_cast<const float4 *>(a2 + r * C + 4 * cg);
         float4 cr = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (carry) cr = *reinterpret_cast<const float4 *>(carry + r * 32 + 4 * cg);
+        if (carry) cr = *reinterpret_cast<const float4 *>(carry + r * C + 4 * cg);
         const float dv[4] = {d4.x, d4.y, d4.z, d4.w}, v1[4] = {x1.x, x1.y, x1.z, x1.w}, v2[4] = {x2.x, x2.y, x2.z, x2.w};
         const float cv[4] = {cr.x, cr.y, cr.z, cr.w};
         float o1[4], o2[4];
@@ -259,8 +262,8 @@ __global__ __launch_bounds__(256) void merge_bwd_reduce_kernel(
             s[0][k] += (double)o1[k]; s[1][k] += (double)o1[k] * (double)c1; s[2][k] += (double)c1 * (double)c1;
             s[3][k] += (double)o2[k]; s[4][k] += (double)o2[k] * (double)c2; s[5][k] += (double)c2 * (double)c2;
         }
-        *reinterpret_cast<float4 *>(dy1 + r * 32 + 4 * cg) = make_float4(o1[0], o1[1], o1[2], o1[3]);
-        *reinterpret_cast<float4 *>(dy2 + r * 32 + 4 * cg) = make_float4(o2[0], o2[1], o2[2], o2[3]);
+        *reinterpret_cast<float4 *>(dy1 + r * C + 4 * cg) = make_float4(o1[0], o1[1], o1[2], o1[3]);
+        *reinterpret_cast<float4 *>(dy2 + r * C + 4 * cg) = make_float4(o2[0], o2[1], o2[2], o2[3]);
         if (resid_grad) {
             float4 *rg = reinterpret_cast<float4 *>(resid_grad + r * ld_r + 4 * cg);
             float4 old = *rg;
@@ -268,29 +271,28 @@ __global__ __launch_bounds__(256) void merge_bwd_reduce_kernel(
             *rg = old;
         }
     }
-    // fixed tree: over the 8 row lanes of a wave (lane bits 3..5), then over the 4 waves through LDS
+    // fixed tree: over the row lanes of a wave (lane bits log2(CG) .. 5), then over the 4 waves through LDS
 #pragma unroll
     for (int q = 0; q < 6; ++q)
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             double v = s[q][k];
-            v += __shfl_xor(v, 8);
-            v += __shfl_xor(v, 16);
-            v += __shfl_xor(v, 32);
+#pragma unroll
+            for (int d = CG; d < 64; d <<= 1) v += __shfl_xor(v, d);
             s[q][k] = v;
         }
-    __shared__ double sh[4][6][32];
+    __shared__ double sh[4][6][C];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane < 8) {
+    if (lane < CG) {
 #pragma unroll
         for (int q = 0; q < 6; ++q)
 #pragma unroll
             for (int k = 0; k < 4; ++k) sh[wave][q][4 * lane + k] = s[q][k];
     }
     __syncthreads();
-    if (threadIdx.x < 192) {
-        const int q = threadIdx.x / 32, ch = threadIdx.x % 32;
-        partial[((int64_t)blockIdx.x * 6 + q) * 32 + ch] = (sh[0][q][ch] + sh[1][q][ch]) + (sh[2][q][ch] + sh[3][q][ch]);
+    for (int e = threadIdx.x; e < 6 * C; e += 256) {
+        const int q = e / C, ch = e % C;
+        partial[((int64_t)blockIdx.x * 6 + q) * C + ch] = (sh[0][q][ch] + sh[1][q][ch]) + (sh[2][q][ch] + sh[3][q][ch]);
     }
 }
 
@@ -298,12 +300,12 @@ __global__ __launch_bounds__(256) void merge_bwd_reduce_kernel(
 // out[co][ci] = sum_r dz[r][co] * x[r][ci]  on v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulation per
 // wave over its rows, fp64 across waves' partial tiles in the final pass).  Block = 4 waves over one (32 TM) x (32 TN)
 // output tile and one row range; wave w takes rows r0 + 2w + 8i (+ lane >> 5).
-// x element (r, k): x[(k / 32) * x_kblock_stride + r * ld_x + k % 32] when x_kblock_stride != 0 (the slot-major
-// skip buffer), else x[r * ld_x + k].
+// x element (r, k): x[(k / W) * x_kblock_stride + r * ld_x + k % W] with W = 1 << x_block_shift when x_kblock_stride != 0
+// (the slot-major skip buffer, slots of W = 32 or 64 columns), else x[r * ld_x + k].
 template <int TM, int TN>
 __global__ __launch_bounds__(256) void wgrad_kernel(const float *__restrict__ dz, int64_t ld_dz,
                                                     const float *__restrict__ x, int64_t ld_x, int64_t x_kblock_stride,
-                                                    int64_t n, int cout, int cin, int64_t rows_per_block,
+                                                    int x_block_shift, int64_t n, int cout, int cin, int64_t rows_per_block,
                                                     float *__restrict__ partial, int64_t partial_stride, int with_bias,
                                                     float *__restrict__ direct_bias) {
     // direct_bias != NULL: there is ONE row range; `partial` is the result itself and the bias gradient goes to direct_bias
@@ -328,7 +330,8 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const float *__restrict__ dz
     for (int j = 0; j < TN; ++j) {
         const int ci = ci0 + 32 * j + (lane & 31);
         xok[j] = ci < cin;
-        xoff[j] = x_kblock_stride ? (int64_t)(ci >> 5) * x_kblock_stride + (ci & 31) : (int64_t)ci;
+        xoff[j] = x_kblock_stride ? (int64_t)(ci >> x_block_shift) * x_kblock_stride + (ci & ((1 << x_block_shift) - 1))
+                                  : (int64_t)ci;
     }
 #pragma unroll
     for (int i = 0; i < TM; ++i) zok[i] = co0 + 32 * i + (lane & 31) < cout;
@@ -464,6 +467,43 @@ __global__ __launch_bounds__(256) void nnconv_type_sum_kernel(const float *__res
         acc[n_types * 32 + lane] = own[j * ld_own + lane] * rs;
         float *o = out + j * ld_out;
         for (int t = 0; t <= n_types; ++t) o[t * 32 + lane] = acc[t * 32 + lane];
+    }
+}
+
+// Width 64: a whole wave per destination row (lane = channel), its T + 1 accumulator rows in LDS (16 KiB per row at T = 63:
+// four rows per block keep a block within 64 KiB and two blocks on a CU), four gathers in flight.  Bytes per call:
+// 256 E (the gathered rows) + 4 (T + 1) 64 N (the result) + 256 N (own rows) + 8 E + 8 N (CSR, types, scales).
+constexpr int kTs64Rows = 4;                // rows (waves) per block
+__global__ __launch_bounds__(256) void nnconv_type_sum64_kernel(const float *__restrict__ rows, int64_t ld_rows,
+                                                                const float *__restrict__ own, int64_t ld_own,
+                                                                const float *__restrict__ root_scale,
+                                                                const int32_t *__restrict__ rowptr,
+                                                                const int32_t *__restrict__ src,
+                                                                const int32_t *__restrict__ type, int64_t n, int n_types,
+                                                                float *__restrict__ out) {
+    extern __shared__ float acc_all[];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    float *acc = acc_all + (int64_t)wv * (n_types + 1) * 64;
+    const int64_t ld_out = (int64_t)(n_types + 1) * 64;
+    for (int64_t j = (int64_t)blockIdx.x * kTs64Rows + wv; j < n; j += (int64_t)gridDim.x * kTs64Rows) {
+        for (int t = 0; t <= n_types; ++t) acc[t * 64 + lane] = 0.f;
+        const int e0 = rowptr[j], e1 = rowptr[j + 1];
+        int e = e0;
+        for (; e + 4 <= e1; e += 4) {
+            const int s0 = src[e], s1 = src[e + 1], s2 = src[e + 2], s3 = src[e + 3];
+            const int t0 = type[e], t1 = type[e + 1], t2 = type[e + 2], t3 = type[e + 3];
+            const float v0 = rows[(int64_t)s0 * ld_rows + lane], v1 = rows[(int64_t)s1 * ld_rows + lane];
+            const float v2 = rows[(int64_t)s2 * ld_rows + lane], v3 = rows[(int64_t)s3 * ld_rows + lane];
+            acc[t0 * 64 + lane] += v0;
+            acc[t1 * 64 + lane] += v1;
+            acc[t2 * 64 + lane] += v2;
+            acc[t3 * 64 + lane] += v3;
+        }
+        for (; e < e1; ++e) acc[type[e] * 64 + lane] += rows[(int64_t)src[e] * ld_rows + lane];
+        const float rs = root_scale ? root_scale[j] : 1.0f;
+        acc[n_types * 64 + lane] = own[j * ld_own + lane] * rs;
+        float *o = out + j * ld_out;
+        for (int t = 0; t <= n_types; ++t) o[t * 64 + lane] = acc[t * 64 + lane];
     }
 }
 
@@ -657,8 +697,8 @@ int tgnn_bn_bwd_apply(const float *dy, int64_t ld_dy, const float *a, int64_t ld
     return TGNN_OK;
 }
 
-/* Backward of the branch merge + the reductions of both BatchNorms behind it (width 32).
- * coef1 / coef2: float [2][32] each; dgamma / dbeta per branch. */
+/* Backward of the branch merge + the reductions of both BatchNorms behind it (width 32 or 64).
+ * coef1 / coef2: float [2][c] each; dgamma / dbeta per branch. */
 int tgnn_merge_bwd_reduce(const float *dh, int64_t ld_dh, const float *a1, const float *stat1, const float *a2,
                           const float *stat2, const float *carry, int64_t n_rows, int32_t c, float eps1, float eps2,
                           float *dy1, float *dy2, float *resid_grad, int64_t ld_resid, float *coef1, float *dgamma1,
@@ -666,24 +706,28 @@ int tgnn_merge_bwd_reduce(const float *dh, int64_t ld_dh, const float *a1, const
                           tgnn_stream_t stream) {
     DeviceGuard guard__(stream);
     TGNN_CHECK_ARG(n_rows >= 1, "shape");
-    if (c != 32) {
-        set_error("tgnn_merge_bwd_reduce: width 32 only");
+    if (c != 32 && c != 64) {
+        set_error("tgnn_merge_bwd_reduce: width 32 or 64 only");
         return TGNN_ERR_UNSUPPORTED;
     }
     TGNN_CHECK_ARG(dh && a1 && a2 && stat1 && stat2 && dy1 && dy2 && coef1 && coef2, "null pointer");
     TGNN_CHECK_ARG(ld_dh % 4 == 0 && (!resid_grad || ld_resid % 4 == 0), "row strides must be multiples of 4");
     const int parts = red_partials(n_rows);
-    TGNN_CHECK_ARG(ws && ws_bytes >= (size_t)parts * 6 * 32 * sizeof(double), "workspace");
+    TGNN_CHECK_ARG(ws && ws_bytes >= (size_t)parts * 6 * c * sizeof(double), "workspace");
     hipStream_t s = (hipStream_t)stream;
     const int64_t rpb = ((n_rows + parts - 1) / parts + 31) / 32 * 32;
     const int used = (int)((n_rows + rpb - 1) / rpb);
     double *partial = static_cast<double *>(ws);
-    hipLaunchKernelGGL(merge_bwd_reduce_kernel, dim3(used), dim3(256), 0, s, dh, ld_dh, a1, stat1, a2, stat2, carry, n_rows,
-                       rpb, dy1, dy2, resid_grad, ld_resid, partial);
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(32 / kFinCols), dim3(256), 0, s, partial, (int64_t)6 * 32, (int64_t)0, used,
-                       32, n_rows, eps1, coef1, dgamma1, dbeta1);
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(32 / kFinCols), dim3(256), 0, s, partial, (int64_t)6 * 32, (int64_t)3 * 32,
-                       used, 32, n_rows, eps2, coef2, dgamma2, dbeta2);
+    if (c == 32)
+        hipLaunchKernelGGL(merge_bwd_reduce_kernel<32>, dim3(used), dim3(256), 0, s, dh, ld_dh, a1, stat1, a2, stat2, carry,
+                           n_rows, rpb, dy1, dy2, resid_grad, ld_resid, partial);
+    else
+        hipLaunchKernelGGL(merge_bwd_reduce_kernel<64>, dim3(used), dim3(256), 0, s, dh, ld_dh, a1, stat1, a2, stat2, carry,
+                           n_rows, rpb, dy1, dy2, resid_grad, ld_resid, partial);
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(c / kFinCols), dim3(256), 0, s, partial, (int64_t)6 * c, (int64_t)0, used,
+                       c, n_rows, eps1, coef1, dgamma1, dbeta1);
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(c / kFinCols), dim3(256), 0, s, partial, (int64_t)6 * c, (int64_t)3 * c,
+                       used, c, n_rows, eps2, coef2, dgamma2, dbeta2);
     TGNN_CHECK_LAUNCH();
     return TGNN_OK;
 }
@@ -695,14 +739,10 @@ size_t tgnn_wgrad_workspace_bytes(int64_t n_rows, int32_t cout, int32_t cin) {
     return align_up((size_t)parts * ((size_t)cout * cin + cout) * sizeof(float), 256);
 }
 
-/* out [cout, cin] (row-major: torch's Linear.weight layout) = dz^T . x over n_rows rows;
- * dbias [cout] (may be NULL) = column sums of dz, from the same pass. */
-int tgnn_wgrad(const float *dz, int64_t ld_dz, const float *x, int64_t ld_x, int64_t x_kblock_stride, int64_t n_rows,
-               int32_t cout, int32_t cin, float *out, float *dbias, void *ws, size_t ws_bytes, tgnn_stream_t stream) {
-    DeviceGuard guard__(stream);
-    TGNN_CHECK_ARG(n_rows >= 0 && cout >= 1 && cin >= 1, "shape");
-    TGNN_CHECK_ARG(out, "null pointer");
-    hipStream_t s = (hipStream_t)stream;
+namespace tgnn {
+static int wgrad_launch(const float *dz, int64_t ld_dz, const float *x, int64_t ld_x, int64_t x_kblock_stride, int x_block_shift,
+                        int64_t n_rows, int32_t cout, int32_t cin, float *out, float *dbias, void *ws, size_t ws_bytes,
+                        hipStream_t s) {
     if (n_rows == 0) {
         TGNN_CHECK_HIP(hipMemsetAsync(out, 0, sizeof(float) * cout * cin, s));
         if (dbias) TGNN_CHECK_HIP(hipMemsetAsync(dbias, 0, sizeof(float) * cout, s));
@@ -717,9 +757,9 @@ int tgnn_wgrad(const float *dz, int64_t ld_dz, const float *x, int64_t ld_x, int
     TGNN_CHECK_ARG(direct || (ws && ws_bytes >= (size_t)parts * elems * sizeof(float)), "workspace");
     float *partial = direct ? out : static_cast<float *>(ws);
     const dim3 grid(parts, (cout + 32 * tm - 1) / (32 * tm), (cin + 32 * tn - 1) / (32 * tn));
-#define TGNN_WGRAD(TM_, TN_)                                                                                         \
-    hipLaunchKernelGGL((wgrad_kernel<TM_, TN_>), grid, dim3(256), 0, s, dz, ld_dz, x, ld_x, x_kblock_stride, n_rows, cout, \
-                       cin, rpb, partial, elems, dbias ? 1 : 0, direct ? dbias : nullptr)
+#define TGNN_WGRAD(TM_, TN_)                                                                                            \
+    hipLaunchKernelGGL((wgrad_kernel<TM_, TN_>), grid, dim3(256), 0, s, dz, ld_dz, x, ld_x, x_kblock_stride, x_block_shift, \
+                       n_rows, cout, cin, rpb, partial, elems, dbias ? 1 : 0, direct ? dbias : nullptr)
     if (tm == 2 && tn == 2) TGNN_WGRAD(2, 2);
     else if (tm == 2) TGNN_WGRAD(2, 1);
     else if (tn == 2) TGNN_WGRAD(1, 2);
@@ -730,6 +770,30 @@ int tgnn_wgrad(const float *dz, int64_t ld_dz, const float *x, int64_t ld_x, int
                            w_elems, out, dbias);
     TGNN_CHECK_LAUNCH();
     return TGNN_OK;
+}
+}  // namespace tgnn
+
+/* out [cout, cin] (row-major: torch's Linear.weight layout) = dz^T . x over n_rows rows;
+ * dbias [cout] (may be NULL) = column sums of dz, from the same pass. */
+int tgnn_wgrad(const float *dz, int64_t ld_dz, const float *x, int64_t ld_x, int64_t x_kblock_stride, int64_t n_rows,
+               int32_t cout, int32_t cin, float *out, float *dbias, void *ws, size_t ws_bytes, tgnn_stream_t stream) {
+    DeviceGuard guard__(stream);
+    TGNN_CHECK_ARG(n_rows >= 0 && cout >= 1 && cin >= 1, "shape");
+    TGNN_CHECK_ARG(out, "null pointer");
+    return wgrad_launch(dz, ld_dz, x, ld_x, x_kblock_stride, 5, n_rows, cout, cin, out, dbias, ws, ws_bytes, (hipStream_t)stream);
+}
+
+/* The same over a SLOT-MAJOR x [S][n_rows][slot_width] read as the concatenation of its slots (cin = S * slot_width):
+ * feature k of row r at x[(k / slot_width) * slot_stride + r * slot_width + k % slot_width]; slot_width 32 or 64. */
+int tgnn_wgrad_slots(const float *dz, int64_t ld_dz, const float *x, int32_t slot_width, int64_t slot_stride, int64_t n_rows,
+                     int32_t cout, int32_t cin, float *out, float *dbias, void *ws, size_t ws_bytes, tgnn_stream_t stream) {
+    DeviceGuard guard__(stream);
+    TGNN_CHECK_ARG(n_rows >= 0 && cout >= 1 && cin >= 1, "shape");
+    TGNN_CHECK_ARG(slot_width == 32 || slot_width == 64, "slot width 32 or 64");
+    TGNN_CHECK_ARG(cin % slot_width == 0 && slot_stride >= n_rows * slot_width, "slots");
+    TGNN_CHECK_ARG(out, "null pointer");
+    return wgrad_launch(dz, ld_dz, x, slot_width, slot_stride, slot_width == 32 ? 5 : 6, n_rows, cout, cin, out, dbias, ws,
+                        ws_bytes, (hipStream_t)stream);
 }
 
 /* Backward of a 3-layer sigmoid MLP without BatchNorm (GraphConv's edge MLP edge_conv.py:17-18, GINConv's MLP
@@ -817,19 +881,29 @@ int tgnn_sigmoid_mlp_bwd(const float *x, int64_t n_rows, int32_t d0, int32_t d1,
     return TGNN_OK;
 }
 
-/* Per-type sums of gathered rows + the (scaled) own row: out [n_nodes][(n_types + 1) * 32].  rowptr / src / type:
- * a CSR of tgnn_csr_build with the type of every slot. */
+/* Per-type sums of gathered rows + the (scaled) own row: out [n_nodes][(n_types + 1) * c], c = 32 or 64.  rowptr / src /
+ * type: a CSR of tgnn_csr_build with the type of every slot. */
 int tgnn_nnconv_type_sum(const float *rows, int64_t ld_rows, const float *own, int64_t ld_own, const float *root_scale,
                          const int32_t *rowptr, const int32_t *src, const int32_t *type, int64_t n_nodes, int32_t n_types,
                          int32_t c, float *out, tgnn_stream_t stream) {
     DeviceGuard guard__(stream);
     TGNN_CHECK_ARG(n_nodes >= 0 && n_types >= 0, "shape");
-    if (c != 32 || n_types > 63) {
-        set_error("tgnn_nnconv_type_sum: width 32 and at most 63 edge types");
+    if ((c != 32 && c != 64) || n_types > 63) {
+        set_error("tgnn_nnconv_type_sum: width 32 or 64 and at most 63 edge types");
         return TGNN_ERR_UNSUPPORTED;
     }
     if (n_nodes == 0) return TGNN_OK;
     TGNN_CHECK_ARG(rows && own && rowptr && out && (src || n_types == 0), "null pointer");
+    TGNN_CHECK_ARG(ld_rows >= c && ld_own >= c, "row strides");
+    if (c == 64) {
+        const size_t lds = (size_t)kTs64Rows * (n_types + 1) * 64 * sizeof(float);
+        int64_t blocks = (n_nodes + kTs64Rows - 1) / kTs64Rows;
+        if (blocks > 16384) blocks = 16384;
+        hipLaunchKernelGGL(nnconv_type_sum64_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, rows, ld_rows,
+                           own, ld_own, root_scale, rowptr, src, type, n_nodes, n_types, out);
+        TGNN_CHECK_LAUNCH();
+        return TGNN_OK;
+    }
     const size_t lds = (size_t)kTsRows * (n_types + 1) * 32 * sizeof(float);
     int64_t blocks = (n_nodes + kTsRows - 1) / kTsRows;
     if (blocks > 8192) blocks = 8192;

@@ -713,6 +713,14 @@ static int forward_impl(const tgnn_model_dims *dims, const void *const *params_h
             return TGNN_ERR_UNSUPPORTED;                       // (the workspace is aligned: cannot happen)
         }
         prof.begin(3);
+        if (keep && c != 32) {
+            // training at width 64: the generic kernel (the one inference runs at this width) also stores the aggregate, keep->u
+            TGNN_TRY(gin_generic_fwd_keep(gin_in, c, gin_stat, graph->col_rowptr, graph->col_src, P.f(b + 13), P.f(b + 14),
+                                          P.f(b + 15), P.f(b + 16), P.f(b + 17), P.f(b + 18), P.f(b + 19), n, c, TGNN_ACT_LEAKY_RELU,
+                                          w.a2[i & 1], w.t0, w.part2, &np2, gs));
+            prof.end();
+            return TGNN_OK;
+        }
         TGNN_TRY(tgnn_gin_fwd(gin_in, c, gin_stat, graph->col_rowptr, graph->col_src, P.f(b + 13), P.f(b + 14),
                               P.f(b + 15), P.f(b + 16), P.f(b + 17), P.f(b + 18), P.f(b + 19), n, c,
                               TGNN_ACT_LEAKY_RELU, w.a2[i & 1], w.t0, w.part2, &np2, gs));

@@ -84,7 +84,7 @@ __device__ __forceinline__ void gin_tile_gather(const GinGraph &A, int64_t tile,
     const int64_t n = A.n;
     const __amdgpu_buffer_rsrc_t a_rs = rsrc_of(src);
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f), one4 = make_float4(1.f, 1.f, 1.f, 1.f);
-    // x = BatchNorm of the previous layer's pre-BN rows, folded into the sum as in gin32_aggregate_kernel (gin.hip)
+    // x = BatchNorm of the previous layer's pre-BN rows, folded into the sum as in gin_aggregate_kernel (gin.hip)
     const float4 mhi = use_stat ? *reinterpret_cast<const float4 *>(st2 + 4 * gp) : zero4;
     const float4 mlo = use_stat ? *reinterpret_cast<const float4 *>(st2 + 32 + 4 * gp) : zero4;
     const float4 gv = use_stat ? *reinterpret_cast<const float4 *>(st2 + 64 + 4 * gp) : one4;

@@ -693,7 +693,7 @@ __global__ __launch_bounds__(kSmallThreads) void forward_layers_small_kernel(Sma
             TGNN_ST2(6)
 #endif
             const bool use_stat = layer > 0;
-            // x = BatchNorm of the previous layer's pre-BN rows, folded into the sum as in gin32_aggregate_kernel
+            // x = BatchNorm of the previous layer's pre-BN rows, folded into the sum as in gin_aggregate_kernel
             const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f), one4 = make_float4(1.f, 1.f, 1.f, 1.f);
             const float4 mhi = use_stat ? *reinterpret_cast<const float4 *>(st + 128 + 4 * gp) : zero4;
             const float4 mlo = use_stat ? *reinterpret_cast<const float4 *>(st + 160 + 4 * gp) : zero4;

@@ -11,7 +11,7 @@
 // normalised collision features are never written to HBM.
 //
 // Two launches per layer:
-//   gin32_aggregate_kernel (HBM-bound gather): 8 lanes x float4 per destination row, CSR by
+//   gin_aggregate_kernel (HBM-bound gather): 8 lanes x float4 per destination row, CSR by
 //            destination, sums in original edge order, XCD-contiguous row ranges; z -> HBM scratch.
 //   gin32_mlp_kernel (MFMA-bound): 32 -> 32 -> 64 -> 32 with sigmoids on v_mfma_f32_32x32x2_f32,
 //            hidden activations wave-private in LDS, LeakyReLU + fp64 BN column sums in the epilogue.
@@ -29,22 +29,23 @@ namespace tgnn {
 
 
 // ------------------------------------------------------------------------------------------
-// K6: neighbourhood sum (HBM-bound gather).  8 lanes x float4 per destination row, rows of one
-// XCD contiguous so that its private L2 holds the activations its gathers touch; no LDS, few
-// registers -> full occupancy hides the rowptr -> col_src -> a[src] dependent-load chain.
+// K6: neighbourhood sum (HBM-bound gather).  C / 4 lanes x float4 per destination row (width 32: 8 lanes, 32 rows per
+// block; width 64: 16 lanes, 16 rows per block), rows of one XCD contiguous so that its private L2 holds the activations
+// its gathers touch; no LDS, few registers -> full occupancy hides the rowptr -> col_src -> a[src] dependent-load chain.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void gin32_aggregate_kernel(
+template <int C>
+__global__ __launch_bounds__(256) void gin_aggregate_kernel(
     const float *__restrict__ a, int64_t lda, const float *__restrict__ in_stat, const int *__restrict__ rowptr,
     const int *__restrict__ col_src, const float *__restrict__ eps_p, int64_t n, float *__restrict__ z) {
-    constexpr int C = 32;
+    constexpr int LPR = C / 4, RPB = 256 / LPR;            // lanes per row, rows per block
 #ifdef TGNN_ABL_EMPTYGIN
     if (n > 0) return;                                     // (timing ablation)
 #endif
-    const int tid = threadIdx.x, g = tid >> 3, q = tid & 7;
-    // block -> (xcd, chunk): XCD x owns rows [n*x/8, n*(x+1)/8), 32 rows per block
+    const int tid = threadIdx.x, g = tid / LPR, q = tid % LPR;
+    // block -> (xcd, chunk): XCD x owns rows [n*x/8, n*(x+1)/8), RPB rows per block
     const int xcd = blockIdx.x & 7, chunk = blockIdx.x >> 3;
     const int64_t r_beg = n * xcd / 8, r_end = n * (xcd + 1) / 8;
-    const int64_t v = r_beg + (int64_t)chunk * 32 + g;
+    const int64_t v = r_beg + (int64_t)chunk * RPB + g;
     if (v >= r_end) return;
     const float one_eps = 1.0f + eps_p[0];
     float4 mhi = make_float4(0, 0, 0, 0), mlo = mhi, gv = make_float4(1, 1, 1, 1), bv = mhi;
@@ -747,7 +748,7 @@ __global__ __launch_bounds__(256) void gin_generic_kernel(
     const int *__restrict__ col_src, const float *__restrict__ eps_p, const float *__restrict__ w1,
     const float *__restrict__ b1, const float *__restrict__ w2, const float *__restrict__ b2,
     const float *__restrict__ w3, const float *__restrict__ b3, int64_t n, int c, int act, float *__restrict__ out,
-    double *__restrict__ bn_partial) {
+    double *__restrict__ bn_partial, float *__restrict__ z_keep) {
     __shared__ float zs[4][256];
     __shared__ float h1s[4][32];
     __shared__ float h2s[4][64];
@@ -764,6 +765,7 @@ __global__ __launch_bounds__(256) void gin_generic_kernel(
             for (int e = beg; e < end; ++e) acc += (a[(int64_t)col_src[e] * lda + k] - mh) - ml;
             const float self = (a[v * lda + k] - mh) - ml;
             zs[wave][k] = fmaf(gg, fmaf(one_eps, self, acc), (one_eps + (float)(end - beg)) * bb);
+            if (z_keep) z_keep[v * c + k] = zs[wave][k];     // the training forward keeps the aggregate the MLP reads
         }
         __builtin_amdgcn_wave_barrier();
         if (lane < 32) {
@@ -843,7 +845,7 @@ int gin32_fwd_folded(const float *a, int64_t lda, const float *in_stat, const in
     }
     const int64_t rows_per_xcd = (n_nodes + 7) / 8;
     const unsigned agg_blocks = (unsigned)(8 * ((rows_per_xcd + 31) / 32));
-    gin32_aggregate_kernel<<<agg_blocks, 256, 0, s>>>(a, lda, in_stat, rowptr, col_src, eps, n_nodes, z_scratch);
+    gin_aggregate_kernel<32><<<agg_blocks, 256, 0, s>>>(a, lda, in_stat, rowptr, col_src, eps, n_nodes, z_scratch);
     return launch_gin32_mlp(z_scratch, w1, b1, w2, b2, w3, b3, n_nodes, act, out, bn_partial, n_partials_host, s, &fin, !need_z);
 }
 }  // namespace tgnn
@@ -868,7 +870,7 @@ extern "C" int tgnn_gin_fwd(const float *a, int64_t lda, const float *in_stat, c
         ((uintptr_t)z_scratch % 16) == 0) {
         const int64_t rows_per_xcd = (n_nodes + 7) / 8;
         const unsigned agg_blocks = (unsigned)(8 * ((rows_per_xcd + 31) / 32));
-        gin32_aggregate_kernel<<<agg_blocks, 256, 0, s>>>(a, lda, in_stat, rowptr, col_src, eps, n_nodes, z_scratch);
+        gin_aggregate_kernel<32><<<agg_blocks, 256, 0, s>>>(a, lda, in_stat, rowptr, col_src, eps, n_nodes, z_scratch);
         // persistent 8-wave blocks; the waves of one SIMD split a contiguous share of 32-row tiles
         blocks = producer_blocks(n_nodes, 16 * kMlpWaves);
         // one block per CU (the weight prologue is paid once per block), minus a few CUs left to the other chain's small
@@ -881,7 +883,7 @@ extern "C" int tgnn_gin_fwd(const float *a, int64_t lda, const float *in_stat, c
     } else {
         blocks = producer_blocks(n_nodes, 4);
         gin_generic_kernel<<<blocks, 256, 0, s>>>(a, lda, in_stat, rowptr, col_src, eps, w1, b1, w2, b2, w3, b3,
-                                                  n_nodes, c, act, out, bn_partial);
+                                                  n_nodes, c, act, out, bn_partial, nullptr);
     }
     if (n_partials_host) *n_partials_host = blocks;
     TGNN_CHECK_LAUNCH();
@@ -929,24 +931,46 @@ int launch_gin32_mlp(const float *z, const float *w1, const float *b1, const flo
 }  // namespace tgnn
 
 /* z = (1 + eps) * BN_in(a) + sum over the row's CSR slots of BN_in(a)[src]  (the input of GINConv's MLP, PyG
- * gin_conv.py; width 32).  Stand-alone because the backward needs it twice per layer: to re-derive the MLP's input, and --
- * on the TRANSPOSED collision graph -- as the adjoint of the aggregation itself. */
+ * gin_conv.py; width 32 or 64).  Stand-alone because the backward needs it twice per layer: to re-derive the MLP's input, and
+ * -- on the TRANSPOSED collision graph -- as the adjoint of the aggregation itself. */
 extern "C" int tgnn_gin_aggregate(const float *a, int64_t lda, const float *in_stat, const int32_t *rowptr,
                                   const int32_t *col_src, const float *eps, int64_t n_nodes, int32_t c, float *z,
                                   tgnn_stream_t stream) {
     DeviceGuard guard__(stream);
     TGNN_CHECK_ARG(n_nodes >= 0, "shape");
-    if (c != 32) {
-        set_error("tgnn_gin_aggregate: width 32 only");
+    if (c != 32 && c != 64) {
+        set_error("tgnn_gin_aggregate: width 32 or 64 only");
         return TGNN_ERR_UNSUPPORTED;
     }
     if (n_nodes == 0) return TGNN_OK;
     TGNN_CHECK_ARG(a && rowptr && eps && z, "null pointer");
     TGNN_CHECK_ARG(lda >= c && lda % 4 == 0 && ((uintptr_t)a % 16) == 0 && ((uintptr_t)z % 16) == 0, "alignment");
+    const int rows_per_block = 256 / (c / 4);
     const int64_t rows_per_xcd = (n_nodes + 7) / 8;
-    const unsigned agg_blocks = (unsigned)(8 * ((rows_per_xcd + 31) / 32));
-    gin32_aggregate_kernel<<<agg_blocks, 256, 0, static_cast<hipStream_t>(stream)>>>(a, lda, in_stat, rowptr, col_src, eps,
-                                                                                    n_nodes, z);
+    const unsigned agg_blocks = (unsigned)(8 * ((rows_per_xcd + rows_per_block - 1) / rows_per_block));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (c == 32)
+        gin_aggregate_kernel<32><<<agg_blocks, 256, 0, s>>>(a, lda, in_stat, rowptr, col_src, eps, n_nodes, z);
+    else
+        gin_aggregate_kernel<64><<<agg_blocks, 256, 0, s>>>(a, lda, in_stat, rowptr, col_src, eps, n_nodes, z);
     TGNN_CHECK_LAUNCH();
     return TGNN_OK;
 }
+
+namespace tgnn {
+// tgnn_gin_fwd's generic branch (any width but the 32 of the MFMA kernels) for the training forward: the same kernel, which also
+// stores the aggregate z it feeds the MLP into z_keep [N][c] -- what the backward re-derives the MLP's activations from
+int gin_generic_fwd_keep(const float *a, int64_t lda, const float *in_stat, const int32_t *rowptr, const int32_t *col_src,
+                         const float *eps, const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
+                         const float *b3, int64_t n_nodes, int32_t c, int32_t act, float *out, float *z_keep, double *bn_partial,
+                         int32_t *n_partials_host, hipStream_t s) {
+    TGNN_CHECK_ARG(n_nodes >= 1 && c >= 1 && c <= 256 && lda >= c, "shape");
+    TGNN_CHECK_ARG(a && rowptr && eps && w1 && b1 && w2 && b2 && w3 && b3 && out && z_keep, "null pointer");
+    const int blocks = producer_blocks(n_nodes, 4);
+    gin_generic_kernel<<<blocks, 256, 0, s>>>(a, lda, in_stat, rowptr, col_src, eps, w1, b1, w2, b2, w3, b3, n_nodes, c, act, out,
+                                              bn_partial, z_keep);
+    if (n_partials_host) *n_partials_host = blocks;
+    TGNN_CHECK_LAUNCH();
+    return TGNN_OK;
+}
+}  // namespace tgnn

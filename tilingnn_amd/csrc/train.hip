@@ -37,6 +37,9 @@ struct Arena {
 };
 
 static const int kFinDims[3] = {256, 128, 64};             // TilinGNN.py:46 hidden_layer_dims
+// tgnn_dense_act_fwd's a_kblock_stride for a row-major A of any width: its K blocks are 32 columns wide (tgnn.h), so block kb
+// starts 32 floats into the row -- the block size, not the network width
+static constexpr int64_t kRowMajorKBlock = 32;
 
 struct BwdBuffers {
     float *dcat, *buf[3], *dy1, *dy2, *dz1, *gsc, *dz2, *sbwd, *wd, *dh1, *dw_in, *dwcat, *rows, *carry[2], *coef, *wt, *zero;
@@ -109,8 +112,8 @@ extern "C" int tgnn_backward(const tgnn_model_dims *dims, const void *const *par
     const int c = dims->network_width, D = dims->network_depth, fx = dims->node_features_dim,
               fe = dims->adj_edge_features_dim, od = dims->output_dim, T = graph->n_types;
     const int64_t n = graph->n_nodes;
-    if (c != 32 || T > 63) {
-        set_error("tgnn_backward: network_width 32 and at most 63 edge types");
+    if ((c != 32 && c != 64) || T > 63) {
+        set_error("tgnn_backward: network_width 32 or 64 and at most 63 edge types");
         return TGNN_ERR_UNSUPPORTED;
     }
     TGNN_CHECK_ARG(n >= 2 && D >= 1 && D <= kMaxDepth, "shape");
@@ -132,7 +135,7 @@ extern "C" int tgnn_backward(const tgnn_model_dims *dims, const void *const *par
     // dz [n, out] . W [out, in] -> dx [n, in]: the forward dense kernel on W^T
     auto dense_dx = [&](const float *dz, const float *w, int out_dim, int in_dim, float *dx) -> int {
         TGNN_TRYB(tgnn_transpose(w, out_dim, in_dim, b.wt, stream));
-        return tgnn_dense_act_fwd(dz, out_dim, 32, nullptr, b.wt, b.zero, n, out_dim, in_dim, TGNN_ACT_NONE, dx, in_dim, nullptr,
+        return tgnn_dense_act_fwd(dz, out_dim, kRowMajorKBlock, nullptr, b.wt, b.zero, n, out_dim, in_dim, TGNN_ACT_NONE, dx, in_dim, nullptr,
                                   nullptr, stream);
     };
     // BatchNorm (train) + LeakyReLU backward of a Linear_trans: dy -> dz; gamma / beta gradients
@@ -165,7 +168,7 @@ extern "C" int tgnn_backward(const tgnn_model_dims *dims, const void *const *par
                 TGNN_TRYB(tgnn_wgrad(dz, f, inp, fin, 0, n, f, fin, G(pi), G(pi + 1), b.wg, b.wg_bytes, stream));
                 TGNN_TRYB(dense_dx(dz, P.f(pi), f, fin, dy));   // dy is free again: dz holds what it carried
             } else {
-                TGNN_TRYB(tgnn_wgrad(dz, f, keep->skip, c, n * c, n, f, fin, G(pi), G(pi + 1), b.wg, b.wg_bytes, stream));
+                TGNN_TRYB(tgnn_wgrad_slots(dz, f, keep->skip, c, n * c, n, f, fin, G(pi), G(pi + 1), b.wg, b.wg_bytes, stream));
                 TGNN_TRYB(dense_dx(dz, P.f(pi), f, fin, b.dcat));
             }
         }
@@ -193,7 +196,7 @@ extern "C" int tgnn_backward(const tgnn_model_dims *dims, const void *const *par
                                        n, T, c, b.sbwd, stream));
         TGNN_TRYB(tgnn_swap_leading(wtab, T, c, c, b.wd, T + 1, stream));
         TGNN_TRYB(tgnn_swap_leading(P.f(pb + 6), 1, c, c, b.wd + (size_t)T * c, T + 1, stream));
-        TGNN_TRYB(tgnn_dense_act_fwd(b.sbwd, (int64_t)(T + 1) * c, 32, nullptr, b.wd, b.zero, n, (T + 1) * c, c, TGNN_ACT_NONE,
+        TGNN_TRYB(tgnn_dense_act_fwd(b.sbwd, (int64_t)(T + 1) * c, kRowMajorKBlock, nullptr, b.wd, b.zero, n, (T + 1) * c, c, TGNN_ACT_NONE,
                                      b.dh1, c, nullptr, nullptr, stream));
         TGNN_TRYB(tgnn_wgrad(h, c, b.sbwd, (int64_t)(T + 1) * c, 0, n, c, (T + 1) * c, b.dw_in, nullptr, b.wg, b.wg_bytes,
                              stream));

@@ -10,7 +10,7 @@ inference forward with the pre-BatchNorm activations, the BatchNorm records and 
 differentiated by torch: `Function.backward` hands the finished parameter gradients to autograd, which only stores
 them in `.grad` for the caller's optimizer (the reference passes one in, network_train.py).
 
-Adjoints, per forward kernel (C = 32, T edge types, D layers):
+Adjoints, per forward kernel (C = network width, T edge types, D layers):
   Linear_trans     dz = BN/activation backward (tgnn_bn_bwd_reduce/_apply); dW = dz^T x (tgnn_wgrad); db = colsum;
                    dx = dz W (tgnn_dense_act_fwd with W^T).
   merge            tgnn_merge_bwd_reduce: dy1 = dh BN2(a2), dy2 = dh BN1(a1) + carry, residual slot += dh, and the six
@@ -21,7 +21,9 @@ Adjoints, per forward kernel (C = 32, T edge types, D layers):
                    The edge MLP (T rows) is back-propagated with the generic dense pieces.
   GIN              t1, t2 re-derived from the kept aggregate; three sigmoid/Linear adjoints; the aggregation's adjoint is
                    the aggregation on the transposed collision graph (tgnn_gin_aggregate).
-Width 32 only (the reference's network_width, inputs/config.py:38); other widths raise.
+Widths 32 (the reference's network_width, inputs/config.py:38) and 64 (BASELINE config 3); other widths raise.  Width 64
+runs the same schedule: the width-64 forms of the adjoint kernels (type sums one wave per row, merge backward, GIN
+aggregation, the slot-major weight gradient over 64-wide slots) and the forward's generic GIN kernel keeping the aggregate.
 """
 from __future__ import annotations
 
@@ -78,19 +80,27 @@ def colsum(x: Tensor) -> Tensor:
 
 def wgrad(dz: Tensor, x: Tensor, slot_major: bool = False, with_bias: bool = False):
     """dz^T . x -> [cout, cin] (with_bias: also the column sums of dz, from the same pass).
-    slot_major: x is the [S, N, C] skip buffer read as [N, S * C]."""
+    slot_major: x is the [S, N, C] skip buffer (C = 32 or 64, contiguous) read as [N, S * C]."""
     n, cout = int(dz.shape[0]), int(dz.shape[1])
     if slot_major:
-        cin, ld_x, kb = int(x.shape[0]) * int(x.shape[2]), int(x.shape[2]), int(x.shape[1]) * int(x.shape[2])
-        if int(x.shape[2]) != 32:
-            raise NotImplementedError("slot-major weight gradient: width 32 only")
+        sw = int(x.shape[2])
+        if sw not in (32, 64):
+            raise NotImplementedError("slot-major weight gradient: slots of 32 or 64 columns")
+        if not x.is_contiguous():
+            raise ValueError("slot-major weight gradient: the skip buffer must be contiguous")
+        cin = int(x.shape[0]) * sw
     else:
-        cin, ld_x, kb = int(x.shape[1]), x.stride(0), 0
+        cin = int(x.shape[1])
     out = torch.empty(cout, cin, dtype=torch.float32, device=dz.device)
     dbias = torch.empty(cout, dtype=torch.float32, device=dz.device) if with_bias else None
     nb = lib.tgnn_wgrad_workspace_bytes(n, cout, cin)
     ws = _Scratch.get("wgrad", nb, dz.device)
-    check(lib.tgnn_wgrad(ptr(dz), dz.stride(0), ptr(x), ld_x, kb, n, cout, cin, ptr(out), ptr(dbias), ptr(ws), nb, _s(dz)))
+    if slot_major:
+        check(lib.tgnn_wgrad_slots(ptr(dz), dz.stride(0), ptr(x), sw, int(x.shape[1]) * sw, n, cout, cin, ptr(out), ptr(dbias),
+                                   ptr(ws), nb, _s(dz)))
+    else:
+        check(lib.tgnn_wgrad(ptr(dz), dz.stride(0), ptr(x), x.stride(0), 0, n, cout, cin, ptr(out), ptr(dbias), ptr(ws), nb,
+                             _s(dz)))
     return (out, dbias) if with_bias else out
 
 
@@ -143,15 +153,19 @@ def bn_bwd_apply(dy: Tensor, a: Tensor, stat: Tensor, coef: Tensor, act: int, ro
 
 def type_sum(rows: Tensor, own: Tensor, root_scale: Optional[Tensor], rowptr: Tensor, src: Tensor, typ: Tensor,
              n: int, n_types: int) -> Tensor:
-    out = torch.empty(n, (n_types + 1) * 32, dtype=torch.float32, device=rows.device)
+    """-> [n, (n_types + 1) * C], C = the width of `rows` (32 or 64)."""
+    c = int(rows.shape[1])
+    out = torch.empty(n, (n_types + 1) * c, dtype=torch.float32, device=rows.device)
     check(lib.tgnn_nnconv_type_sum(ptr(rows), rows.stride(0), ptr(own), own.stride(0), ptr(root_scale), ptr(rowptr),
-                                   ptr(src), ptr(typ), n, n_types, 32, ptr(out), _s(rows)))
+                                   ptr(src), ptr(typ), n, n_types, c, ptr(out), _s(rows)))
     return out
 
 
-def gin_aggregate(a: Tensor, rowptr: Tensor, src: Tensor, eps: Tensor, n: int) -> Tensor:
-    z = torch.empty(n, 32, dtype=torch.float32, device=a.device)
-    check(lib.tgnn_gin_aggregate(ptr(a), a.stride(0), None, ptr(rowptr), ptr(src), ptr(eps), n, 32, ptr(z), _s(a)))
+def gin_aggregate(a: Tensor, rowptr: Tensor, src: Tensor, eps: Tensor, n: int, in_stat: Optional[Tensor] = None) -> Tensor:
+    """-> [n, C], C = the width of `a` (32 or 64); in_stat: BatchNorm record applied to `a` while gathering."""
+    c = int(a.shape[1])
+    z = torch.empty(n, c, dtype=torch.float32, device=a.device)
+    check(lib.tgnn_gin_aggregate(ptr(a), a.stride(0), ptr(in_stat), ptr(rowptr), ptr(src), ptr(eps), n, c, ptr(z), _s(a)))
     return z
 
 
@@ -197,8 +211,8 @@ def forward_train(net, x: Tensor, adj_e_index: Tensor, adj_e_features: Tensor, c
     """The forward of the training step: `tgnn_forward_train` = the fused inference forward (same kernels, same two-stream
     schedule) writing what the backward reads into buffers that outlive it.  -> (probs, saved)."""
     c, depth = net.network_width, net.network_depth
-    if c != 32:
-        raise NotImplementedError("the training path is built for network_width = 32 (inputs/config.py:38)")
+    if c not in (32, 64):
+        raise NotImplementedError("the training path is built for network_width = 32 or 64 (inputs/config.py:38)")
     n = int(x.shape[0])
     if n < 2:
         raise ValueError("Expected more than 1 value per channel when training")
@@ -285,7 +299,7 @@ def nnconv_backward(conv, prefix: str, tg: TrainGraph, wtab: Tensor, h: Tensor, 
     input; dz: gradient at the conv's output; g_scaled = dz / deg.  Fills the gradients of root, bias and the edge MLP
     under `prefix`; returns the gradient at h."""
     g = tg.g
-    n, T, c = g.n_nodes, g.n_types, 32
+    n, T, c = g.n_nodes, g.n_types, int(h.shape[1])
     dev = h.device
     # ONE gather pass serves both gradients: S'[j][t] = sum over the out-edges (j -> v) of type t of g[v]  (type sums over
     # the TRANSPOSED graph; root slot = g[j] deg[j] = dz[j]).
@@ -333,7 +347,7 @@ def backward_train(net, sv, dprobs: Tensor) -> Dict[str, Tensor]:
     grads: Dict[str, Tensor] = {}
     dprobs = ops._f32c(dprobs, "grad of probs")
 
-    # ---- final Linear_trans (32 -> out, Sigmoid, no BatchNorm), then the final MLP
+    # ---- final Linear_trans (C -> out, Sigmoid, no BatchNorm), then the final MLP
     last = net.final_mlp[1]
     dl = sigmoid_bwd(dprobs, sv.probs)
     y = ops.bn_apply(sv.fin_a[-1], sv.fin_stat[-1])
