@@ -905,6 +905,31 @@ int tgnn_forward_bf16(const tgnn_model_dims *dims, const void *const *params_hos
 int tgnn_forward_bf16_begin(const tgnn_model_dims *dims, const void *const *params_host, const float *x, int64_t n_nodes,
                             int32_t update_running, void *ws, size_t ws_bytes, tgnn_stream_t stream2);
 
+/* ---- tile-in-region predicate (csrc/region.hip): the reference's `contain` (util/algo_util.py:143-144) for K regions x all tiles
+ * of a complete graph, in fp64, one launch (a fixed few for K > 65535); no host synchronisation, same bits from run to run.
+ *   alive_out [K][n_tiles] int32 = 1 iff |area(R_k n T_i) - tile_area[i]| < 1e-6;  area_out [K][n_tiles] (may be NULL) = area(R_k n T_i).
+ * Tiles: tri_xy [n_tri][3][2] counter-clockwise triangles of every tile's ring (ear clipping, so non-convex tiles work),
+ *   tile_tri_ptr [n_tiles + 1] the tile -> triangle range, tile_bbox [n_tiles][4] = xmin ymin xmax ymax, tile_area [n_tiles]
+ *   what the difference is taken against (the GEOS ring area, tile_graph.ring_area), tile_point [n_tiles][2] a point strictly
+ *   inside the tile.
+ * Regions: ring_xy [n_pts][2] with rings NOT closed (last vertex not repeated), ring_ptr [n_rings + 1] ring -> vertex range,
+ *   region_ring_ptr [K + 1] region -> ring range (exterior counter-clockwise, holes clockwise: tilingnn_amd.tiling.region
+ *   normalises), region_bbox [K][4] each region's box.  The ranges are trusted: the caller builds them (Region.buffers).
+ * max_region_edges: an upper bound of any region's vertex count; it only picks the launch shape (8 lanes per pair up to 48
+ *   edges, a wave per pair above).  A region whose winding number is 0/1 everywhere (a valid polygon) gets the set the
+ *   reference means; where rings overlap, the tile is inside where the winding number is non-zero (fast path) and the
+ *   boundary path integrates the winding number. */
+int tgnn_tiles_in_region(const double *tri_xy, const int32_t *tile_tri_ptr, const double *tile_bbox, const double *tile_area,
+                         const double *tile_point, int64_t n_tiles, const double *ring_xy, const int32_t *ring_ptr,
+                         const int32_t *region_ring_ptr, const double *region_bbox, int64_t n_regions, int32_t max_region_edges,
+                         int32_t *alive_out, double *area_out, tgnn_stream_t stream);
+/* counts_out [K][2] (int64, written whole) = {collision edges, adjacency edges} of the complete graph whose two ends are alive
+ * in region k (alive [K][n_tiles], as tgnn_tiles_in_region writes it); edge indices [2][E] int64.  *err_flag (may be NULL) is
+ * set on an edge end outside [0, n_tiles); such an edge is not counted. */
+int tgnn_region_edge_counts(const int32_t *alive, int64_t n_regions, int64_t n_tiles, const int64_t *col_edge_index,
+                            int64_t n_col_edges, const int64_t *adj_edge_index, int64_t n_adj_edges, int64_t *counts_out,
+                            int32_t *err_flag, tgnn_stream_t stream);
+
 int tgnn_rows_gather(const float *src, int64_t ld_src, const int32_t *idx, int64_t n_idx, int32_t c,
                      float *out, int64_t ld_out, tgnn_stream_t stream);
 int tgnn_rows_scatter(const float *in, const int32_t *idx, int64_t n_idx, int32_t c, float *dst,

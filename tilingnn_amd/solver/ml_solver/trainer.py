@@ -12,8 +12,8 @@ Here: the same loop with
   * forward + backward through the adjoint kernels (tilingnn_amd/train.py; `network.autograd` is switched on around the
     steps), the loss and its gradient on the GPU (solver/ml_solver/losses.py),
   * the caller's optimizer untouched (`optimizer.step()` on the `.grad`s, as in network_train.py).
-Not mirrored: `create_data` (random target shapes cut out of the complete graph with shapely, trainer.py:39-50, :126-165)
-and the per-checkpoint debug plots (`ml_solver.save_debug_info`, trainer.py:113-121).  batch_size must be 1, the only
+`create_data` (trainer.py:39-50, :126-165) judges its random target shapes on the GPU (csrc/region.hip) instead of with
+shapely in a 16-process pool.  Not mirrored: the per-checkpoint debug plots (`ml_solver.save_debug_info`, trainer.py:113-121).  batch_size must be 1, the only
 value the reference configures; a larger one would need PyG's disjoint-union batching.
 """
 import glob
@@ -85,9 +85,61 @@ class Trainer:
         self.model_save_path = model_save_path
         os.makedirs(self.model_save_path, exist_ok=True)
 
-    def create_data(self, *args, **kwargs):
-        raise NotImplementedError("create_data cuts random target shapes with shapely (trainer.py:39-50): generate the "
-                                  "layout files with the reference, they load here")
+    def create_data(self, complete_graph, low=0.4, high=0.8, max_vertices=10, testing_ratio=0.2, number_of_data=20000,
+                    rng=None, batch=4096):
+        """trainer.py:39-50, :126-165: `number_of_data` training layouts, then int(number_of_data * testing_ratio) testing
+        layouts, cut out of the complete graph by random stars (tile_factory.generate_random_inputs) and written as
+        `<data_path>/{train,test}/raw/data_<i>.pkl` in the reference's schema (write_brick_layout_data, with features).
+
+        rng: a random.Random (default: the global `random` module).  Candidates are drawn in stream order and judged on the
+        GPU `batch` at a time (the predicate and the edge counts in one launch each; a candidate with no collision or no
+        adjacency edge is rejected, as the reference's loop draws again); data i is the i-th accepted candidate, and its file
+        is what create_brick_layout_from_super_set + write_brick_layout_data give for its tiles.  Afterwards the stream is
+        where a sequential loop would leave it: at the draw of the last accepted candidate of the test split.
+        The reference forks a pool of 16 workers that all inherit one random state (trainer.py:137-138), so its files depend
+        on the scheduling; that is not mirrored.  The seconds spent are left in `self.create_data_times`
+        (gpu = draws + predicate + counts, write = the producer and the files)."""
+        import random as _random
+        rng = _random if rng is None else rng
+        for path in (self.data_path, self.training_path, self.testing_path):
+            os.makedirs(path, exist_ok=True)
+        self.create_data_times = {"gpu": 0.0, "write": 0.0}
+        self._create_data(complete_graph, self.training_path, number_of_data, low, high, max_vertices, rng, batch)
+        self._create_data(complete_graph, self.testing_path, int(number_of_data * testing_ratio), low, high, max_vertices,
+                          rng, batch)
+
+    def _create_data(self, graph, data_path, number_of_data, low, high, max_vertices, rng, batch):
+        import time
+        from ...tiling import tile_factory
+        from ...tiling.region import Region
+        os.makedirs(os.path.join(data_path, "raw"), exist_ok=True)
+        on_device = data_util.graph_on_device(graph, self.device)
+        bound = tile_factory.get_graph_bound(graph)
+        done = 0
+        while done < number_of_data:
+            t0 = time.perf_counter()
+            want = number_of_data - done
+            n = min(batch, max(64, want + want // 2))
+            regions, states = [], []
+            for _ in range(n):
+                regions.append(Region(tile_factory.draw_random_polygon(bound, max_vertices, low, high, rng), validate=False))
+                states.append(rng.getstate())
+            alive = on_device.tiles_in_regions(regions)
+            counts = on_device.region_edge_counts(alive).cpu().numpy()
+            accepted = np.flatnonzero((counts[:, 0] > 0) & (counts[:, 1] > 0))[:want]
+            rows = alive[torch.from_numpy(accepted).to(alive.device)].cpu().numpy() if accepted.size else None
+            t1 = time.perf_counter()
+            self.create_data_times["gpu"] += t1 - t0
+            for j, k in enumerate(accepted):
+                out = data_util.create_brick_layout_from_super_set(graph, np.flatnonzero(rows[j]).tolist())
+                data_util.write_brick_layout_data(save_path="raw/data_{}.pkl".format(done + j), node_features=out[0],
+                                                  collide_edge_index=out[1], collide_edge_features=out[2],
+                                                  align_edge_index=out[3], align_edge_features=out[4], re_index=out[5],
+                                                  prefix=data_path, predict=None, predict_order=None, predict_probs=None)
+            self.create_data_times["write"] += time.perf_counter() - t1
+            done += int(accepted.size)
+            if done == number_of_data and accepted.size:
+                rng.setstate(states[int(accepted[-1])])      # the draws past the last accepted candidate are undone
 
     def train_step(self, layout, optimizer):
         """trainer.py:69-84 for one layout; returns the loss (a 0-dim tensor) or None when the layout has an empty edge

@@ -10,6 +10,8 @@ hands back for an empty edge list) as the reference's module; what changed is ho
   layout_on_device                (new)     the same super-set cut carried out on the GPU: the complete graph is uploaded
       once (`CompleteGraphOnDevice`), a layout is its `alive` mask run through `tgnn_sublayout_compact`
       (csrc/graph_prep.hip) -- the arrays `to_torch_tensor` (:110-117) would have produced, without a host copy.
+  tiles_in_regions                (new)     the tile-in-region predicate of tile_factory.py:39 (`contain`, util/algo_util.py:
+      143-144) for K target regions at once (csrc/region.hip); the tile geometry is uploaded on first use.
   write_brick_layout_data / load_brick_layout_data / write_bricklayout / load_bricklayout   :18-78
       the same pickle schema; read through the schema-restricted unpickler of tile_graph.py.
 """
@@ -152,7 +154,7 @@ def recover_features_from_reindex(re_index, complete_graph: TileGraph):
 
 def create_brick_layout_from_super_set(graph: TileGraph, tiles_super_set):
     """tile_factory.py:49-58 after the polygon test: the six producer outputs for a given list of tiles.  (Which tiles
-    lie inside a target polygon is a shapely question, tile_factory.py:39 -- not answered here.)"""
+    lie inside a target polygon, tile_factory.py:39, is answered on the GPU: CompleteGraphOnDevice.tiles_in_regions.)"""
     a = graph.arrays
     col_rows, adj_rows = filter_edges(graph, tiles_super_set)
     return _produce(a, np.asarray(tiles_super_set, dtype=np.int64).reshape(-1), a.colli_edges[:, col_rows], col_rows,
@@ -178,6 +180,8 @@ class CompleteGraphOnDevice:
         self.adj_type = t(a.adj_type, torch.int32)
         self._builder = SubLayoutBuilder(self.full)
         self._alive = torch.zeros(self.n_tiles, dtype=torch.int32, device=self.device)
+        self._graph = graph
+        self._geometry = None
 
     def layout(self, tiles_super_set):
         """DeviceLayout of the given tiles (ASCENDING complete-graph ids: the order get_all_placement_in_polygon,
@@ -193,6 +197,82 @@ class CompleteGraphOnDevice:
         if s.size:
             self._alive[torch.from_numpy(s).to(self.device)] = 1
         return self._builder.build(self._alive)
+
+
+    # -------------------------------------------------------------------------- the tile-in-region predicate
+    def _tile_geometry(self):
+        """Tile triangles, triangle ranges, boxes, areas (the GEOS ring areas the reference compares against) and inside
+        points, uploaded on first use."""
+        if self._geometry is None:
+            import torch
+            from ..tiling.region import tile_geometry
+            g = self._graph
+            rings = [t.tile_poly.exterior for t in g.tiles]
+            tri, tri_ptr, bbox, area, point = tile_geometry(rings, g.arrays.tile_areas)
+            t = lambda arr: torch.from_numpy(np.ascontiguousarray(arr)).to(self.device)
+            self._geometry = (t(tri), t(tri_ptr), t(bbox), t(area), t(point))
+        return self._geometry
+
+    def tiles_in_regions(self, regions, with_area=False):
+        """alive [K, n_tiles] int32 on the device: 1 where |area(R_k n T_i) - area(T_i)| < 1e-6 (the reference's `contain`).
+        `regions`: tiling.region.Region objects.  with_area: also area(R_k n T_i) [K, n_tiles] float64.  No host sync."""
+        import torch
+        from .. import _lib
+        from .._lib import check, lib, ptr
+        from ..tiling.region import pack_regions
+        regions = list(regions)
+        k = len(regions)
+        alive = torch.empty(k, self.n_tiles, dtype=torch.int32, device=self.device)
+        area = torch.empty(k, self.n_tiles, dtype=torch.float64, device=self.device) if with_area else None
+        if k:
+            tri, tri_ptr, bbox, t_area, point = self._tile_geometry()
+            ring_xy, ring_ptr, region_ring_ptr, region_bbox, max_edges = pack_regions(regions)
+            up = lambda arr: torch.from_numpy(np.ascontiguousarray(arr)).to(self.device, non_blocking=False)
+            ring_xy_d = up(ring_xy if ring_xy.shape[0] else np.zeros((1, 2)))
+            bufs = (ring_xy_d, up(ring_ptr), up(region_ring_ptr), up(region_bbox))
+            check(lib.tgnn_tiles_in_region(ptr(tri), ptr(tri_ptr), ptr(bbox), ptr(t_area), ptr(point), self.n_tiles,
+                                           *(ptr(b) for b in bufs), k, max_edges, ptr(alive), ptr(area),
+                                           _lib.current_stream(self.device)))
+        return (alive, area) if with_area else alive
+
+    def region_edge_counts(self, alive):
+        """[K, 2] int64 on the device: collision and adjacency edges of the complete graph with both ends alive."""
+        import torch
+        from .. import _lib
+        from .._lib import check, lib, ptr
+        k = int(alive.shape[0])
+        counts = torch.empty(k, 2, dtype=torch.int64, device=self.device)
+        err = torch.zeros(1, dtype=torch.int32, device=self.device)
+        col, adj = self.full.collide_edge_index, self.full.align_edge_index
+        if k:
+            check(lib.tgnn_region_edge_counts(ptr(alive.contiguous()), k, self.n_tiles, ptr(col) if col.shape[1] else None,
+                                              int(col.shape[1]), ptr(adj) if adj.shape[1] else None, int(adj.shape[1]),
+                                              ptr(counts), ptr(err), _lib.current_stream(self.device)))
+        return counts
+
+    def layouts_in_regions(self, regions):
+        """One DeviceLayout per region: the tiles inside it cut out of the complete graph (what `layout` gives for that
+        tile set).  Each layout owns its buffers."""
+        from .algorithms import DeviceLayout
+        alive = self.tiles_in_regions(regions)
+        out = []
+        for k in range(alive.shape[0]):
+            sub = self._builder.build(alive[k])
+            out.append(DeviceLayout(sub.node_feature.clone(), sub.align_edge_index.clone(), sub.align_edge_features.clone(),
+                                    sub.collide_edge_index.clone(), sub.inverse_index.clone()))
+        return out
+
+
+def graph_on_device(graph: TileGraph, device=None) -> CompleteGraphOnDevice:
+    """The CompleteGraphOnDevice of `graph` on `device` (default: the current CUDA device), made once and kept on the graph."""
+    import torch
+    dev = torch.device(device if device is not None else "cuda")
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    cache = graph.__dict__.setdefault("_on_device", {})
+    if dev not in cache:
+        cache[dev] = CompleteGraphOnDevice(graph, dev)
+    return cache[dev]
 
 
 def layout_on_device(graph_on_device: CompleteGraphOnDevice, tiles_super_set):
