@@ -930,6 +930,27 @@ int tgnn_region_edge_counts(const int32_t *alive, int64_t n_regions, int64_t n_t
                             int64_t n_col_edges, const int64_t *adj_edge_index, int64_t n_adj_edges, int64_t *counts_out,
                             int32_t *err_flag, tgnn_stream_t stream);
 
+/* ---- area of the union of the alive tiles of K masks (csrc/union_area.hip): the reference's
+ * BrickLayout.get_super_contour_poly().area (tiling/brick_layout.py:180-188) without the polygon -- what the coverage of a crop
+ * (tile_factory.py:197) and Losses.solution_score (losses.py:126) divide by.  One call for all K masks, no host synchronisation,
+ * the same bits on every run (fixed summation order, no floating-point atomics).
+ *   ring_xy [n_pts][2], ring_ptr [n_tiles + 1]: every tile's ring, NOT closed, COUNTER-CLOCKWISE (tilingnn_amd.tiling.region.
+ *   union_geometry normalises); col_ptr [n_tiles + 1], col_idx: the collision edges as CSR, row i = the tiles that overlap tile i
+ *   in area or share a side with it from the same side (col_idx may be NULL when col_ptr is all 0); alive [K][n_tiles] int32,
+ *   != 0 = the tile is in mask k (as tgnn_tiles_in_region writes it; any 0/1 mask).  The ranges are trusted; an entry of
+ *   col_idx outside [0, n_tiles) is skipped and reported.
+ *   tol: points within tol of a side's line count as on it (1e-6: the radius the reference buffers every tile by); it must lie
+ *   between the noise of vertices that should coincide and the smallest real feature of the tiles.
+ *   area_out [K] fp64 (0.0 exactly for an empty mask).  *err_flag (device, required, zeroed by the caller) gets
+ *   TGNN_UNION_ERR_* bits OR-ed in: then area_out is not to be used.  ws: tgnn_union_area_workspace_bytes(K, n_tiles) bytes,
+ *   8-byte aligned. */
+#define TGNN_UNION_ERR_INDEX 1     /* a col_idx entry outside [0, n_tiles) */
+#define TGNN_UNION_ERR_INTERVALS 2 /* one tile side is covered in more than 8 separate stretches */
+size_t tgnn_union_area_workspace_bytes(int64_t n_masks, int64_t n_tiles);
+int tgnn_union_area(const double *ring_xy, const int32_t *ring_ptr, int64_t n_tiles, const int32_t *col_ptr,
+                    const int32_t *col_idx, const int32_t *alive, int64_t n_masks, double tol, double *area_out,
+                    int32_t *err_flag, void *ws, size_t ws_bytes, tgnn_stream_t stream);
+
 int tgnn_rows_gather(const float *src, int64_t ld_src, const int32_t *idx, int64_t n_idx, int32_t c,
                      float *out, int64_t ld_out, tgnn_stream_t stream);
 int tgnn_rows_scatter(const float *in, const int32_t *idx, int64_t n_idx, int32_t c, float *dst,

@@ -3,7 +3,9 @@
 A layout is five numpy arrays + the index maps to the complete graph.  The reference's class also draws, unions and
 measures polygons through shapely (`show_*`, `get_super_contour_poly`, `detect_holes`, ...): geometry is outside this
 package and those methods are not mirrored -- hand the arrays of this object to the reference's class when they are
-needed (same constructor arguments).  What `ML_Solver.predict` and the greedy loop read is here:
+needed (same constructor arguments).  One number of that geometry is here, because every score divides by it: the AREA of the
+union of the layout's tiles, `compute_super_contour_area` (on the GPU, csrc/union_area.hip) -> `super_contour_area`; there is
+deliberately no method called `get_super_contour_poly`.  What `ML_Solver.predict` and the greedy loop read is here:
 `get_data_as_torch_tensor` (:242-246) and `compute_sub_layout` (:248-286, vectorised: one membership mask instead of
 four comprehensions over every edge).
 """
@@ -31,6 +33,7 @@ class BrickLayout:
         self.predict_order = []
         self.target_polygon = target_polygon
         self.super_contour_poly = None
+        self.super_contour_area = None                             # compute_super_contour_area, or the crop path's coverage=True
 
     def __deepcopy__(self, memo):                                  # :57-73: arrays shared, predictions copied
         new = type(self).__new__(self.__class__)
@@ -47,6 +50,24 @@ class BrickLayout:
         from ..util.data_util import to_torch_tensor
         return to_torch_tensor(device, self.node_feature, self.align_edge_index, self.align_edge_features,
                                self.collide_edge_index, self.collide_edge_features)
+
+    def compute_super_contour_area(self, device=None):
+        """The area of the union of this layout's tiles -- the reference's `get_super_contour_poly().area` (:180-188) --
+        computed on the GPU from the complete graph's rings and `re_index` (csrc/union_area.hip), stored in
+        `self.super_contour_area` (what `Losses.solution_score` divides by) and returned.  There is no host fallback."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("compute_super_contour_area runs on the GPU (csrc/union_area.hip) and no GPU is available; "
+                               "there is no host fallback")
+        from ..util.data_util import graph_on_device
+        on_device = graph_on_device(self.complete_graph, device)
+        tiles = np.fromiter(self.re_index.keys(), dtype=np.int64, count=len(self.re_index))
+        if tiles.size and (tiles.min() < 0 or tiles.max() >= on_device.n_tiles):
+            raise ValueError(f"re_index names a tile outside [0, {on_device.n_tiles})")
+        alive = np.zeros(on_device.n_tiles, dtype=np.int32)
+        alive[tiles] = 1
+        self.super_contour_area = float(on_device.union_areas(torch.from_numpy(alive).to(on_device.device)).item())
+        return self.super_contour_area
 
     def compute_sub_layout(self, predict):
         """:248-286.  `predict`: a SelectionSolution-like object with dicts `labelled_nodes` / `unlabelled_nodes`."""

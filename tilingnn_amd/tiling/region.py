@@ -234,3 +234,76 @@ def tile_geometry(rings, areas):
         point.append(t[0].mean(axis=0))
     return (np.ascontiguousarray(np.concatenate(tris)), np.asarray(ptr, dtype=np.int32), np.asarray(bbox, dtype=np.float64),
             np.ascontiguousarray(areas, dtype=np.float64), np.asarray(point, dtype=np.float64))
+
+
+# ---------------------------------------------------------------------------------------------- union of tiles
+UNION_TOL = 1e-6          # the radius the reference buffers every tile by before its union (brick_layout.py:185)
+
+
+def union_geometry(rings, colli_edges, n_tiles=None):
+    """Device-side description of tgnn_union_area (csrc/union_area.hip): ring_xy [P, 2] f64 with every ring open and
+    counter-clockwise (the graphs store them clockwise), ring_ptr [n + 1] i32, and the collision edges [2, E] (either or
+    both directions) as a symmetric CSR without self loops or duplicates: col_ptr [n + 1] i32, col_idx i32."""
+    out = []
+    for r in rings:
+        r = _open_ring(r)
+        if r.shape[0] < 3:
+            raise ValueError("a tile ring with fewer than three vertices")
+        out.append(np.ascontiguousarray(r if signed_area(r) >= 0 else r[::-1]))
+    n = len(out) if n_tiles is None else int(n_tiles)
+    if n != len(out):
+        raise ValueError(f"{len(out)} rings for {n} tiles")
+    ring_ptr = np.zeros(n + 1, dtype=np.int64)
+    ring_ptr[1:] = np.cumsum([r.shape[0] for r in out])
+    col = np.asarray(colli_edges, dtype=np.int64).reshape(2, -1)
+    if col.size and (col.min() < 0 or col.max() >= n):
+        raise ValueError(f"collision edge end outside [0, {n})")
+    both = np.concatenate([col, col[::-1]], axis=1)
+    both = both[:, both[0] != both[1]]
+    keys = np.unique(both[0] * n + both[1])
+    col_ptr = np.searchsorted(keys // max(n, 1), np.arange(n + 1))
+    if ring_ptr[-1] >= 2 ** 31 or keys.size >= 2 ** 31:
+        raise ValueError("too many tile vertices or collision edges for one call")
+    return (np.ascontiguousarray(np.concatenate(out) if out else np.zeros((0, 2)), dtype=np.float64), ring_ptr.astype(np.int32),
+            col_ptr.astype(np.int32), (keys % max(n, 1)).astype(np.int32))
+
+
+def _point_segment_distances(pts, a, b):
+    """[..., V, S] distances of the points pts [..., V, 2] to the segments a -> b [..., S, 2]."""
+    d = b - a
+    rel = pts[..., :, None, :] - a[..., None, :, :]
+    dd = np.maximum(np.sum(d * d, axis=-1), 1e-300)[..., None, :]
+    t = np.clip(np.sum(rel * d[..., None, :, :], axis=-1) / dd, 0.0, 1.0)
+    gap = rel - t[..., None] * d[..., None, :, :]
+    return np.hypot(gap[..., 0], gap[..., 1])
+
+
+def vertex_side_distances(ring_xy, ring_ptr, pairs):
+    """Every distance from a vertex of tile v to a side of tile u, for the pairs [2, E] = (u, v); one flat array.  Pairs are
+    grouped by the two rings' vertex counts, so the work is a few array operations whatever the tile shapes are."""
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(2, -1)
+    if pairs.shape[1] == 0:
+        return np.zeros(0)
+    size = np.diff(ring_ptr).astype(np.int64)
+    out = []
+    shape_key = size[pairs[0]] * (int(size.max()) + 1) + size[pairs[1]]
+    for key in np.unique(shape_key):
+        u, v = pairs[:, shape_key == key]
+        nu, nv = int(size[u[0]]), int(size[v[0]])
+        a = ring_xy[ring_ptr[u][:, None] + np.arange(nu)[None, :]]
+        b = ring_xy[ring_ptr[u][:, None] + (np.arange(nu)[None, :] + 1) % nu]
+        p = ring_xy[ring_ptr[v][:, None] + np.arange(nv)[None, :]]
+        out.append(_point_segment_distances(p, a, b).reshape(-1))
+    return np.concatenate(out)
+
+
+def check_tolerance_gap(ring_xy, ring_ptr, col_ptr, col_idx, tol=UNION_TOL):
+    """tgnn_union_area snaps what lies within `tol` of a side onto it, which is only sound when nothing real is that small:
+    raises ValueError when a vertex of a tile lies between tol and 100 tol from a side of a tile it collides with."""
+    n = ring_ptr.shape[0] - 1
+    u = np.repeat(np.arange(n, dtype=np.int64), np.diff(col_ptr))
+    d = vertex_side_distances(ring_xy, ring_ptr, np.stack([u, col_idx.astype(np.int64)]))
+    bad = (d >= tol) & (d <= 100.0 * tol)
+    if bad.any():
+        raise ValueError(f"{int(bad.sum())} vertex-to-side distances between colliding tiles lie in [{tol:g}, {100 * tol:g}] "
+                         f"(the smallest: {float(d[bad].min()):.3g}): the union's tolerance cannot tell noise from geometry here")

@@ -12,8 +12,9 @@ A star whose clipped radii reach 0 at two non-adjacent vertices touches itself a
 GEOS polygon, and the reference's intersection may raise on it, in which case its `try` draws again; here the winding
 number still defines the set the reference means and the candidate is kept.  The test suite counts how often this happens.
 
-Not mirrored: `compute_super_graph` (polygon union), the coverage score of `crop_multiple_layouts_from_contour` (it needs
-the union of the selected tiles: None is returned in its place), plotting, SVG input.
+The coverage score of `crop_multiple_layouts_from_contour` (the area of the union of the cropped tiles over the target's) is
+opt-in, `coverage=True` (csrc/union_area.hip); by default None is returned in its place.
+Not mirrored: `compute_super_graph` (the union polygon itself), plotting, SVG input.
 """
 from __future__ import annotations
 
@@ -160,21 +161,29 @@ def crop_variants(exterior_contour, interior_contours, complete_graph, start_ang
 
 
 def crop_multiple_layouts_from_contour(exterior_contour, interior_contours, complete_graph, start_angle=0.0, end_angle=60.0,
-                                       num_of_angle=1, movement_delta_ratio=[0], margin_padding_ratios=[0.2], device=None):
+                                       num_of_angle=1, movement_delta_ratio=[0], margin_padding_ratios=[0.2], device=None,
+                                       coverage=False):
     """[(BrickLayout, coverage)] for every margin x angle x offset variant whose crop holds a tile; every variant is
-    evaluated in one kernel launch.  coverage is None: it needs the union of the cropped tiles (not mirrored)."""
+    evaluated in one kernel launch.  coverage=True: the second member is the reference's (tile_factory.py:197), the area of
+    the union of the cropped tiles over the target's area (csrc/union_area.hip, all variants in one call), and the layout's
+    `super_contour_area` is set, so that `ML_Solver.solve` scores it.  The default leaves both None."""
     from .brick_layout import BrickLayout
     from ..util.data_util import create_brick_layout_from_super_set
     regions = crop_variants(exterior_contour, interior_contours, complete_graph, start_angle, end_angle, num_of_angle,
                             movement_delta_ratio, margin_padding_ratios)
-    alive = _device_graph(complete_graph, device).tiles_in_regions(regions).cpu().numpy()
+    on_device = _device_graph(complete_graph, device)
+    alive_dev = on_device.tiles_in_regions(regions)
+    areas = on_device.union_areas(alive_dev).cpu().tolist() if coverage else [None] * len(regions)
+    alive = alive_dev.cpu().numpy()
     result = []
-    for region, row in zip(regions, alive):
+    for region, row, area in zip(regions, alive, areas):
         tiles = np.flatnonzero(row).tolist()
         if not tiles:
             continue
         node_feature, col, colf, adj, adjf, re_index = create_brick_layout_from_super_set(complete_graph, tiles)
         layout = BrickLayout(complete_graph, node_feature, col, colf, adj, adjf, re_index, target_polygon=region)
         layout.predict_probs = [0.5 for _ in range(node_feature.shape[0])]
-        result.append((layout, None))
+        if coverage:
+            layout.super_contour_area = area
+        result.append((layout, area / region.area if coverage else None))
     return result

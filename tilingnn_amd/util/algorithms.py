@@ -36,6 +36,7 @@ class DeviceLayout:
         self.collide_edge_index = collide_edge_index
         self.collide_edge_features = None                     # never read by the network (TilinGNN.py:51)
         self.inverse_index = inverse_index                    # sub-layout node -> original node
+        self.super_contour_area = None                        # set by CompleteGraphOnDevice.layouts_in_regions(with_area=True)
 
     def get_data_as_torch_tensor(self, device):
         return (self.node_feature, self.align_edge_index, self.align_edge_features, self.collide_edge_index,

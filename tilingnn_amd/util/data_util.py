@@ -182,6 +182,7 @@ class CompleteGraphOnDevice:
         self._alive = torch.zeros(self.n_tiles, dtype=torch.int32, device=self.device)
         self._graph = graph
         self._geometry = None
+        self._union = None
 
     def layout(self, tiles_super_set):
         """DeviceLayout of the given tiles (ASCENDING complete-graph ids: the order get_all_placement_in_polygon,
@@ -250,16 +251,63 @@ class CompleteGraphOnDevice:
                                               ptr(counts), ptr(err), _lib.current_stream(self.device)))
         return counts
 
-    def layouts_in_regions(self, regions):
+    # -------------------------------------------------------------------------- the area of a union of tiles
+    def _union_geometry(self):
+        """Tile rings (open, counter-clockwise) and the collision edges as CSR, uploaded on first use; the graph is checked
+        once for features the union's tolerance could not tell from noise (region.check_tolerance_gap)."""
+        if self._union is None:
+            import torch
+            from ..tiling.region import check_tolerance_gap, union_geometry
+            g = self._graph
+            geo = union_geometry([t.tile_poly.exterior for t in g.tiles], g.arrays.colli_edges, self.n_tiles)
+            check_tolerance_gap(*geo)
+            self._union = tuple(torch.from_numpy(a if a.size else np.zeros(1, dtype=a.dtype)).to(self.device) for a in geo)
+        return self._union
+
+    def union_areas(self, alive):
+        """[K] float64 on the device: the area of the union of the tiles with alive[k, i] != 0 (`alive` [K, n_tiles] or
+        [n_tiles], any integer or bool tensor on this device; what `tiles_in_regions` returns, or a solver's selection) -- the
+        reference's `get_super_contour_poly().area` of that tile set.  csrc/union_area.hip; one device-to-host copy of the
+        error word."""
+        import torch
+        from .. import _lib
+        from .._lib import check, lib, ptr
+        from ..tiling.region import UNION_TOL
+        alive = torch.as_tensor(alive, device=self.device)
+        if alive.dim() == 1:
+            alive = alive[None, :]
+        if alive.dim() != 2 or alive.shape[1] != self.n_tiles:
+            raise ValueError(f"alive must be [K, {self.n_tiles}], got {tuple(alive.shape)}")
+        alive = (alive != 0).to(torch.int32).contiguous() if alive.dtype != torch.int32 else alive.contiguous()
+        k = int(alive.shape[0])
+        area = torch.empty(k, dtype=torch.float64, device=self.device)
+        if k:
+            ring_xy, ring_ptr, col_ptr, col_idx = self._union_geometry()
+            err = torch.zeros(1, dtype=torch.int32, device=self.device)
+            ws_bytes = int(lib.tgnn_union_area_workspace_bytes(k, self.n_tiles))
+            ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=self.device)
+            check(lib.tgnn_union_area(ptr(ring_xy), ptr(ring_ptr), self.n_tiles, ptr(col_ptr), ptr(col_idx), ptr(alive), k,
+                                      UNION_TOL, ptr(area), ptr(err), ptr(ws), ws_bytes, _lib.current_stream(self.device)))
+            code = int(err.item())
+            if code:
+                raise _lib.TgnnError(f"tgnn_union_area: device error word {code} (1: collision index out of range, 2: a tile "
+                                     "side is covered in more separate stretches than the kernel's interval list holds)")
+        return area
+
+    def layouts_in_regions(self, regions, with_area=False):
         """One DeviceLayout per region: the tiles inside it cut out of the complete graph (what `layout` gives for that
-        tile set).  Each layout owns its buffers."""
+        tile set).  Each layout owns its buffers.  with_area: every layout also carries `super_contour_area`, the area of
+        the union of its tiles as a Python float (one kernel call and one copy for all regions)."""
         from .algorithms import DeviceLayout
         alive = self.tiles_in_regions(regions)
+        areas = self.union_areas(alive).cpu().tolist() if with_area else None
         out = []
         for k in range(alive.shape[0]):
             sub = self._builder.build(alive[k])
             out.append(DeviceLayout(sub.node_feature.clone(), sub.align_edge_index.clone(), sub.align_edge_features.clone(),
                                     sub.collide_edge_index.clone(), sub.inverse_index.clone()))
+            if with_area:
+                out[-1].super_contour_area = areas[k]
         return out
 
 
