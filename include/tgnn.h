@@ -732,6 +732,44 @@ int tgnn_greedy_finish(const int64_t *inverse, int64_t n_sub, const int64_t *col
                        int32_t first_round, int32_t max_rounds, uint64_t seed, double *prob_saved, int32_t *alive,
                        int32_t *selected_round, int64_t *n_selected, int32_t *err_flag, int32_t *out, tgnn_stream_t stream);
 
+/* ---- K greedy solves in ONE loop (csrc/greedy_many.hip; tilingnn_amd.util.algorithms.solve_many_by_device_greedy) ----------
+ * The four entries above and tgnn_solution_score_sums for K independent layouts per call, per layout exactly what the
+ * single-layout entry computes (same order, same draws, same fixed summation tree).  PACKED layouts: the K layouts' arrays
+ * concatenated, node_ptr / adj_ptr / col_ptr (device int64 [K + 1]) the offsets of layout k's nodes / adjacency edges / collision
+ * edges; total_* (host) the sizes of the packed arrays (= ptr[K]).  Layout k's edge index is its own [2][E_k] block at element
+ * 2 * ptr[k], ends in LOCAL node numbers; outputs of layout k are written at layout k's offsets (buffers sized for the
+ * un-compacted counts; a compacted index block has its rows E'_k apart), so a sub-layout is a plain view.  active / finish
+ * (device int32 [K], active may be NULL = all): layouts whose word is 0 are skipped, nothing of theirs is written.
+ * err_flag (device int32 [K]): set to 1 for a layout with an edge end, an offset or a count out of range -- such items are
+ * skipped, nothing is read or written out of range; the caller clears it.  One launch per step over all K (a layout's work is
+ * spread over blocks of 1 024 items; a block looks its layout up in a table built on the device). */
+size_t tgnn_sublayout_compact_many_workspace_bytes(int32_t n_layouts, int64_t total_nodes, int64_t total_adj_edges,
+                                                   int64_t total_col_edges);
+/* tgnn_sublayout_compact per layout: counts_out (device int64 [K][3]) = {N'_k, Ea'_k, Ec'_k}. */
+int tgnn_sublayout_compact_many(int32_t n_layouts, const int32_t *active, const int64_t *node_ptr, const int64_t *adj_ptr,
+                                const int64_t *col_ptr, int64_t total_nodes, int64_t total_adj_edges, int64_t total_col_edges,
+                                const int32_t *alive, const float *x, int32_t fx, const int64_t *adj_edge_index,
+                                const float *adj_edge_attr, int32_t fe, const int64_t *col_edge_index, float *x_out,
+                                int64_t *inverse_out, int64_t *adj_out, float *adj_attr_out, int64_t *col_out, int64_t *counts_out,
+                                int32_t *err_flag, void *ws, size_t ws_bytes, tgnn_stream_t stream);
+size_t tgnn_greedy_round_many_workspace_bytes(int32_t n_layouts, int64_t total_nodes);
+/* tgnn_greedy_round per layout.  prob: device table of K device pointers, prob[k] = the probabilities of sub-layout k (stride
+ * ld_prob floats; a NULL entry = probability 1 for every node); counts [K][3], inverse and col_edge_index: the sub-layouts as
+ * tgnn_sublayout_compact_many left them; seeds (device uint64 [K]); the draw is uniform(seeds[k], round, local original node);
+ * prob_saved / alive / selected_round packed over the original nodes, n_selected (device int64 [K]). */
+int tgnn_greedy_round_many(int32_t n_layouts, const int32_t *active, const float *const *prob, int64_t ld_prob,
+                           const int64_t *node_ptr, const int64_t *col_ptr, int64_t total_nodes, int64_t total_col_edges,
+                           const int64_t *counts, const int64_t *inverse, const int64_t *col_edge_index, int32_t round,
+                           const uint64_t *seeds, double *prob_saved, int32_t *alive, int32_t *selected_round, int64_t *n_selected,
+                           int32_t *err_flag, void *ws, size_t ws_bytes, tgnn_stream_t stream);
+/* tgnn_greedy_finish for every layout k with finish[k] != 0, one block each, one launch (sub-layouts of at most
+ * tgnn_greedy_finish_max_nodes() nodes; a larger one sets its error word).  out (device int32 [K][2]): rounds run, nodes left. */
+int tgnn_greedy_finish_many(int32_t n_layouts, const int32_t *finish, const int64_t *node_ptr, const int64_t *col_ptr,
+                            int64_t total_nodes, int64_t total_col_edges, const int64_t *counts, const int64_t *inverse,
+                            const int64_t *col_edge_index, int32_t first_round, int32_t max_rounds, const uint64_t *seeds,
+                            double *prob_saved, int32_t *alive, int32_t *selected_round, int64_t *n_selected, int32_t *err_flag,
+                            int32_t *out, tgnn_stream_t stream);
+
 /* ---- the loss on the predict path -------------------------------------------------
  * Losses.calculate_unsupervised_loss (solver/ml_solver/losses.py:48-116), evaluated by ML_Solver.predict through
  * get_best_prob_map (ml_solver.py:46,133-136): for every probability map m (column of probs [N, n_maps])
@@ -763,6 +801,14 @@ int tgnn_solution_score_sums(const float *predict, const float *area_ratio, int6
                              int64_t n_nodes, const int64_t *adj_edge_index, int64_t n_adj_edges,
                              const float *adj_edge_len, int64_t ld_len, double *sums, void *ws, size_t ws_bytes,
                              tgnn_stream_t stream);
+
+/* tgnn_solution_score_sums for K selections on packed layouts (see tgnn_sublayout_compact_many): sums (device double [K][3]),
+ * each layout summed over the fixed tree of the single-layout call (same bits); a layout with an edge end out of range gets NaN. */
+size_t tgnn_solution_score_sums_many_workspace_bytes(int32_t n_layouts);
+int tgnn_solution_score_sums_many(int32_t n_layouts, const int32_t *active, const int64_t *node_ptr, const int64_t *adj_ptr,
+                                  int64_t total_nodes, int64_t total_adj_edges, const float *predict, const float *area_ratio,
+                                  int64_t ld_area, const float *perimeter, const int64_t *adj_edge_index, const float *adj_edge_len,
+                                  int64_t ld_len, double *sums, void *ws, size_t ws_bytes, tgnn_stream_t stream);
 
 /* ---- the training step: adjoints of the forward kernels ---------------------------------
  * Trainer.train (solver/ml_solver/trainer.py:68-84) = forward in train mode, the unsupervised loss, loss.backward(),

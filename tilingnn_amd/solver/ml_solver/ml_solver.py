@@ -8,6 +8,7 @@
 
     solve(brick_layout)              ml_solver.py:64-73   (greedy assembly loop: tilingnn_amd/util/algorithms.py keeps the
                                                            layout on the GPU; `greedy_solver=` swaps in the reference's)
+    solve_many(brick_layouts)        Tiling-Shape.py:60-64 (the crop loop: K device-greedy solves in one loop)
 The debug dumps stay with the reference.
 
 `brick_layout` is duck-typed exactly as the reference uses it: `.node_feature`,
@@ -135,6 +136,30 @@ class ML_Solver:
         output_layout.predict = output_solution
         output_layout.predict_probs = self.predict(brick_layout)
         return output_layout, score
+
+    def solve_many(self, brick_layouts, seed=None):
+        """`solve` for K layouts at once -- the crop loop of the reference (Tiling-Shape.py:60-64) as ONE greedy loop on the GPU
+        (tilingnn_amd.util.algorithms.solve_many_by_device_greedy: per round one compaction, one read-back, the sub-layouts
+        scored side by side, one acceptance call).  Every layout is solved as `solve_by_device_greedy` solves it alone with the
+        same seed (default: `device_greedy_seed`), whatever `device_greedy_min_nodes` says.  Returns a list of
+        (output_layout, score) in input order; `predict`, `predict_order` as in `solve`; `predict_probs` = the first round's
+        probabilities (the first round's sub-layout IS the layout: what `self.predict(layout)` returns, without K more forwards).
+        In train mode the BatchNorm running statistics are left untouched (see `TilinGNN.forward_many`)."""
+        from ...util.algorithms import solve_many_by_device_greedy
+        brick_layouts = list(brick_layouts)
+        if not brick_layouts:
+            return []
+        results = solve_many_by_device_greedy(self, brick_layouts, seed=self.device_greedy_seed if seed is None else seed,
+                                              score_fn=self._score_fn)
+        first = solve_many_by_device_greedy.last_first_probs
+        out = []
+        for layout, (selection, score, order), probs in zip(brick_layouts, results, first):
+            output_layout = deepcopy(layout)
+            output_layout.predict_order = order
+            output_layout.predict = selection
+            output_layout.predict_probs = probs.cpu().numpy() if probs is not None else self.predict(layout)
+            out.append((output_layout, score))
+        return out
 
     def load_saved_network(self, net_path):
         self.network.load_state_dict(torch.load(net_path, map_location=self.device))

@@ -16,6 +16,9 @@ Same return values as the reference: (selection_predict, score, predict_order). 
 layout carries what it needs -- its complete graph (tile rings, max_area, max_align_length) and the area of its super
 contour (`layout.super_contour_area`, or the reference class's `get_super_contour_poly()`); a bare `DeviceLayout` has
 neither and scores `None` unless `score_fn(selection, origin_layout)` is given.
+
+`solve_many_by_device_greedy` runs K such device-greedy solves (the crops of one silhouette, Tiling-Shape.py:60-64) in one loop
+over `PackedLayouts`: one compaction, one read-back and one acceptance call per round for all of them (csrc/greedy_many.hip).
 """
 import ctypes as C
 
@@ -223,6 +226,325 @@ def solve_by_device_greedy(ml_solver, origin_layout, seed=0, score_fn=None, on_r
     score = create_score(selection, origin_layout, score_fn, device)
     solve_by_device_greedy.last_rounds = rounds
     return selection, score, order
+
+
+class PackedLayouts:
+    """K layouts packed ONCE for `solve_many_by_device_greedy` (csrc/greedy_many.hip): their arrays concatenated on the device,
+    offset tables node_ptr / adj_ptr / col_ptr [K + 1] (int64, host lists `*_h` and device tensors), edge ends in each layout's
+    LOCAL numbering, layout k's edge index its own [2][E_k] block at element 2 * ptr[k] of the flat index buffer.
+    `layouts`: DeviceLayouts or BrickLayout-like numpy layouts (converted as DeviceLayout.upload does; all-numpy input is
+    concatenated on the host and uploaded in four copies instead of 4 K)."""
+
+    def __init__(self, layouts, device):
+        layouts = list(layouts)
+        self.k = len(layouts)
+        device = torch.device(device)
+        on_dev = [l for l in layouts if isinstance(l, DeviceLayout)]
+        if on_dev:
+            device = on_dev[0].node_feature.device
+            layouts = [l if isinstance(l, DeviceLayout) else DeviceLayout.upload(l, device) for l in layouts]
+        self.device = device
+        xs, adjs, attrs, cols = [], [], [], []
+        for l in layouts:
+            if on_dev:
+                x, adj, attr, col = l.node_feature, l.align_edge_index.reshape(2, -1), l.align_edge_features, l.collide_edge_index.reshape(2, -1)
+            else:
+                x = np.ascontiguousarray(l.node_feature, dtype=np.float32)
+                adj = np.asarray(l.align_edge_index).reshape(2, -1).astype(np.int64, copy=False)
+                col = np.asarray(l.collide_edge_index).reshape(2, -1).astype(np.int64, copy=False)
+                attr = np.asarray(l.align_edge_features)
+                attr = attr.reshape(-1, attr.shape[-1] if attr.size else 1).astype(np.float32, copy=False)
+            xs.append(x); adjs.append(adj); attrs.append(attr); cols.append(col)
+        self.fx = max([int(x.shape[1]) for x in xs if x.ndim == 2] or [1])
+        self.fe = max([int(a.shape[1]) for a, e in zip(attrs, adjs) if e.shape[1]] or [1])
+        for k, (x, adj, attr) in enumerate(zip(xs, adjs, attrs)):
+            if x.shape[0] and (x.ndim != 2 or x.shape[1] != self.fx):
+                raise ValueError(f"layout {k}: node_feature must be [N, {self.fx}], got {tuple(x.shape)}")
+            if adj.shape[1] and (attr.shape[0] != adj.shape[1] or attr.shape[1] != self.fe):
+                raise ValueError(f"layout {k}: align_edge_features must be [{adj.shape[1]}, {self.fe}], got {tuple(attr.shape)}")
+        ptr_of = lambda sizes: [0] + [int(v) for v in np.cumsum(sizes, dtype=np.int64)]
+        self.node_ptr_h = ptr_of([x.shape[0] for x in xs])
+        self.adj_ptr_h = ptr_of([a.shape[1] for a in adjs])
+        self.col_ptr_h = ptr_of([c.shape[1] for c in cols])
+        self.n, self.ea, self.ec = self.node_ptr_h[-1], self.adj_ptr_h[-1], self.col_ptr_h[-1]
+        none = lambda shape: tuple(0 if v == -1 else v for v in shape)
+        if on_dev:
+            cat = lambda ts, shape, dt: (torch.cat([t.reshape(shape).to(dt) for t in ts]) if ts else torch.empty(none(shape), dtype=dt, device=device)).contiguous()
+            self.x = cat([x for x in xs if x.shape[0]], (-1, self.fx), torch.float32)
+            self.adj = cat([a for a in adjs if a.shape[1]], (-1,), torch.int64)
+            self.attr = cat([a for a, e in zip(attrs, adjs) if e.shape[1]], (-1, self.fe), torch.float32)
+            self.col = cat([c for c in cols if c.shape[1]], (-1,), torch.int64)
+        else:
+            cat = lambda arrs, shape, dt: torch.from_numpy(np.ascontiguousarray(
+                np.concatenate([np.asarray(a, dtype=dt).reshape(shape) for a in arrs]) if arrs else np.zeros(none(shape), dtype=dt))).to(device)
+            self.x = cat([x for x in xs if x.shape[0]], (-1, self.fx), np.float32)
+            self.adj = cat([a for a in adjs if a.shape[1]], (-1,), np.int64)
+            self.attr = cat([a for a, e in zip(attrs, adjs) if e.shape[1]], (-1, self.fe), np.float32)
+            self.col = cat([c for c in cols if c.shape[1]], (-1,), np.int64)
+        ptrs = torch.tensor([self.node_ptr_h, self.adj_ptr_h, self.col_ptr_h], dtype=torch.int64).to(device)
+        self.node_ptr, self.adj_ptr, self.col_ptr = ptrs[0], ptrs[1], ptrs[2]
+
+    def nodes(self, k: int) -> int:
+        return self.node_ptr_h[k + 1] - self.node_ptr_h[k]
+
+    def layout(self, k: int) -> DeviceLayout:
+        """Layout k as a view of the packed arrays."""
+        return self.view(k, self.x, self.adj, self.attr, self.col, *(p[k + 1] - p[k] for p in (self.node_ptr_h, self.adj_ptr_h, self.col_ptr_h)))
+
+    def view(self, k, x, adj, attr, col, n, ea, ec, inverse=None) -> DeviceLayout:
+        """The first n nodes / ea / ec edges of layout k's part of buffers laid out like the packed arrays (a sub-layout)."""
+        n0, a0, c0 = self.node_ptr_h[k], self.adj_ptr_h[k], self.col_ptr_h[k]
+        return DeviceLayout(x[n0:n0 + n], adj[2 * a0:2 * (a0 + ea)].view(2, ea), attr[a0:a0 + ea], col[2 * c0:2 * (c0 + ec)].view(2, ec),
+                            None if inverse is None else inverse[n0:n0 + n])
+
+
+def _forward_many_checked(network, subs, streams):
+    """`forward_many` + what `forward_checked` adds to a forward, ONCE for all layouts: a stale-result status of an earlier
+    unchecked forward is answered by queueing the forwards again; the health word of the persistent kernels is polled (this
+    synchronises the current stream) and, if set, the forwards are repeated on the general launch schedule."""
+    args = [(s.node_feature, s.align_edge_index, s.align_edge_features, s.collide_edge_index) for s in subs]
+    try:
+        outs = network.forward_many(args, streams=streams)
+    except _lib.TgnnError as exc:
+        if exc.code != _lib.ERR_STALE_RESULT:
+            raise
+        outs = network.forward_many(args, streams=streams)
+    dev = subs[0].node_feature.device
+    code = C.c_uint32(0)
+    check(lib.tgnn_spin_error_poll(_lib.current_stream(dev), C.byref(code)))
+    if code.value:
+        import warnings
+        warnings.warn("tilingnn_amd: a persistent forward kernel gave up waiting for its blocks (another process holds compute "
+                      f"units; reason bits {code.value}); the forwards are repeated on the general launch schedule, which the "
+                      "next forwards of this process take as well", RuntimeWarning)
+        outs = network.forward_many(args, streams=streams)
+    return outs
+
+
+def solve_many_by_device_greedy(ml_solver, layouts, seed=0, seeds=None, score_fn=None, max_rounds=100000, streams=3):
+    """K independent `solve_by_device_greedy` runs in ONE loop (csrc/greedy_many.hip): per round one compaction call for all
+    layouts (`tgnn_sublayout_compact_many`), ONE copy of the K x 3 counts and the K error words to the host, the sub-layouts that
+    still need the network scored side by side (`network.forward_many`), the health poll of `forward_checked` once, one
+    acceptance call (`tgnn_greedy_round_many`); layouts that reach the state from which ML_Solver.predict answers 1 without the
+    network finish in one launch (`tgnn_greedy_finish_many`) and leave; the loop ends when no layout is active.
+    THE SAME COMPUTATION as K single solves: result k equals `solve_by_device_greedy(ml_solver, layouts[k], seed=s_k)` -- selection,
+    predict_order, round count and score (`forward_many` gives the solo forward's bits, the draws are keyed by (seed, round,
+    local node), the sums run over fixed trees).  One difference that does not reach any output: in train mode `forward_many`
+    leaves the BatchNorm running statistics untouched where K `forward` calls update them; train-mode outputs do not read them.
+    `layouts`: a list of DeviceLayouts / BrickLayout-like numpy layouts, or a PackedLayouts; seeds: one per layout (default:
+    `seed` for all).  Returns a list of K (selection, score, predict_order); `.last_rounds` = the K round counts,
+    `.last_first_probs` = the first round's probabilities per layout ([n_k] float32 on the device: what predict_on_device
+    gives for the whole layout)."""
+    device = ml_solver.device
+    originals = None if isinstance(layouts, PackedLayouts) else list(layouts)
+    solve_many_by_device_greedy.last_rounds = []
+    solve_many_by_device_greedy.last_first_probs = []
+    if originals is not None and not originals:
+        return []
+    pk = layouts if isinstance(layouts, PackedLayouts) else PackedLayouts(originals, device)
+    K = pk.k
+    if K == 0:
+        return []
+    seeds_h = [int(seed)] * K if seeds is None else [int(s) for s in seeds]
+    if len(seeds_h) != K:
+        raise ValueError(f"seeds: one per layout ({K}), got {len(seeds_h)}")
+    # a layout without nodes: whatever the single-layout loop makes of it (it never enters a round here)
+    empty = {k: solve_by_device_greedy(ml_solver, originals[k] if originals is not None else pk.layout(k), seed=seeds_h[k],
+                                       score_fn=score_fn, max_rounds=max_rounds) for k in range(K) if pk.nodes(k) == 0}
+    dev = pk.device
+    stream = lambda: _lib.current_stream(dev)
+    n_tot, ea_tot, ec_tot = pk.n, pk.ea, pk.ec
+    i64, i32 = torch.int64, torch.int32
+    x_out = torch.empty(max(n_tot, 1), pk.fx, dtype=torch.float32, device=dev)
+    inverse = torch.empty(max(n_tot, 1), dtype=i64, device=dev)
+    adj_out = torch.empty(2 * max(ea_tot, 1), dtype=i64, device=dev)
+    attr_out = torch.empty(max(ea_tot, 1), pk.fe, dtype=torch.float32, device=dev)
+    col_out = torch.empty(2 * max(ec_tot, 1), dtype=i64, device=dev)
+    alive = torch.ones(max(n_tot, 1), dtype=i32, device=dev)
+    selected = torch.zeros(max(n_tot, 1), dtype=i32, device=dev)
+    saved = torch.ones(max(n_tot, 1), dtype=torch.float64, device=dev)
+    # what the host reads: counts [K][3] | error words [K] int32 | finish results [K][2] int32 | accepted so far [K]
+    tail = torch.zeros(6 * K, dtype=i64, device=dev)
+    counts, err = tail[:3 * K], tail[3 * K:4 * K].view(i32)[:K]
+    fin_out, n_selected = tail[4 * K:5 * K].view(i32), tail[5 * K:]
+    tail_h = torch.empty(6 * K, dtype=i64, pin_memory=True)
+    # what the host sends per round: probability pointers [K] | finish words [K] int32 | acceptance words [K] int32
+    meta = torch.zeros(2 * K, dtype=i64, device=dev)
+    meta_h = torch.zeros(2 * K, dtype=i64, pin_memory=True)
+    prob_tab, fin_words, act_words = meta[:K], meta[K:].view(i32)[:K], meta[K:].view(i32)[K:]
+    words_h = meta_h[K:].view(i32)
+    seeds_dev = torch.from_numpy(np.array([s & (2 ** 64 - 1) for s in seeds_h], dtype=np.uint64).view(np.int64)).to(dev)
+    cws_bytes = int(lib.tgnn_sublayout_compact_many_workspace_bytes(K, n_tot, ea_tot, ec_tot))
+    rws_bytes = int(lib.tgnn_greedy_round_many_workspace_bytes(K, n_tot))
+    cws = torch.empty(cws_bytes, dtype=torch.uint8, device=dev)
+    rws = torch.empty(rws_bytes, dtype=torch.uint8, device=dev)
+    fin_max = int(lib.tgnn_greedy_finish_max_nodes())
+    active = [pk.nodes(k) > 0 for k in range(K)]
+    rounds = [0] * K
+    finished_in = {}                                            # layout -> the round its finishing launch started in
+    first_probs = [None] * K
+    words_h[K:] = torch.tensor([int(a) for a in active], dtype=i32)
+    words_h[:K] = 0
+    meta.copy_(meta_h, non_blocking=True)
+    network = ml_solver.network
+    rnd = 0
+
+    def raise_errors(words):
+        bad = [k for k in range(K) if words[k]]
+        if bad:
+            raise IndexError(f"edge index out of range in layout {bad[0]} of {K}" + (f" (and in layouts {bad[1:]})" if bad[1:] else ""))
+
+    while any(active):
+        check(lib.tgnn_sublayout_compact_many(K, ptr(act_words), ptr(pk.node_ptr), ptr(pk.adj_ptr), ptr(pk.col_ptr), n_tot, ea_tot, ec_tot,
+                                              ptr(alive), ptr(pk.x), pk.fx, ptr(pk.adj), ptr(pk.attr), pk.fe, ptr(pk.col), ptr(x_out),
+                                              ptr(inverse), ptr(adj_out), ptr(attr_out), ptr(col_out), ptr(counts), ptr(err), ptr(cws),
+                                              cws_bytes, stream()))
+        tail_h.copy_(tail, non_blocking=True)                   # the round's ONE read-back
+        torch.cuda.current_stream(dev).synchronize()
+        host = tail_h.numpy()
+        raise_errors(host[3 * K:4 * K].view(np.int32)[:K])
+        cnt = host[:3 * K].reshape(K, 3)
+        rnd += 1
+        fin, need_net, subs = [], [], {}
+        for k in range(K):
+            if not active[k]:
+                continue
+            n2, ea2, ec2 = (int(v) for v in cnt[k])
+            if n2 == 0:
+                active[k] = False
+                rounds[k] = rnd - 1
+                continue
+            if rnd > max_rounds:
+                raise RuntimeError(f"solve_many_by_device_greedy: layout {k}: {n2} nodes still unlabelled after {max_rounds} rounds")
+            if (ea2 == 0 or ec2 == 0) and n2 <= fin_max:
+                fin.append(k)
+                active[k] = False
+                finished_in[k] = rnd
+                if rnd == 1:
+                    first_probs[k] = torch.ones(n2, dtype=torch.float32, device=dev)
+                continue
+            rounds[k] = rnd
+            if ea2 == 0 or ec2 == 0:                            # probability 1 without the network (ml_solver.py:31-32), too large to finish in one block
+                if rnd == 1:
+                    first_probs[k] = torch.ones(n2, dtype=torch.float32, device=dev)
+                continue
+            subs[k] = pk.view(k, x_out, adj_out, attr_out, col_out, n2, ea2, ec2, inverse)
+            need_net.append(k)
+        meta_h[:K] = 0
+        keep = []
+        if need_net:
+            views = [subs[k] for k in need_net]
+            if hasattr(network, "forward_many"):
+                outs = _forward_many_checked(network, views, streams)
+            else:
+                outs = [ml_solver.predict_on_device(v).reshape(-1, 1) for v in views]
+            for k, sub, out in zip(need_net, views, outs):
+                best = ml_solver._best_prob_map(out, sub) if out.shape[1] > 1 else 0
+                meta_h[k] = out.data_ptr() + 4 * best
+                if rnd == 1:
+                    first_probs[k] = out[:, best].detach().contiguous()
+            keep = outs
+            ld_prob = int(outs[0].shape[1])
+        else:
+            ld_prob = 1
+        words_h[:K] = torch.tensor([int(k in finished_in and finished_in[k] == rnd) for k in range(K)], dtype=i32)
+        words_h[K:] = torch.tensor([int(a) for a in active], dtype=i32)
+        meta.copy_(meta_h, non_blocking=True)                   # the round's ONE upload (the pinned buffer is rewritten only after the next round's synchronisation)
+        if fin:
+            check(lib.tgnn_greedy_finish_many(K, ptr(fin_words), ptr(pk.node_ptr), ptr(pk.col_ptr), n_tot, ec_tot, ptr(counts), ptr(inverse),
+                                              ptr(col_out), rnd, max_rounds - rnd + 1, ptr(seeds_dev), ptr(saved), ptr(alive), ptr(selected),
+                                              ptr(n_selected), ptr(err), ptr(fin_out), stream()))
+        if any(active):
+            check(lib.tgnn_greedy_round_many(K, ptr(act_words), ptr(prob_tab), ld_prob, ptr(pk.node_ptr), ptr(pk.col_ptr), n_tot, ec_tot,
+                                             ptr(counts), ptr(inverse), ptr(col_out), rnd, ptr(seeds_dev), ptr(saved), ptr(alive),
+                                             ptr(selected), ptr(n_selected), ptr(err), ptr(rws), rws_bytes, stream()))
+        del keep
+    tail_h.copy_(tail, non_blocking=True)
+    sel_h = selected.cpu().numpy()                              # (synchronises: the copy above has landed too)
+    host = tail_h.numpy()
+    raise_errors(host[3 * K:4 * K].view(np.int32)[:K])
+    fin_h = host[4 * K:5 * K].view(np.int32).reshape(K, 2)
+    selections, orders = [], []
+    for k in range(K):
+        if k in finished_in:
+            ran, left = int(fin_h[k, 0]), int(fin_h[k, 1])
+            rounds[k] = finished_in[k] + ran - 1
+            if left:
+                raise RuntimeError(f"solve_many_by_device_greedy: layout {k}: {left} nodes still unlabelled after {max_rounds} rounds")
+        sel_round = sel_h[pk.node_ptr_h[k]:pk.node_ptr_h[k + 1]]
+        selections.append((sel_round > 0).astype(np.float64))
+        picked = np.flatnonzero(sel_round > 0)
+        orders.append([int(v) for v in picked[np.lexsort((picked, sel_round[picked]))]])
+    scores = _scores_many(pk, selections, originals, score_fn, device)
+    solve_many_by_device_greedy.last_rounds = rounds
+    solve_many_by_device_greedy.last_first_probs = first_probs
+    return [empty[k] if k in empty else (selections[k], scores[k], orders[k]) for k in range(K)]
+
+
+def _scores_many(pk, selections, originals, score_fn, device):
+    """`create_score` for K selections: `score_fn` when given; `Losses.solution_score` -- its three sums for all layouts in one
+    `tgnn_solution_score_sums_many` call, over the single-layout call's summation tree -- for the layouts that carry their
+    complete graph and super-contour area; None for the others."""
+    K = pk.k
+    if originals is None:
+        originals = [None] * K
+    if score_fn is not None:
+        return [score_fn(selections[k], originals[k]) for k in range(K)]
+    import math
+    from ..solver.ml_solver.losses import loss_weights
+    areas = [None] * K
+    for k, lay in enumerate(originals):
+        if lay is None or getattr(lay, "complete_graph", None) is None or not pk.nodes(k):
+            continue
+        area = getattr(lay, "super_contour_area", None)
+        if area is None and hasattr(lay, "get_super_contour_poly"):
+            area = lay.get_super_contour_poly().area
+        areas[k] = area
+    scored = [k for k in range(K) if areas[k] is not None]
+    if not scored:
+        return [None] * K
+    dev = pk.device
+    perims = np.zeros(max(pk.n, 1), dtype=np.float32)
+    for k in scored:
+        lay, n = originals[k], pk.nodes(k)
+        per = getattr(lay, "_tile_perimeters", None)
+        if per is None or per.shape[0] != n:
+            inv, cg = lay.inverse_index, lay.complete_graph
+            per = np.array([cg.tiles[inv[i]].get_perimeter() for i in range(n)], dtype=np.float64)
+            try:
+                lay._tile_perimeters = per
+            except AttributeError:
+                pass
+        perims[pk.node_ptr_h[k]:pk.node_ptr_h[k + 1]] = per.astype(np.float32)            # (losses.py: torch.from_numpy(perims).float())
+    predict = torch.from_numpy(np.concatenate(selections).astype(np.float32) if pk.n else np.zeros(1, dtype=np.float32)).to(dev)
+    per_dev = torch.from_numpy(perims).to(dev)
+    words = torch.zeros(K, dtype=torch.int32)
+    words[scored] = 1
+    words = words.to(dev)
+    sums = torch.zeros(K, 3, dtype=torch.float64, device=dev)
+    ws_bytes = int(lib.tgnn_solution_score_sums_many_workspace_bytes(K))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.tgnn_solution_score_sums_many(K, ptr(words), ptr(pk.node_ptr), ptr(pk.adj_ptr), pk.n, pk.ea, ptr(predict),
+                                                C.c_void_p(pk.x.data_ptr() + 4 * (pk.fx - 1)), pk.fx, ptr(per_dev),
+                                                ptr(pk.adj) if pk.ea else None, C.c_void_p(pk.attr.data_ptr() + 4) if pk.ea else None,
+                                                pk.fe, ptr(sums), ptr(ws), ws_bytes, _lib.current_stream(dev)))
+    sums_h = sums.cpu().tolist()
+    wc, wl, wa = loss_weights()
+    scores = [None] * K
+    for k in scored:
+        s0, s1, s2 = sums_h[k]
+        if math.isnan(s0) or math.isnan(s1):
+            raise IndexError(f"edge index out of range [0, {pk.nodes(k)}) in the align_edge_index of layout {k}")
+        cg = originals[k].complete_graph
+        e_adj = pk.adj_ptr_h[k + 1] - pk.adj_ptr_h[k]
+        filled_area = s0 * float(cg.max_area) / float(areas[k])                           # Losses.solution_score, term for term
+        assert -1e-7 <= filled_area <= 1 + 1e-7, filled_area
+        loss_align_length = s1 * float(cg.max_align_length) if e_adj else 0.0
+        ratio = loss_align_length / s2
+        assert -1e-7 < ratio < 1 + 1e-7, ratio
+        scores[k] = float(wa * filled_area + wl * ratio)
+    return scores
 
 
 def create_score(selection, origin_layout, score_fn=None, device=None):
