@@ -669,6 +669,26 @@ int tgnn_forward_many(const tgnn_model_dims *dims, const void *const *params_hos
                       const float *const *adj_edge_attr, const tgnn_graph *graphs, int32_t update_running,
                       int32_t use_running_stats, float *const *probs, void *const *ws, const size_t *ws_bytes,
                       const tgnn_stream_t *streams, int32_t n_streams, tgnn_stream_t stream2);
+/* tgnn_forward_many with the small layouts inside ONE persistent kernel launch: every layout that a solo forward would send down
+ * the small-layout path (tgnn_set_small_layout_limit, at most 30 edge types, in-degree <= 31, train-mode BatchNorm, no fall-back
+ * window open) becomes a TEAM of blocks of one launch on `stream` -- its own barrier counter, partial rows and BatchNorm
+ * population, the solo kernel's block count, sum orders and formulas, hence the solo forward's bits -- behind ONE parameter pack,
+ * ONE edge-weight launch and ONE asynchronous table copy for all of them.  Layouts are grouped in input order into launches of at
+ * most (compute units - 16) blocks (tgnn_forward_union_plan).  Every other layout is queued on streams[k % n_streams] exactly as
+ * tgnn_forward_many queues it; results land in probs[k] in input order whatever the mix.  The graphs are prepared (tgnn_graph),
+ * the workspaces are tgnn_forward_workspace_bytes each; whatever prepared them must be ordered in front of `stream` by the caller,
+ * who also joins `streams` behind the call.  Running statistics are never updated (tgnn_forward_many with update_running = 0). */
+int tgnn_forward_union(const tgnn_model_dims *dims, const void *const *params_host, int32_t n_layouts, const float *const *x,
+                       const float *const *adj_edge_attr, const tgnn_graph *graphs, int32_t use_running_stats,
+                       float *const *probs, void *const *ws, const size_t *ws_bytes, tgnn_stream_t stream,
+                       const tgnn_stream_t *streams, int32_t n_streams, tgnn_stream_t stream2);
+/* The grouping alone (host only, no device needed): group_out[k] = the launch layout k of n_nodes[k] nodes rides in, groups
+ * numbered from 0 in input order, each at most capacity_blocks blocks of 16 rows; -1 = ineligible by size alone (fewer than 2
+ * nodes, above the small-layout limit, more blocks than capacity_blocks).  Returns the number of groups, or TGNN_ERR_INVALID_ARG. */
+int tgnn_forward_union_plan(const int64_t *n_nodes, int32_t k, int32_t capacity_blocks, int32_t *group_out);
+/* out[0] = persistent launches queued by tgnn_forward_union so far in this process, out[1] = layouts scored inside them (each also
+ * counts as a small-layout forward in tgnn_forward_path_counts). */
+void tgnn_forward_union_counts(int64_t out[2]);
 /* The PRODUCTION forward (tgnn_forward, train mode, two chains when stream2 is given; no event, no profiler) with the column
  * NNConv launches stamped on the device's wall clock: nnconv_us_host [network_depth] = last block out - first block in of every
  * layer's launch, microseconds -- the duration a kernel trace reports, measured inside the schedule as it runs (0 where the

@@ -177,6 +177,9 @@ def _load() -> C.CDLL:
         "tgnn_forward_profiled": (C.c_int, [C.POINTER(ModelDims), C.POINTER(C.c_void_p), p, p, C.POINTER(Graph), i32,
                                             i32, p, p, sz, p, C.POINTER(C.c_float), pi32]),
         "tgnn_forward_many": (C.c_int, [C.POINTER(ModelDims), C.POINTER(C.c_void_p), i32, p, p, p, i32, i32, p, p, p, p, i32, p]),
+        "tgnn_forward_union": (C.c_int, [C.POINTER(ModelDims), C.POINTER(C.c_void_p), i32, p, p, p, i32, p, p, p, p, p, i32, p]),
+        "tgnn_forward_union_plan": (C.c_int, [p, i32, i32, p]),
+        "tgnn_forward_union_counts": (None, [p]),
         "tgnn_forward_stamped": (C.c_int, [C.POINTER(ModelDims), C.POINTER(C.c_void_p), p, p, C.POINTER(Graph), i32, p, p, sz, p, p,
                                            C.POINTER(C.c_float)]),
         "tgnn_forward_profiled_two_stream": (C.c_int, [C.POINTER(ModelDims), C.POINTER(C.c_void_p), p, p, C.POINTER(Graph), i32,
@@ -252,7 +255,7 @@ EXPORTED_SYMBOLS = (
     "tgnn_ubench_row_gather", "tgnn_mid_entries_words", "tgnn_mid_entries_build", "tgnn_forward_path_counts", "tgnn_set_mid_layout_limit", "tgnn_get_mid_layout_limit", "tgnn_mid_layout_max_nodes",
     "tgnn_spin_error_poll", "tgnn_set_spin_budget_us", "tgnn_persist_fallback", "tgnn_spin_error_peek", "tgnn_gin_fwd", "tgnn_dense_act_fwd", "tgnn_dense_act_slots_fwd", "tgnn_dense_act_slots_f16_fwd", "tgnn_bn_finalize", "tgnn_bn_apply",
     "tgnn_merge_fwd", "tgnn_param_count", "tgnn_param_name", "tgnn_forward_workspace_bytes", "tgnn_forward", "tgnn_forward_begin", "tgnn_forward_resume",
-    "tgnn_forward_profiled", "tgnn_forward_profiled_two_stream", "tgnn_forward_stamped", "tgnn_forward_many", "tgnn_graph_prep_small_max_nodes", "tgnn_graph_prep_small_max_edges", "tgnn_graph_prep_small_tmp_ints",
+    "tgnn_forward_profiled", "tgnn_forward_profiled_two_stream", "tgnn_forward_stamped", "tgnn_forward_many", "tgnn_forward_union", "tgnn_forward_union_plan", "tgnn_forward_union_counts", "tgnn_graph_prep_small_max_nodes", "tgnn_graph_prep_small_max_edges", "tgnn_graph_prep_small_tmp_ints",
     "tgnn_graph_prep_small", "tgnn_graph_prep_workspace_bytes", "tgnn_graph_prep", "tgnn_graph_prep_wait", "tgnn_set_small_layout_limit", "tgnn_get_small_layout_limit", "tgnn_set_split_precision", "tgnn_set_gin_fused", "tgnn_set_gin_mlp_f16", "tgnn_set_mid_tail", "tgnn_set_nnconv_eg", "tgnn_set_dense_rows_mode", "tgnn_set_lean_head", "tgnn_set_prep_words_poll", "tgnn_forward_begin_weights", "tgnn_forward_bf16_begin", "tgnn_forward_small_prepass", "tgnn_rccl_available", "tgnn_rccl_unique_id_bytes", "tgnn_rccl_unique_id", "tgnn_rccl_comm_create", "tgnn_rccl_comm_destroy", "tgnn_rccl_counters", "tgnn_forward_train", "tgnn_backward_workspace_bytes", "tgnn_backward", "tgnn_forward_sharded_workspace_bytes", "tgnn_forward_sharded",
     "tgnn_rows_gather", "tgnn_rows_scatter", "tgnn_unsupervised_loss_workspace_bytes", "tgnn_unsupervised_loss", "tgnn_solution_score_sums",
     "tgnn_sublayout_workspace_bytes", "tgnn_sublayout_compact", "tgnn_greedy_round_workspace_bytes", "tgnn_greedy_round", "tgnn_greedy_finish_max_nodes", "tgnn_greedy_finish", "tgnn_shard_alive_rows",
@@ -272,6 +275,24 @@ def forward_path_counts():
     out = (C.c_int64 * 3)()
     lib.tgnn_forward_path_counts(out)
     return tuple(int(v) for v in out)
+
+
+def forward_union_counts():
+    """(persistent launches queued by tgnn_forward_union, layouts scored inside them) so far in this process."""
+    out = (C.c_int64 * 2)()
+    lib.tgnn_forward_union_counts(out)
+    return tuple(int(v) for v in out)
+
+
+def forward_union_plan(n_nodes, capacity_blocks):
+    """tgnn_forward_union_plan: (group of every layout, -1 = ineligible by size alone; number of groups)."""
+    k = len(n_nodes)
+    sizes = (C.c_int64 * max(k, 1))(*[int(v) for v in n_nodes])
+    out = (C.c_int32 * max(k, 1))()
+    n_groups = int(lib.tgnn_forward_union_plan(sizes, k, int(capacity_blocks), out))
+    if n_groups < 0:
+        raise ValueError("tgnn_forward_union_plan: invalid arguments")
+    return [int(out[i]) for i in range(k)], n_groups
 
 
 def check(rc: int) -> None:

@@ -136,6 +136,7 @@ static std::atomic<int> g_split_f16{1};              // tgnn_set_split_precision
 static std::atomic<int> g_nnconv_eg{1};              // tgnn_set_nnconv_eg
 static std::atomic<int> g_lean_head{3};              // tgnn_set_lean_head: bit 0 the head without memsets / early edge-weight event, bit 1 the fused init MLP
 static std::atomic<int64_t> g_path_count[3];          // forwards queued on the general schedule / small-layout kernel / mid-size kernel
+static std::atomic<int64_t> g_union_count[2];         // tgnn_forward_union: persistent launches / layouts scored inside them
 
 // n = rows this device computes; nr >= n = rows of the buffers that are GATHERED from (owned rows, then halo rows
 // of other shards; nr == n on a single device)
@@ -308,6 +309,18 @@ static int forward_head_init(const tgnn_model_dims *dims, const Params &P, const
     }
     return launch_init_mlp_fused(x, fx, fx, P.f(P.init(0)), P.f(P.init(0) + 1), P.f(P.init(1)), P.f(P.init(1) + 1), j0, j1, n, 1e-5f, 0.1f,
                                  w.mid, slot_max, st);
+}
+
+// the buffer-addressed gathers of the column NNConv (width 32, the gathered buffers below 2 GB) over the layout's column structure
+static bool forward_cols_ok(const tgnn_model_dims *dims, const tgnn_graph *graph, int64_t nr) {
+    return graph->nn_tile_col_ptr && dims->network_width == 32 && (int64_t)nr * dims->network_width * 4 < (int64_t(1) << 31);
+}
+// What a forward must be to take the one persistent kernel of forward_small.hip at all -- single device, inference, train-mode
+// BatchNorm, not profiled --, whatever the layout's size: forward_impl and tgnn_forward_union both ask here, then
+// small_layout_teams / small_union_tiles about the layout itself.
+static bool small_path_open(const tgnn_model_dims *dims, const tgnn_graph *graph, int64_t n, int64_t nr, bool sharded, bool keep,
+                            bool use_running_stats, bool profiled) {
+    return forward_cols_ok(dims, graph, nr) && !sharded && !keep && !use_running_stats && !profiled && nr == n;
 }
 
 static int forward_impl(const tgnn_model_dims *dims, const void *const *params_host, const float *x,
@@ -487,10 +500,11 @@ static int forward_impl(const tgnn_model_dims *dims, const void *const *params_h
     hipStream_t sw = s;
     constexpr bool weights_on_side = true;
     const bool addr_ok = c == 32 && (int64_t)nr * c * 4 < (int64_t(1) << 31);   // buffer-addressed gathers
-    const bool cols_ok = graph->nn_tile_col_ptr && addr_ok;
+    const bool cols_ok = forward_cols_ok(dims, graph, nr);
     const bool groups_ok = graph->nn_tile_grp_ptr && graph->nn_grp && addr_ok && graph->nn_max_in_degree <= 2048 && g_nnconv_eg;
     // Small layouts: the layer loop below is replaced by one persistent kernel (forward_small.hip)
-    const int small_teams = (cols_ok && !sh && !keep && !use_running_stats && !prof.on && nr == n) ? small_layout_teams(dims, n, T, graph->nn_max_in_degree) : 0;
+    const int small_teams = small_path_open(dims, graph, n, nr, sh != nullptr, keep != nullptr, use_running_stats != 0, prof.on)
+                                ? small_layout_teams(dims, n, T, graph->nn_max_in_degree) : 0;
     const int64_t cat_w_floats = (int64_t)c * (D + 1) * kFinalDims[0];
     const int fin_dims[5] = {c * (D + 1), kFinalDims[0], kFinalDims[1], kFinalDims[2], c};   // in / out widths of the final MLP's layers
     // fp16-pair operands (3 matrix terms instead of the 6 of bf16 x 3) wherever a bound of the operand is at hand: the kernels
@@ -1140,6 +1154,74 @@ extern "C" int tgnn_forward_many(const tgnn_model_dims *dims, const void *const 
         if (rc != TGNN_OK) return rc;
     }
     return TGNN_OK;
+}
+
+// K layouts, the eligible ones inside ONE persistent launch per group (forward_small.hip: forward_layers_small_union_kernel), on
+// `stream`; every other layout exactly where tgnn_forward_many sends it.  See include/tgnn.h.
+extern "C" int tgnn_forward_union(const tgnn_model_dims *dims, const void *const *params_host, int32_t n_layouts,
+                                  const float *const *x, const float *const *adj_edge_attr, const tgnn_graph *graphs,
+                                  int32_t use_running_stats, float *const *probs, void *const *ws, const size_t *ws_bytes,
+                                  tgnn_stream_t stream, const tgnn_stream_t *streams, int32_t n_streams, tgnn_stream_t stream2) {
+    TGNN_CHECK_ARG(n_layouts >= 0 && n_streams >= 1 && x && adj_edge_attr && graphs && probs && ws && ws_bytes && streams,
+                   "arguments");
+    TGNN_CHECK_ARG(dims_ok(dims) && params_host, "model dims / parameters");
+    if (n_layouts == 0) return TGNN_OK;
+    const int K = n_layouts;
+    std::vector<int> teams((size_t)K, 0);
+    std::vector<int32_t> group((size_t)K, -1);
+    int n_groups = 0;
+    {
+        DeviceGuard guard__(stream);
+        // a persistent kernel of an earlier call that gave up and whose failure nobody collected (forward_persist.h): loud, here,
+        // before anything is queued
+        TGNN_TRY(spin_error_collect_stale(static_cast<hipStream_t>(stream)));
+        const int np = tgnn_param_count(dims);
+        bool params_ok = true;
+        for (int i = 0; i < np; ++i) params_ok = params_ok && params_host[i];
+        for (int k = 0; k < K && params_ok; ++k) {
+            const tgnn_graph *g = graphs + k;
+            const int64_t n = g->n_nodes;
+            // (whatever forward_impl would refuse is left to it: it says why)
+            const bool sane = x[k] && probs[k] && ws[k] && n >= 2 && g->adj_rowptr && g->col_rowptr &&
+                              (g->n_types == 0 || (adj_edge_attr[k] && g->type_rep_edge && g->adj_src && g->adj_type));
+            if (!sane || !small_path_open(dims, g, n, n, false, false, use_running_stats != 0, false)) continue;
+            if (carve(*dims, n, n, g->n_types, ws[k], ws_bytes[k]).bytes > ws_bytes[k]) continue;
+            teams[(size_t)k] = small_union_tiles(dims, n, g->n_types, g->nn_max_in_degree);
+        }
+        n_groups = small_union_plan(teams.data(), K, small_union_capacity(), group.data());
+    }
+    for (int k = 0; k < K; ++k) {                               // the others: tgnn_forward_many's lanes
+        if (group[(size_t)k] >= 0) continue;
+        tgnn_stream_t st = streams[k % n_streams];
+        DeviceGuard guard__(st);
+        Prof prof;
+        const int rc = forward_impl(dims, params_host, x[k], adj_edge_attr[k], graphs + k, 0, use_running_stats, probs[k], ws[k],
+                                    ws_bytes[k], st, stream2, prof);
+        if (rc != TGNN_OK) return rc;
+    }
+    if (n_groups == 0) return TGNN_OK;
+    DeviceGuard guard__(stream);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::vector<SmallUnionLayout> L;
+    std::vector<int32_t> grp;
+    for (int k = 0; k < K; ++k) {
+        if (group[(size_t)k] < 0) continue;
+        const tgnn_graph *g = graphs + k;
+        const Workspace w = carve(*dims, g->n_nodes, g->n_nodes, g->n_types, ws[k], ws_bytes[k]);
+        L.push_back(SmallUnionLayout{x[k], adj_edge_attr[k], g, probs[k], w.mid, w.a2[0], w.a2[1], w.wtab, w.wimg, w.small_part,
+                                     w.small_part_wide});
+        grp.push_back(group[(size_t)k]);
+    }
+    const Params P{params_host, dims->network_depth};
+    TGNN_TRY(launch_forward_small_union(dims, P, L.data(), (int)L.size(), grp.data(), n_groups, 1e-5f, 0.1f, s));
+    g_path_count[1].fetch_add((int64_t)L.size(), std::memory_order_relaxed);
+    g_union_count[0].fetch_add(n_groups, std::memory_order_relaxed);
+    g_union_count[1].fetch_add((int64_t)L.size(), std::memory_order_relaxed);
+    TGNN_CHECK_LAUNCH();
+    return TGNN_OK;
+}
+extern "C" void tgnn_forward_union_counts(int64_t *out2) {
+    for (int k = 0; k < 2; ++k) out2[k] = g_union_count[k].load(std::memory_order_relaxed);
 }
 
 extern "C" int tgnn_forward_train(const tgnn_model_dims *dims, const void *const *params_host, const float *x,

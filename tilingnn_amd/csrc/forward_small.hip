@@ -334,12 +334,13 @@ __device__ __forceinline__ void small_tile_planes_from_act(const float *act, con
 
 // Train-mode BatchNorm statistics of act [valid_rows][M] over ALL tiles: this block's column sums -> its partial row -> grid
 // barrier -> every block folds all rows in the same order -> record [4][256] in LDS (block 0 updates the running buffers).
+// `tile` / `nblk`: this block's number in its team and the team's size (the whole grid, or one layout's blocks of a union launch).
 // Consecutive calls alternate between two sets of partial rows (`part_wide` = the caller's set for this call): nothing but this
 // one barrier separates a fast block's next row from a slow block's reads of the current ones.
 template <int M>
 __device__ __forceinline__ void small_tile_bn(const float *act, int valid_rows, const SmallDense &L, double *part_wide, double *red,
                                               float *rec, int64_t n_total, float eps, float momentum, int update_running,
-                                              unsigned *ctr, unsigned &target, unsigned nblk, SpinCtx &sp, int tid) {
+                                              unsigned *ctr, unsigned &target, unsigned tile, unsigned nblk, SpinCtx &sp, int tid) {
     static_assert(M == 32 || M == 64 || M == 128 || M == 256, "width");
     const __amdgpu_buffer_rsrc_t rs = rsrc_of(part_wide);
     if (tid < 2 * M) {
@@ -350,7 +351,7 @@ __device__ __forceinline__ void small_tile_bn(const float *act, int valid_rows, 
             const double v = (double)act[r * kDActLd + ch];
             acc += sq ? v * v : v;
         }
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, acc), rs, ((uint32_t)blockIdx.x * 512u + (uint32_t)tid) * 8u, 0, kCpSc1);
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, acc), rs, ((uint32_t)tile * 512u + (uint32_t)tid) * 8u, 0, kCpSc1);
     }
     small_grid_barrier(ctr, target, nblk, sp);
     {
@@ -389,7 +390,7 @@ __device__ __forceinline__ void small_tile_bn(const float *act, int valid_rows, 
             rec[256 + tid] = (float)(mean - (double)mh);
             rec[512 + tid] = (float)((double)L.gamma[tid] / sqrt(var + (double)eps));
             rec[768 + tid] = L.beta[tid];
-            if (blockIdx.x == 0 && update_running) {
+            if (tile == 0 && update_running) {
                 const double unbiased = n_total > 1 ? var * ((double)n_total / (double)(n_total - 1)) : var;
                 L.rm[tid] = (float)((1.0 - (double)momentum) * (double)L.rm[tid] + (double)momentum * mean);
                 L.rv[tid] = (float)((1.0 - (double)momentum) * (double)L.rv[tid] + (double)momentum * unbiased);
@@ -400,12 +401,16 @@ __device__ __forceinline__ void small_tile_bn(const float *act, int valid_rows, 
     }
 }
 
-__global__ __launch_bounds__(kSmallThreads) void forward_layers_small_kernel(SmallArgs A, SmallRunTab R, SmallEnds E) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
+// One block's share of a layout's forward: tile `tile_u` of a TEAM of `nblk` blocks that owns the layout -- the whole grid
+// (forward_layers_small_kernel) or one layout's blocks of a union launch (forward_layers_small_union_kernel).  Everything the
+// team shares -- barrier counter, partial rows, BatchNorm population -- is reached through A / E; LDS is used by A.n_types and
+// A.depth alone, never by the launch's dynamic size (a union launch carries the largest of its layouts').
+__device__ __forceinline__ void forward_layers_small_body(const SmallArgs &A, const SmallRunTab *R, const SmallEnds &E, const unsigned tile_u,
+                                                          const unsigned nblk, float *lds) {
     constexpr int NT = kSmallThreads;
-    if (A.fault && blockIdx.x == gridDim.x - 1) return;         // (test hook: a block that never shows up)
     const int T = A.n_types, D = A.depth;
     const int64_t n = A.n;
+    float *const a2_0 = A.a2[0], *const a2_1 = A.a2[1];        // (values, not elements picked by address: A may be a local copy)
     // LDS of the layer loop: GIN weight image | parameter vectors of two layers | NNConv partial products [6][64][8] (phase B:
     // the fp64 fold [8][128]; set-up: the entry lists) | collision z tiles [2][8][32] | a1 tile | a2 tile | records | root degrees |
     // run types; then, behind everything the init / final phases use, the type-sum tiles S [(T + 1)][16][32]
@@ -424,9 +429,8 @@ __global__ __launch_bounds__(kSmallThreads) void forward_layers_small_kernel(Sma
 
     const int tid = threadIdx.x, lane = tid & 63, tw = tid >> 6;
     const int fj = lane & 15, fq = lane >> 4;
-    const int64_t tile = blockIdx.x, my_row = tile * 16 + fj;
+    const int64_t tile = tile_u, my_row = tile * 16 + fj;
     const bool row_ok = my_row < n;
-    const unsigned nblk = gridDim.x;
     unsigned target = 0;
     SpinCtx spin{A.err, A.spin_budget, false, A.err_host};
     const size_t slot = (size_t)n * 32;
@@ -471,12 +475,12 @@ __global__ __launch_bounds__(kSmallThreads) void forward_layers_small_kernel(Sma
             dact[r * kDActLd + ch] = leakyf_(acc);
         }
         __syncthreads();
-        small_tile_bn<32>(dact, valid_rows, E.i0, E.part_wide, dred, drec, n, A.eps, A.momentum, A.update_running, A.ctr, target, nblk, spin, tid);
+        small_tile_bn<32>(dact, valid_rows, E.i0, E.part_wide, dred, drec, n, A.eps, A.momentum, A.update_running, A.ctr, target, tile_u, nblk, spin, tid);
         small_tile_planes_from_act(dact, drec, 32, valid_rows, dx, tid);
         __syncthreads();
         small_tile_dense<1>(E.i1.img, 1, 2, E.i1.bias, dx, dact, tw, lane);
         __syncthreads();
-        small_tile_bn<32>(dact, valid_rows, E.i1, E.part_wide + kPartWideSet, dred, drec, n, A.eps, A.momentum, A.update_running, A.ctr, target, nblk, spin, tid);
+        small_tile_bn<32>(dact, valid_rows, E.i1, E.part_wide + kPartWideSet, dred, drec, n, A.eps, A.momentum, A.update_running, A.ctr, target, tile_u, nblk, spin, tid);
         if (tid < 128) {
             const int row = tid >> 3, c4 = (tid & 7) * 4;
             if (row < valid_rows) {
@@ -671,7 +675,7 @@ __global__ __launch_bounds__(kSmallThreads) void forward_layers_small_kernel(Sma
             //      neighbourhood sum in registers, z through a wave-private LDS tile into the B-operand layout, then the
             //      32 -> 32 -> 64 -> 32 MLP of gin32_mlp_kernel on the half-filled 16-row tile.  Runs beside the NNConv waves.
             TGNN_ST2_RESET
-            const float *src = layer == 0 ? A.mid : ((layer - 1) & 1 ? A.a2[1] : A.a2[0]);
+            const float *src = layer == 0 ? A.mid : ((layer - 1) & 1 ? a2_1 : a2_0);
             const __amdgpu_buffer_rsrc_t a_rs = rsrc_of(src);
             // (all kGinCached slots are loaded, used or not: with the loads of the unused ones behind a wave-uniform `k < longest row`
             //  branch hipcc drains the queue at every join -- 0.375 instead of 0.337 ms per forward)
@@ -781,7 +785,7 @@ __global__ __launch_bounds__(kSmallThreads) void forward_layers_small_kernel(Sma
                 *reinterpret_cast<float4 *>(a2s + fj * 32 + 16 + 4 * fq) = r1;
             }
             TGNN_ST2(3)
-            const __amdgpu_buffer_rsrc_t o_rs = rsrc_of(layer & 1 ? A.a2[1] : A.a2[0]);
+            const __amdgpu_buffer_rsrc_t o_rs = rsrc_of(layer & 1 ? a2_1 : a2_0);
             const uint32_t o_off = mine && row_ok ? (uint32_t)my_row * 128u + (uint32_t)fq * 16u : kOob;
             st_sc1_f4(o_rs, o_off, r0);
             st_sc1_f4(o_rs, o_off == kOob ? kOob : o_off + 64u, r1);
@@ -828,7 +832,7 @@ __global__ __launch_bounds__(kSmallThreads) void forward_layers_small_kernel(Sma
                 const double v = (double)tile_s[r * 32 + ch];
                 acc2 += sq ? v * v : v;
             }
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, acc2), part_rs, ((uint32_t)blockIdx.x * 128u + (uint32_t)tid) * 8u, 0,
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, acc2), part_rs, ((uint32_t)tile_u * 128u + (uint32_t)tid) * 8u, 0,
                                                   kCpSc1);
         }
         TGNN_ST(3)
@@ -889,7 +893,7 @@ __global__ __launch_bounds__(kSmallThreads) void forward_layers_small_kernel(Sma
                 rec[32 + ch] = (float)(mean - (double)mh);
                 rec[64 + ch] = (float)((double)gamma / sqrt(var + (double)A.eps));
                 rec[96 + ch] = beta;
-                if (blockIdx.x == 0 && A.update_running) {
+                if (tile_u == 0 && A.update_running) {
                     // the running buffers are updated after the last layer (their read-modify-write round trips would make
                     // block 0 the straggler of every barrier): park the batch statistics
                     double *rs = A.runstat + (size_t)layer * 128 + job * 64;
@@ -935,13 +939,13 @@ __global__ __launch_bounds__(kSmallThreads) void forward_layers_small_kernel(Sma
         TGNN_ST(7)
     }
 
-    if (blockIdx.x == 0 && A.update_running && __hip_atomic_load(A.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
+    if (tile_u == 0 && A.update_running && __hip_atomic_load(A.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
         // running statistics of the 2 x depth BatchNorms of the layers (momentum update, num_batches_tracked); not after a
         // wait that gave up: the parked statistics are garbage then, and the host repeats the forward
         __syncthreads();
         for (int idx = tid; idx < D * 64; idx += NT) {
             const int l = idx >> 6, job = (idx >> 5) & 1, ch = idx & 31;
-            const SmallRun run = R.l[l];
+            const SmallRun run = R->l[l];
             float *rm = job ? run.rm2 : run.rm1, *rv = job ? run.rv2 : run.rv1;
             const double *rs = A.runstat + (size_t)l * 128 + job * 64;
             rm[ch] = (float)((1.0 - (double)A.momentum) * (double)rm[ch] + (double)A.momentum * rs[ch]);
@@ -972,22 +976,22 @@ __global__ __launch_bounds__(kSmallThreads) void forward_layers_small_kernel(Sma
         __syncthreads();
         small_tile_dense<2>(E.f[0].img, D + 1, 16, E.f[0].bias, dx, dact, tw, lane);
         __syncthreads();
-        small_tile_bn<256>(dact, valid_rows, E.f[0], E.part_wide, dred, drec, n, A.eps, A.momentum, A.update_running, A.ctr, target, nblk, spin, tid);
+        small_tile_bn<256>(dact, valid_rows, E.f[0], E.part_wide, dred, drec, n, A.eps, A.momentum, A.update_running, A.ctr, target, tile_u, nblk, spin, tid);
         small_tile_planes_from_act(dact, drec, 256, valid_rows, dx, tid);
         __syncthreads();
         small_tile_dense<1>(E.f[1].img, 8, 8, E.f[1].bias, dx, dact, tw, lane);
         __syncthreads();
-        small_tile_bn<128>(dact, valid_rows, E.f[1], E.part_wide + kPartWideSet, dred, drec, n, A.eps, A.momentum, A.update_running, A.ctr, target, nblk, spin, tid);
+        small_tile_bn<128>(dact, valid_rows, E.f[1], E.part_wide + kPartWideSet, dred, drec, n, A.eps, A.momentum, A.update_running, A.ctr, target, tile_u, nblk, spin, tid);
         small_tile_planes_from_act(dact, drec, 128, valid_rows, dx, tid);
         __syncthreads();
         small_tile_dense<1>(E.f[2].img, 4, 4, E.f[2].bias, dx, dact, tw, lane);
         __syncthreads();
-        small_tile_bn<64>(dact, valid_rows, E.f[2], E.part_wide, dred, drec, n, A.eps, A.momentum, A.update_running, A.ctr, target, nblk, spin, tid);
+        small_tile_bn<64>(dact, valid_rows, E.f[2], E.part_wide, dred, drec, n, A.eps, A.momentum, A.update_running, A.ctr, target, tile_u, nblk, spin, tid);
         small_tile_planes_from_act(dact, drec, 64, valid_rows, dx, tid);
         __syncthreads();
         small_tile_dense<1>(E.f[3].img, 2, 2, E.f[3].bias, dx, dact, tw, lane);
         __syncthreads();
-        small_tile_bn<32>(dact, valid_rows, E.f[3], E.part_wide + kPartWideSet, dred, drec, n, A.eps, A.momentum, A.update_running, A.ctr, target, nblk, spin, tid);
+        small_tile_bn<32>(dact, valid_rows, E.f[3], E.part_wide + kPartWideSet, dred, drec, n, A.eps, A.momentum, A.update_running, A.ctr, target, tile_u, nblk, spin, tid);
         for (int it = tid; it < 16 * E.out_dim; it += NT) {      // final_mlp.1
             const int r = it / E.out_dim, o = it - r * E.out_dim;
             if (r < valid_rows) {
@@ -1006,6 +1010,67 @@ __global__ __launch_bounds__(kSmallThreads) void forward_layers_small_kernel(Sma
     if (tid == 0 && blockIdx.x < 260)
         for (int k = 0; k < 8; ++k) g_small_timing[blockIdx.x * 32 + 16 + k] = tacc3[k];
 #endif
+#undef TGNN_SMALL_PREFETCH
+#undef TGNN_SMALL_COMMIT
+}
+
+__global__ __launch_bounds__(kSmallThreads) void forward_layers_small_kernel(SmallArgs A, SmallRunTab R, SmallEnds E) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    if (A.fault && blockIdx.x == gridDim.x - 1) return;         // (test hook: a block that never shows up)
+    forward_layers_small_body(A, &R, E, blockIdx.x, gridDim.x, lds);
+}
+
+// ---- K layouts in ONE launch (tgnn_forward_union) -------------------------------------------------------------------------
+// Layout j of the launch owns the blocks [first_block[j], first_block[j + 1]): a team that runs forward_layers_small_body exactly
+// as the grid of a solo launch does -- the same block count, sum orders and formulas, so the solo forward's bits -- with its own
+// barrier counter (a 128-byte line per team), partial rows and BatchNorm population.  What differs per layout comes from a device
+// table, what the layouts share (parameters, pack, spin-error word and budget) from the kernel arguments.  Running statistics are
+// never updated here (forward_many's mode), the edge weights are stream-ordered in front of the launch.
+struct SmallUnionEntry {
+    float *mid, *a2[2];
+    const float *wimg;
+    const int *tile_col_ptr, *col_meta, *col_src, *col_rowptr, *col_nbr;
+    double *part, *part_wide;
+    unsigned *ctr;
+    const float *x;
+    float *probs;
+    int64_t n;
+    int n_types, pad_;
+};
+__global__ __launch_bounds__(kSmallThreads) void forward_layers_small_union_kernel(SmallArgs A, SmallEnds E,
+                                                                                   const SmallUnionEntry *__restrict__ tab,
+                                                                                   const int *__restrict__ first_block, int n_layouts) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    // the block's layout: the largest j with first_block[j] <= blockIdx.x (wave-uniform: every operand is)
+    int lo = 0, hi = n_layouts;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (first_block[mid] <= (int)blockIdx.x) lo = mid; else hi = mid;
+    }
+    const int j = __builtin_amdgcn_readfirstlane(lo);
+    const int b0 = __builtin_amdgcn_readfirstlane(first_block[j]), b1 = __builtin_amdgcn_readfirstlane(first_block[j + 1]);
+    const SmallUnionEntry *e = tab + j;                          // (a uniform address: scalar loads)
+    A.mid = e->mid;
+    A.a2[0] = e->a2[0];
+    A.a2[1] = e->a2[1];
+    A.wimg = e->wimg;
+    A.tile_col_ptr = e->tile_col_ptr;
+    A.col_meta = e->col_meta;
+    A.col_src = e->col_src;
+    A.col_rowptr = e->col_rowptr;
+    A.col_nbr = e->col_nbr;
+    A.part = e->part;
+    A.ctr = e->ctr;
+    A.n = e->n;
+    A.n_types = e->n_types;
+    A.weights_done = nullptr;
+    A.update_running = 0;
+    A.runstat = nullptr;
+    E.x = e->x;
+    E.probs = e->probs;
+    E.part_wide = e->part_wide;
+    // (no SmallRunTab: it is read only where the running statistics are updated -- never, here)
+    forward_layers_small_body(A, nullptr, E, (unsigned)((int)blockIdx.x - b0), (unsigned)(b1 - b0), lds);
 }
 
 // ---- the device's spin-error word (forward_persist.h) ------------------------------------------------------------------
@@ -1078,6 +1143,7 @@ static void spin_error_clear(hipStream_t s) {                // (stream-ordered 
 }
 static std::atomic<int64_t> g_persist_off{0};                // forwards left in the fallback window
 void persist_fallback(int64_t n_forwards) { g_persist_off.store(n_forwards > 0 ? n_forwards : 0, std::memory_order_relaxed); }
+bool persist_window_open() { return g_persist_off.load(std::memory_order_relaxed) > 0; }
 bool persist_allowed() {
     int64_t v = g_persist_off.load(std::memory_order_relaxed);
     while (v > 0 && !g_persist_off.compare_exchange_weak(v, v - 1)) {}
@@ -1103,38 +1169,91 @@ constexpr size_t kSmallMaxLds = 160 * 1024 - 256;
 
 static std::atomic<int64_t> g_small_limit{4096};
 
-// 1 = eligible: one 16-row tile per block and at most one block per CU, the weight images of a layer fit LDS and the
-// prefetch registers, the final MLP's input planes fit LDS
-int small_layout_teams(const tgnn_model_dims *d, int64_t n_nodes, int n_types, int max_in_degree) {
+// What makes a layout eligible for the persistent kernel, in the pieces the solo path (small_layout_teams) and the union path
+// (small_union_tiles) share: the node count against the limit; one 16-row tile per block with the weight images of a layer in LDS
+// and the prefetch registers, the final MLP's input planes in LDS; the device's capacity in blocks.
+static bool small_layout_size_ok(int64_t n_nodes) {
     const int64_t limit = g_small_limit.load(std::memory_order_relaxed);
-    if (n_nodes < 2 || n_nodes > limit || n_nodes > 4096) return 0;
-    if (!persist_allowed()) return 0;                        // (a starved kernel of this kind a few forwards ago: general schedule for now)
-    if (max_in_degree < 1 || max_in_degree + 1 > kNnEntries) return 0;   // a row's gather list (edges + the root row) in registers
+    return n_nodes >= 2 && n_nodes <= limit && n_nodes <= 4096;
+}
+static bool small_layout_shape_ok(const tgnn_model_dims *d, int n_types, int max_in_degree) {
+    if (max_in_degree < 1 || max_in_degree + 1 > kNnEntries) return false;   // a row's gather list (edges + the root row) in registers
     if (d->network_width != 32 || d->network_depth < 1 || d->network_depth > kSmallMaxDepth || d->output_dim > 256 ||
         d->node_features_dim > 256)
-        return 0;
-    if (small_lds_bytes(n_types, d->network_depth) > kSmallMaxLds) return 0;
-    if (n_types + 1 > kRunWaves * kRunsPerWave || n_types + 1 > 31) return 0;      // runs per multiplying wave; run_type[32]
-    // The grid barrier needs every block resident at the same time.  The kernel is launched as an ordinary kernel on the
-    // caller's stream (a cooperative launch goes through a queue of its own: ~25 us of cross-queue dependency before and
-    // after the kernel, measured), so the guarantee a cooperative launch gives is checked here instead: blocks <= CUs of
-    // the device (of the partition, in CPX / NPS modes) x resident blocks per CU for this kernel's registers and LDS.
-    static std::atomic<int> capacity[64];
+        return false;
+    if (small_lds_bytes(n_types, d->network_depth) > kSmallMaxLds) return false;
+    if (n_types + 1 > kRunWaves * kRunsPerWave || n_types + 1 > 31) return false;      // runs per multiplying wave; run_type[32]
+    return true;
+}
+// The grid barrier needs every block resident at the same time.  The kernel is launched as an ordinary kernel on the
+// caller's stream (a cooperative launch goes through a queue of its own: ~25 us of cross-queue dependency before and
+// after the kernel, measured), so the guarantee a cooperative launch gives is checked here instead: blocks <= CUs of
+// the device (of the partition, in CPX / NPS modes) x resident blocks per CU for this kernel's registers and LDS.
+template <class Kern>
+static int small_kernel_capacity(Kern kern, std::atomic<int> (&capacity)[64], LdsOptIn &site) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
     int cap = capacity[dev].load(std::memory_order_acquire);
     if (cap == 0) {
-        static LdsOptIn site;
         int per_cu = 0, cus = 0;
-        if (opt_in_dynamic_lds(forward_layers_small_kernel, (int)kSmallMaxLds, site) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, forward_layers_small_kernel, kSmallThreads, kSmallMaxLds) != hipSuccess ||
+        if (opt_in_dynamic_lds(kern, (int)kSmallMaxLds, site) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kSmallThreads, kSmallMaxLds) != hipSuccess ||
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
             return 0;
         cap = per_cu > 0 && cus > 0 ? (per_cu > 1 ? 1 : per_cu) * cus : -1;   // (counted as one block per CU: the LDS images fill it)
         capacity[dev].store(cap, std::memory_order_release);
     }
-    // 2: at least 16 CUs stay free -- the pre-pass may then still be running when the kernel starts (it waits on a flag)
+    return cap;
+}
+static int small_capacity_blocks() {
+    static std::atomic<int> capacity[64];
+    static LdsOptIn site;
+    return small_kernel_capacity(forward_layers_small_kernel, capacity, site);
+}
+
+// 1 = eligible, 2: at least 16 CUs stay free -- the pre-pass may then still be running when the kernel starts (it waits on a flag)
+int small_layout_teams(const tgnn_model_dims *d, int64_t n_nodes, int n_types, int max_in_degree) {
+    if (!small_layout_size_ok(n_nodes)) return 0;
+    if (!persist_allowed()) return 0;                        // (a starved kernel of this kind a few forwards ago: general schedule for now)
+    if (!small_layout_shape_ok(d, n_types, max_in_degree)) return 0;
+    const int cap = small_capacity_blocks();
+    if (cap == 0) return 0;
     return (n_nodes + 15) / 16 <= cap - 16 ? 2 : (n_nodes + 15) / 16 <= cap ? 1 : 0;
+}
+
+// ---- union launches: capacity, eligibility, the planner ------------------------------------------------------------------
+// blocks one union launch may carry: one block per CU, 16 CUs left free -- what spin_kernel_chain admits beside nothing else
+int small_union_capacity() {
+    static std::atomic<int> capacity[64];
+    static LdsOptIn site;
+    const int solo = small_capacity_blocks(), uni = small_kernel_capacity(forward_layers_small_union_kernel, capacity, site);
+    const int cap = (solo < uni ? solo : uni) < device_cus() ? (solo < uni ? solo : uni) : device_cus();
+    return cap - 16 > 0 ? cap - 16 : 0;
+}
+// the layout's team size in a union launch, 0 = not eligible.  The conditions are small_layout_teams's; the fall-back window is only
+// looked at (the forward that takes the general schedule instead counts it down itself)
+int small_union_tiles(const tgnn_model_dims *d, int64_t n_nodes, int n_types, int max_in_degree) {
+    if (!small_layout_size_ok(n_nodes) || persist_window_open() || !small_layout_shape_ok(d, n_types, max_in_degree)) return 0;
+    const int tiles = (int)((n_nodes + 15) / 16);
+    return tiles <= small_union_capacity() ? tiles : 0;
+}
+// Greedy and order-preserving: teams[j] blocks (0 = layout j stays out: group -1) go to the current group while it stays within
+// `capacity` blocks, else open the next one.  Returns the number of groups.
+int small_union_plan(const int *teams, int k, int capacity, int32_t *group_out) {
+    int group = -1, used = 0;
+    for (int j = 0; j < k; ++j) {
+        if (teams[j] <= 0 || teams[j] > capacity) {
+            group_out[j] = -1;
+            continue;
+        }
+        if (group < 0 || used + teams[j] > capacity) {
+            ++group;
+            used = 0;
+        }
+        used += teams[j];
+        group_out[j] = group;
+    }
+    return group + 1;
 }
 
 // workspace of the path, floats: per-layer packs | dense images (init 1, final 0..3)
@@ -1240,6 +1359,28 @@ int spin_kernel_chain(hipStream_t s, void (*launch)(void *ctx, hipStream_t s), v
     return TGNN_OK;
 }
 
+// what every layout of a parameter set shares of SmallEnds (x, probs, part_wide: the layout's own)
+static SmallEnds small_ends_of(const tgnn_model_dims *d, const Params &P, const float *pack) {
+    const int depth = d->network_depth;
+    size_t off[5];
+    small_image_floats(depth, off);
+    const float *img = pack + (size_t)depth * kSpStride;
+    auto dense = [&](int pi, const float *image) {
+        const BnPtrs b = P.bn(pi + 2);
+        return SmallDense{image, P.f(pi + 1), b.gamma, b.beta, b.rm, b.rv, b.nbt};
+    };
+    SmallEnds E{};
+    E.w0 = P.f(P.init(0));
+    E.i0 = dense(P.init(0), nullptr);
+    E.i1 = dense(P.init(1), img + off[0]);
+    for (int l = 0; l < 4; ++l) E.f[l] = dense(P.fin(l), img + off[1 + l]);
+    E.w_last = P.f(P.last());
+    E.b_last = P.f(P.last() + 1);
+    E.fx = d->node_features_dim;
+    E.out_dim = d->output_dim;
+    return E;
+}
+
 // The whole forward behind the pre-pass: x -> probs (stream order)
 int launch_forward_small(const tgnn_model_dims *d, const Params &P, const float *x, float *probs, float *mid, float *a2_0,
                          float *a2_1, const float *wimg, float *pack, const tgnn_graph *graph, double *part, double *part_wide,
@@ -1281,25 +1422,10 @@ int launch_forward_small(const tgnn_model_dims *d, const Params &P, const float 
         const BnPtrs b1 = P.bn(P.layer(i) + 8), b2 = P.bn(P.layer(i) + 20);
         R.l[i] = SmallRun{b1.rm, b1.rv, b1.nbt, b2.rm, b2.rv, b2.nbt};
     }
-    size_t off[5];
-    small_image_floats(depth, off);
-    const float *img = pack + (size_t)depth * kSpStride;
-    auto dense = [&](int pi, const float *image) {
-        const BnPtrs b = P.bn(pi + 2);
-        return SmallDense{image, P.f(pi + 1), b.gamma, b.beta, b.rm, b.rv, b.nbt};
-    };
-    SmallEnds E{};
+    SmallEnds E = small_ends_of(d, P, pack);
     E.x = x;
-    E.w0 = P.f(P.init(0));
-    E.i0 = dense(P.init(0), nullptr);
-    E.i1 = dense(P.init(1), img + off[0]);
-    for (int l = 0; l < 4; ++l) E.f[l] = dense(P.fin(l), img + off[1 + l]);
-    E.w_last = P.f(P.last());
-    E.b_last = P.f(P.last() + 1);
     E.probs = probs;
     E.part_wide = part_wide;
-    E.fx = d->node_features_dim;
-    E.out_dim = d->output_dim;
     const int blocks = (int)((n + 15) / 16);
     static LdsOptIn site;
     TGNN_CHECK_HIP(opt_in_dynamic_lds(forward_layers_small_kernel, (int)kSmallMaxLds, site));
@@ -1313,7 +1439,159 @@ int launch_forward_small(const tgnn_model_dims *d, const Params &P, const float 
     return TGNN_OK;
 }
 
+// ---- tgnn_forward_union: k eligible layouts, `group[j]` (consecutive, from small_union_plan) = the launch layout j rides in ------
+// Everything on `s`, in order: ONE copy of the tables, ONE pack launch (it also zeroes the teams' counters), ONE edge-weight launch,
+// one persistent kernel per group.  Pack, counters and tables live in a library-owned per-device buffer that only grows.
+// The pinned staging buffer (and with it the device buffer: a later call may come on another stream) must not be rewritten while an
+// earlier call's copy or kernels may still be in flight: a RING of kUnionRing such buffer sets, each with an EVENT recorded behind
+// the call's last launch that the next user of the set waits for on the host -- four calls later, i.e. practically never.
+namespace {
+constexpr int kUnionRing = 4;
+struct UnionSet {
+    char *dev = nullptr, *host = nullptr;
+    size_t dev_cap = 0, host_cap = 0;
+    hipEvent_t ev = nullptr;
+};
+struct UnionRing {
+    UnionSet set[kUnionRing];
+    unsigned next = 0;
+};
+}  // namespace
+int launch_forward_small_union(const tgnn_model_dims *d, const Params &P, const SmallUnionLayout *L, int k, const int32_t *group,
+                               int n_groups, float eps, float momentum, hipStream_t s) {
+    static std::mutex mu;
+    static UnionRing rings[64];
+    const int depth = d->network_depth, fe = d->adj_edge_features_dim;
+    int dev = 0;
+    TGNN_CHECK_HIP(hipGetDevice(&dev));
+    TGNN_CHECK_ARG(dev >= 0 && dev < 64 && k >= 1 && n_groups >= 1, "device index / counts");
+    unsigned *err = spin_error_word();
+    if (!err) {
+        set_error("tgnn_forward_union: the spin-error word of the device could not be allocated");
+        return TGNN_ERR_LAUNCH;
+    }
+    // device: pack | counters [k][32] | tables;  tables (= the staging buffer): entries [k] | edge-weight entries [k] | first blocks
+    const size_t pack_bytes = align_up(small_pack_floats(depth) * sizeof(float), 256), ctr_bytes = (size_t)k * 128;
+    const size_t ent_bytes = align_up((size_t)k * sizeof(SmallUnionEntry), 256), ew_bytes = align_up((size_t)k * sizeof(EdgeWeightUnionEntry), 256);
+    const size_t tab_bytes = ent_bytes + ew_bytes + align_up((size_t)(k + n_groups) * sizeof(int), 256);
+    const size_t dev_bytes = pack_bytes + ctr_bytes + tab_bytes;
+    std::lock_guard<std::mutex> lock(mu);
+    UnionRing &ring = rings[dev];
+    UnionSet &u = ring.set[ring.next++ % kUnionRing];
+    if (!u.ev) TGNN_CHECK_HIP(hipEventCreateWithFlags(&u.ev, hipEventDisableTiming));
+    else TGNN_CHECK_HIP(hipEventSynchronize(u.ev));
+    if (u.dev_cap < dev_bytes) {                                 // (nothing of this set is in flight: see above)
+        if (u.dev) (void)hipFree(u.dev);
+        u.dev = nullptr;
+        u.dev_cap = 0;
+        TGNN_CHECK_HIP(hipMalloc(reinterpret_cast<void **>(&u.dev), dev_bytes * 2));
+        u.dev_cap = dev_bytes * 2;
+    }
+    if (u.host_cap < tab_bytes) {
+        if (u.host) (void)hipHostFree(u.host);
+        u.host = nullptr;
+        u.host_cap = 0;
+        TGNN_CHECK_HIP(hipHostMalloc(reinterpret_cast<void **>(&u.host), tab_bytes * 2, hipHostMallocDefault));
+        u.host_cap = tab_bytes * 2;
+    }
+    float *pack = reinterpret_cast<float *>(u.dev);
+    unsigned *ctr = reinterpret_cast<unsigned *>(u.dev + pack_bytes);
+    char *tab_dev = u.dev + pack_bytes + ctr_bytes;
+    SmallUnionEntry *ent = reinterpret_cast<SmallUnionEntry *>(u.host);
+    EdgeWeightUnionEntry *ew = reinterpret_cast<EdgeWeightUnionEntry *>(u.host + ent_bytes);
+    int *fb = reinterpret_cast<int *>(u.host + ent_bytes + ew_bytes);
+    const SmallUnionEntry *ent_dev = reinterpret_cast<const SmallUnionEntry *>(tab_dev);
+    const EdgeWeightUnionEntry *ew_dev = reinterpret_cast<const EdgeWeightUnionEntry *>(tab_dev + ent_bytes);
+    const int *fb_dev = reinterpret_cast<const int *>(tab_dev + ent_bytes + ew_bytes);
+    struct Group { int first, count, blocks, fb_at; size_t lds; };
+    std::vector<Group> groups((size_t)n_groups, Group{0, 0, 0, 0, 0});
+    int max_types = 0, fb_at = 0;
+    for (int j = 0; j < k; ++j) {
+        const tgnn_graph *g = L[j].graph;
+        TGNN_CHECK_ARG(group[j] >= 0 && group[j] < n_groups && (j == 0 ? group[j] == 0 : group[j] == group[j - 1] || group[j] == group[j - 1] + 1),
+                       "groups are consecutive");
+        SmallUnionEntry e{};
+        e.mid = L[j].mid;
+        e.a2[0] = L[j].a2_0;
+        e.a2[1] = L[j].a2_1;
+        e.wimg = L[j].wimg;
+        e.tile_col_ptr = g->nn_tile_col_ptr;
+        e.col_meta = g->nn_col_meta;
+        e.col_src = g->nn_col_src;
+        e.col_rowptr = g->col_rowptr;
+        e.col_nbr = g->col_src;
+        e.part = L[j].part;
+        e.part_wide = L[j].part_wide;
+        e.ctr = ctr + (size_t)j * 32;                          // (a 128-byte line per team)
+        e.x = L[j].x;
+        e.probs = L[j].probs;
+        e.n = g->n_nodes;
+        e.n_types = g->n_types;
+        ent[j] = e;
+        ew[j] = EdgeWeightUnionEntry{L[j].edge_attr, g->type_rep_edge, L[j].wtab, L[j].wimg, g->n_types, 0};
+        max_types = g->n_types > max_types ? g->n_types : max_types;
+        Group &G = groups[(size_t)group[j]];
+        if (G.count == 0) {
+            G.first = j;
+            G.fb_at = fb_at++;                                  // its prefix array: count + 1 words
+            fb[G.fb_at] = 0;
+        }
+        const int tiles = (int)((g->n_nodes + 15) / 16);
+        G.blocks += tiles;
+        G.count += 1;
+        fb[fb_at++] = G.blocks;
+        const size_t lds = small_lds_bytes(g->n_types, depth);
+        G.lds = lds > G.lds ? lds : G.lds;
+    }
+    TGNN_CHECK_HIP(hipMemcpyAsync(tab_dev, u.host, tab_bytes, hipMemcpyHostToDevice, s));
+    launch_small_pack(P, depth, pack, nullptr, s, true, ctr, ctr_bytes);
+    {
+        EdgeMlpLayers layers{};
+        const float *roots[kMaxDepth];
+        for (int i = 0; i < depth; ++i) {
+            const int b = P.layer(i);
+            layers.l[i] = EdgeMlpLayer{P.f(b), P.f(b + 1), P.f(b + 2), P.f(b + 3), P.f(b + 4), P.f(b + 5)};
+            roots[i] = P.f(b + 6);
+        }
+        launch_edge_weight_table_union(ew_dev, k, max_types, fe, layers, depth, roots, s);
+    }
+    SmallArgs A{};
+    A.pack = pack;
+    A.depth = depth;
+    A.eps = eps;
+    A.momentum = momentum;
+    A.err = err;
+    A.err_host = spin_error_mirror();
+    A.spin_budget = spin_budget_ticks();                       // (the tgnn_debug_spin_fault hook is not consumed here)
+    SmallEnds E = small_ends_of(d, P, pack);
+    const int capacity = small_union_capacity();               // (also: the kernel's opt-in to its dynamic LDS on this device)
+    int rc = TGNN_OK;
+    for (const Group &G : groups) {
+        if (G.count == 0 || G.blocks > capacity || G.lds > kSmallMaxLds) {
+            set_error("tgnn_forward_union: a group of %d blocks / %zu bytes of LDS does not fit the device (%d blocks)", G.blocks, G.lds, capacity);
+            rc = TGNN_ERR_INVALID_ARG;
+            break;
+        }
+        struct Ctx { SmallArgs *A; SmallEnds *E; const SmallUnionEntry *tab; const int *fb; int count, blocks; size_t lds; }
+            ctx{&A, &E, ent_dev + G.first, fb_dev + G.fb_at, G.count, G.blocks, G.lds};
+        rc = spin_kernel_chain(s, [](void *c, hipStream_t st) {
+            Ctx *x = static_cast<Ctx *>(c);
+            forward_layers_small_union_kernel<<<dim3(x->blocks), dim3(kSmallThreads), x->lds, st>>>(*x->A, *x->E, x->tab, x->fb, x->count);
+        }, &ctx, G.blocks);                                    // (one block per CU: everything in flight fits the device together)
+        if (rc != TGNN_OK) break;
+    }
+    TGNN_CHECK_HIP(hipEventRecord(u.ev, s));                   // (whatever was queued: the set is free again behind it)
+    return rc;
+}
+
 }  // namespace tgnn
+
+extern "C" int tgnn_forward_union_plan(const int64_t *n_nodes, int32_t k, int32_t capacity_blocks, int32_t *group_out) {
+    if (k < 0 || capacity_blocks < 0 || (k > 0 && (!n_nodes || !group_out))) return -1;
+    std::vector<int> teams((size_t)k);
+    for (int j = 0; j < k; ++j) teams[(size_t)j] = tgnn::small_layout_size_ok(n_nodes[j]) ? (int)((n_nodes[j] + 15) / 16) : 0;
+    return tgnn::small_union_plan(teams.data(), k, capacity_blocks, group_out);
+}
 
 #ifdef TGNN_SMALL_TIMING
 extern "C" int tgnn_debug_small_timing(unsigned long long *out, int n_blocks) {

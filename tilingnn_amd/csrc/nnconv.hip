@@ -58,20 +58,21 @@ __device__ __forceinline__ void weight_image_put_f16(_Float16 *dst, int r, float
     dst[kWtPlane * 2 + at] = (_Float16)(xs - (float)h);
 }
 
-__global__ __launch_bounds__(256) void edge_weight_table_kernel(
-    const float *__restrict__ edge_attr, const int *__restrict__ type_rep_edge, int fe, EdgeMlpLayers layers, int cc,
-    float *__restrict__ wtab_all, int n_types, RootPtrs roots, float *__restrict__ wimg_all, unsigned *__restrict__ done_ctr,
-    const unsigned *__restrict__ root_max, float img_scale) {
+// (the body of the two kernels below: block (bx, by) = (type | root, layer) of ONE layout's table)
+__device__ __forceinline__ void edge_weight_table_body(
+    const float *__restrict__ edge_attr, const int *__restrict__ type_rep_edge, int fe, const EdgeMlpLayers &layers, int cc,
+    float *__restrict__ wtab_all, int n_types, const RootPtrs &roots, float *__restrict__ wimg_all, unsigned *__restrict__ done_ctr,
+    const unsigned *__restrict__ root_max, float img_scale, const int bx, const int by) {
     // wimg_all != NULL (width 32): the block also writes its type's slice of the matrix-core operand image, and one more
-    // block per layer (blockIdx.x == n_types) the root matrix's -- no second launch on the way to the first NNConv
+    // block per layer (bx == n_types) the root matrix's -- no second launch on the way to the first NNConv
     // root_max != NULL: fp16-pair images (two planes, scaled), else bf16 x 3
     const bool f16 = root_max != nullptr;
-    const float wscale = f16 ? nnconv_weight_scale(root_max[blockIdx.y]) * img_scale : 1.0f;   // (img_scale: a power of two)
-    const int64_t img_at = ((int64_t)blockIdx.y * (n_types + 1) + blockIdx.x) * (f16 ? kWtTypeF16 : kWtType);
+    const float wscale = f16 ? nnconv_weight_scale(root_max[by]) * img_scale : 1.0f;   // (img_scale: a power of two)
+    const int64_t img_at = ((int64_t)by * (n_types + 1) + bx) * (f16 ? kWtTypeF16 : kWtType);
     __bf16 *img = wimg_all ? reinterpret_cast<__bf16 *>(wimg_all + img_at) : nullptr;
     _Float16 *img16 = reinterpret_cast<_Float16 *>(img);
-    if ((int)blockIdx.x == n_types) {
-        const float *src = roots.p[blockIdx.y];
+    if (bx == n_types) {
+        const float *src = roots.p[by];
         if (f16) for (int r = threadIdx.x; r < 1024; r += 256) weight_image_put_f16(img16, r, src[r] * wscale);
         else for (int r = threadIdx.x; r < 1024; r += 256) weight_image_put(img, r, src[r]);
         if (done_ctr) {                                     // (a consumer on another stream counts the finished blocks)
@@ -81,14 +82,14 @@ __global__ __launch_bounds__(256) void edge_weight_table_kernel(
         }
         return;
     }
-    const EdgeMlpLayer L = layers.l[blockIdx.y];
+    const EdgeMlpLayer L = layers.l[by];
     const float *__restrict__ w1 = L.w1, *__restrict__ b1 = L.b1, *__restrict__ w2 = L.w2, *__restrict__ b2 = L.b2,
                 *__restrict__ w3 = L.w3, *__restrict__ b3 = L.b3;
-    float *__restrict__ wtab = wtab_all + (int64_t)blockIdx.y * n_types * cc;
+    float *__restrict__ wtab = wtab_all + (int64_t)by * n_types * cc;
     __shared__ float e_s[1024];
     __shared__ float h1_s[kEH1];
     __shared__ float h2_s[kEH2];
-    const int t = blockIdx.x;
+    const int t = bx;
     const int64_t row = type_rep_edge[t];
     for (int k = threadIdx.x; k < fe; k += blockDim.x) e_s[k] = edge_attr[row * fe + k];
     __syncthreads();
@@ -131,6 +132,22 @@ __global__ __launch_bounds__(256) void edge_weight_table_kernel(
         __syncthreads();
         if (threadIdx.x == 0) __hip_atomic_fetch_add(done_ctr, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
+}
+__global__ __launch_bounds__(256) void edge_weight_table_kernel(
+    const float *__restrict__ edge_attr, const int *__restrict__ type_rep_edge, int fe, EdgeMlpLayers layers, int cc,
+    float *__restrict__ wtab_all, int n_types, RootPtrs roots, float *__restrict__ wimg_all, unsigned *__restrict__ done_ctr,
+    const unsigned *__restrict__ root_max, float img_scale) {
+    edge_weight_table_body(edge_attr, type_rep_edge, fe, layers, cc, wtab_all, n_types, roots, wimg_all, done_ctr, root_max, img_scale,
+                           (int)blockIdx.x, (int)blockIdx.y);
+}
+// The union form (tgnn_forward_union): blockIdx.z = layout, its pointers and type count from a device table; bf16 x 3 images, no
+// counter.  The grid's x is sized for the layout with the most types: surplus blocks leave.
+__global__ __launch_bounds__(256) void edge_weight_table_union_kernel(const EdgeWeightUnionEntry *__restrict__ tab, int fe,
+                                                                      EdgeMlpLayers layers, int cc, RootPtrs roots) {
+    const EdgeWeightUnionEntry e = tab[blockIdx.z];
+    if ((int)blockIdx.x > e.n_types) return;
+    edge_weight_table_body(e.edge_attr, e.type_rep_edge, fe, layers, cc, e.wtab, e.n_types, roots, e.wimg, nullptr, nullptr, 1.0f,
+                           (int)blockIdx.x, (int)blockIdx.y);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -422,10 +439,11 @@ __global__ __launch_bounds__(256) void nnconv_generic_kernel(
 // layers -- during which the persistent layer loops (forward_small.hip, forward_mid.hip), started beside it, found no free CUs for
 // half of their blocks.  Same multiply-add order per output as edge_weight_table_kernel: the same bits.
 constexpr int kEwTypes = 16, kEwMaxFe = 64;   // types per pass; attribute columns (beyond: the kernel above)
-__global__ __launch_bounds__(256) void edge_weight_table_chunks_kernel(
-    const float *__restrict__ edge_attr, const int *__restrict__ type_rep_edge, int fe, EdgeMlpLayers layers, int cc,
-    float *__restrict__ wtab_all, int n_types, RootPtrs roots, float *__restrict__ wimg_all, unsigned *__restrict__ done_ctr,
-    const unsigned *__restrict__ root_max, float img_scale, const int *__restrict__ n_types_dev, int max_types_dev) {
+__device__ __forceinline__ void edge_weight_table_chunks_body(
+    const float *__restrict__ edge_attr, const int *__restrict__ type_rep_edge, int fe, const EdgeMlpLayers &layers, int cc,
+    float *__restrict__ wtab_all, int n_types, const RootPtrs &roots, float *__restrict__ wimg_all, unsigned *__restrict__ done_ctr,
+    const unsigned *__restrict__ root_max, float img_scale, const int *__restrict__ n_types_dev, int max_types_dev, const int bx,
+    const int by) {
     // [r6] n_types_dev: the type count read on the device (tgnn_forward_begin_weights: queued before the host knows it); more types
     // than the workspace was carved for: nothing is written (the caller finds that out from the count and runs the general call)
     unsigned own_root_max = 0u;
@@ -437,7 +455,7 @@ __global__ __launch_bounds__(256) void edge_weight_table_chunks_kernel(
         if (root_max) {
             __shared__ float wm[4];
             float m = 0.f;
-            m = absmax4(m, reinterpret_cast<const float4 *>(roots.p[blockIdx.y])[threadIdx.x]);   // 1024 floats
+            m = absmax4(m, reinterpret_cast<const float4 *>(roots.p[by])[threadIdx.x]);   // 1024 floats
 #pragma unroll
             for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
             if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
@@ -446,23 +464,23 @@ __global__ __launch_bounds__(256) void edge_weight_table_chunks_kernel(
         }
     }
     const bool f16 = root_max != nullptr;
-    const float wscale = f16 ? nnconv_weight_scale(n_types_dev ? own_root_max : root_max[blockIdx.y]) * img_scale : 1.0f;
+    const float wscale = f16 ? nnconv_weight_scale(n_types_dev ? own_root_max : root_max[by]) * img_scale : 1.0f;
     const int chunks = cc / 256, tid = threadIdx.x;
-    auto image_of = [&](int t) { return wimg_all + ((int64_t)blockIdx.y * (n_types + 1) + t) * (f16 ? kWtTypeF16 : kWtType); };
-    if ((int)blockIdx.x == chunks) {                             // the root matrix's image (width 32 only)
-        const float *src = roots.p[blockIdx.y];
+    auto image_of = [&](int t) { return wimg_all + ((int64_t)by * (n_types + 1) + t) * (f16 ? kWtTypeF16 : kWtType); };
+    if (bx == chunks) {                             // the root matrix's image (width 32 only)
+        const float *src = roots.p[by];
         __bf16 *img = reinterpret_cast<__bf16 *>(image_of(n_types));
         if (f16) for (int r = tid; r < 1024; r += 256) weight_image_put_f16(reinterpret_cast<_Float16 *>(img), r, src[r] * wscale);
         else for (int r = tid; r < 1024; r += 256) weight_image_put(img, r, src[r]);
     } else {
-        const EdgeMlpLayer L = layers.l[blockIdx.y];
+        const EdgeMlpLayer L = layers.l[by];
         const float *__restrict__ w1 = L.w1, *__restrict__ b1 = L.b1, *__restrict__ w2 = L.w2, *__restrict__ b2 = L.b2,
                     *__restrict__ w3 = L.w3, *__restrict__ b3 = L.b3;
-        float *__restrict__ wtab = wtab_all + (int64_t)blockIdx.y * n_types * cc;
+        float *__restrict__ wtab = wtab_all + (int64_t)by * n_types * cc;
         __shared__ float e_s[kEwTypes * kEwMaxFe];
         __shared__ float h1_s[kEwTypes * kEH1];
         __shared__ __attribute__((aligned(16))) float h2_s[kEwTypes * kEH2];
-        const int j = blockIdx.x * 256 + tid;                     // this thread's output
+        const int j = bx * 256 + tid;                     // this thread's output
         float4 wr[kEH2 / 4];
 #pragma unroll
         for (int q = 0; q < kEH2 / 4; ++q) wr[q] = reinterpret_cast<const float4 *>(w3 + (int64_t)j * kEH2)[q];
@@ -516,6 +534,20 @@ __global__ __launch_bounds__(256) void edge_weight_table_chunks_kernel(
         if (tid == 0) __hip_atomic_fetch_add(done_ctr, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
+__global__ __launch_bounds__(256) void edge_weight_table_chunks_kernel(
+    const float *__restrict__ edge_attr, const int *__restrict__ type_rep_edge, int fe, EdgeMlpLayers layers, int cc,
+    float *__restrict__ wtab_all, int n_types, RootPtrs roots, float *__restrict__ wimg_all, unsigned *__restrict__ done_ctr,
+    const unsigned *__restrict__ root_max, float img_scale, const int *__restrict__ n_types_dev, int max_types_dev) {
+    edge_weight_table_chunks_body(edge_attr, type_rep_edge, fe, layers, cc, wtab_all, n_types, roots, wimg_all, done_ctr, root_max,
+                                  img_scale, n_types_dev, max_types_dev, (int)blockIdx.x, (int)blockIdx.y);
+}
+// ... and its union form: blockIdx.z = layout (see edge_weight_table_union_kernel; this grid does not depend on the type counts)
+__global__ __launch_bounds__(256) void edge_weight_table_chunks_union_kernel(const EdgeWeightUnionEntry *__restrict__ tab, int fe,
+                                                                             EdgeMlpLayers layers, int cc, RootPtrs roots) {
+    const EdgeWeightUnionEntry e = tab[blockIdx.z];
+    edge_weight_table_chunks_body(e.edge_attr, e.type_rep_edge, fe, layers, cc, e.wtab, e.n_types, roots, e.wimg, nullptr, nullptr, 1.0f,
+                                  nullptr, 0, (int)blockIdx.x, (int)blockIdx.y);
+}
 
 constexpr size_t kMaxDynLds = 160 * 1024 - 256;
 
@@ -545,6 +577,19 @@ void launch_edge_weight_table_batched(const float *edge_attr, const int *type_re
     edge_weight_table_kernel<<<dim3(n_types + (image ? 1 : 0), depth), 256, 0, s>>>(edge_attr, type_rep_edge, fe, layers, c * c, wtab,
                                                                                   n_types, rp, image ? wimg_all : nullptr, done_ctr,
                                                                                   image ? root_max : nullptr, img_scale);
+}
+
+// The edge weights and bf16 x 3 operand images (width 32) of n_layouts layouts in ONE launch: the union form of whichever of the two
+// kernels launch_edge_weight_table_batched picks for these dims; per (layout, layer, type) the computation is the solo one
+void launch_edge_weight_table_union(const EdgeWeightUnionEntry *tab_dev, int n_layouts, int max_types, int fe, const EdgeMlpLayers &layers,
+                                    int depth, const float *const *roots, hipStream_t s) {
+    constexpr int c = 32;
+    RootPtrs rp{};
+    for (int i = 0; i < depth; ++i) rp.p[i] = roots[i];
+    if (edge_table_by_chunks(fe, c))
+        edge_weight_table_chunks_union_kernel<<<dim3(c * c / 256 + 1, depth, n_layouts), 256, 0, s>>>(tab_dev, fe, layers, c * c, rp);
+    else
+        edge_weight_table_union_kernel<<<dim3(max_types + 1, depth, n_layouts), 256, 0, s>>>(tab_dev, fe, layers, c * c, rp);
 }
 
 // words [0, n_zero) = 0; then block b < depth: max |roots[b]| -> root_max[b]; the other blocks: their share of dense_w -> *dense_max

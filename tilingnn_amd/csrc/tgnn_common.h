@@ -480,6 +480,16 @@ void launch_edge_weight_table_batched(const float *edge_attr, const int *type_re
                                       float *wimg_all, hipStream_t s, unsigned *done_ctr = nullptr,
                                       const unsigned *root_max = nullptr, float img_scale = 1.0f, const int *n_types_dev = nullptr,
                                       int max_types_dev = 0);
+// The same for n_layouts layouts in one launch (tgnn_forward_union; width 32, bf16 x 3 images): a device table of the layouts' own
+// pointers and type counts, one more grid dimension over it; max_types = the largest n_types of the table
+struct EdgeWeightUnionEntry {
+    const float *edge_attr;
+    const int *type_rep_edge;
+    float *wtab, *wimg;
+    int n_types, pad_;
+};
+void launch_edge_weight_table_union(const EdgeWeightUnionEntry *tab_dev, int n_layouts, int max_types, int fe, const EdgeMlpLayers &layers,
+                                    int depth, const float *const *roots, hipStream_t s);
 // [r6] n_types_dev (device): the kernel reads the type count itself (more than max_types_dev: it writes nothing) -- only where the
 // launch's grid does not depend on the count:
 bool edge_weight_table_device_count_ok(int fe, int c);
@@ -596,6 +606,22 @@ int launch_forward_small(const tgnn_model_dims *d, const Params &P, const float 
                          float *a2_1, const float *wimg, float *pack, const tgnn_graph *graph, double *part, double *part_wide,
                          double *runstat, unsigned *ctr, const unsigned *weights_done, unsigned weights_target, int64_t n,
                          int update_running, float eps, float momentum, hipStream_t s);
+// K small layouts in ONE persistent launch (forward_small.hip: forward_layers_small_union_kernel; tgnn_forward_union).
+// small_union_tiles: the blocks of the layout's team, 0 = not eligible -- the conditions of small_layout_teams; small_union_capacity:
+// blocks one launch may carry; small_union_plan: teams -> consecutive groups of at most `capacity` blocks (-1: stays out), returns
+// their number.  launch_forward_small_union queues, on `s` and in order, one table copy, one pack, one edge-weight launch and one
+// kernel per group; the per-layout buffers are the forward workspace's (train-mode BatchNorm, running statistics untouched).
+struct SmallUnionLayout {
+    const float *x, *edge_attr;
+    const tgnn_graph *graph;
+    float *probs, *mid, *a2_0, *a2_1, *wtab, *wimg;
+    double *part, *part_wide;
+};
+int small_union_tiles(const tgnn_model_dims *d, int64_t n_nodes, int n_types, int max_in_degree);
+int small_union_capacity();
+int small_union_plan(const int *teams, int k, int capacity, int32_t *group_out);
+int launch_forward_small_union(const tgnn_model_dims *d, const Params &P, const SmallUnionLayout *L, int k, const int32_t *group,
+                               int n_groups, float eps, float momentum, hipStream_t s);
 // Mid-size layouts (up to 65 536 nodes): the 20 layers as ONE persistent kernel between the general schedule's init and final
 // MLP (forward_mid.hip).  mid_layout_tiles_per_block: 0 = not eligible; the pack (GIN images + parameter vectors) is
 // launch_small_pack's, the NNConv images are the fp16-pair ones of launch_edge_weight_table_batched.

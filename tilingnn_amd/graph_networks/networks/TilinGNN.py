@@ -145,7 +145,7 @@ class TilinGNN(Tracked, nn.Module):
         return state
 
     # ---- forward ----------------------------------------------------------------------------
-    def forward_many(self, layouts, streams: int = 3):
+    def forward_many(self, layouts, streams: int = 3, union: bool = False):
         """K independent layouts, every one a batch of its own (own BatchNorm statistics: exactly what K forward() calls
         compute, bit for bit) scored SIDE BY SIDE -- the reference's crop loop (Tiling-Shape.py:52-64) and the first rounds of
         several greedy solves hand over layouts of ~1 000 nodes that fill a third of the chip each.  layouts: sequence of
@@ -155,6 +155,11 @@ class TilinGNN(Tracked, nn.Module):
         than HIP's default 4 hardware queues (current + side + K layout streams): GPU_MAX_HW_QUEUES=8 in the environment before
         the process's first GPU call; the streams used are measured to overlap (_lib.concurrent_streams).  Train mode: the running statistics are left
         untouched (K concurrent updates of the same buffers would race; they do not enter train-mode outputs).
+        union=True: the layouts a solo forward would send down the small-layout path (train-mode BatchNorm) are scored inside ONE
+        persistent kernel launch per ~240 blocks on the current stream -- every layout a team of blocks with its own barrier counter
+        and BatchNorm population, behind one parameter pack, one edge-weight launch and one table copy for all of them
+        (tgnn_forward_union, csrc/forward_small.hip); the preparation stays per layout on the lanes, every other layout takes
+        its lane as before.  The same bits either way.
         Returns the list of probs tensors, ready on the current stream."""
         table, dev = self._param_table()
         layouts = list(layouts)
@@ -185,6 +190,16 @@ class TilinGNN(Tracked, nn.Module):
             xs.append(xf); attrs.append(ea); graphs.append(graph); outs.append(probs); wss.append(ws)
         arr = lambda ts: (C.c_void_p * k_n)(*[t.data_ptr() for t in ts])
         gs = (_lib.Graph * k_n)(*[g.c_struct() for g in graphs])
+        if union:
+            for st in used:                                      # the preparations: in front of the union launches on the current stream
+                cur.wait_stream(st)
+            check(lib.tgnn_forward_union(C.byref(dims), table, k_n, arr(xs), arr(attrs), gs, int(not bn_train), arr(outs), arr(wss),
+                                         (C.c_size_t * k_n)(*[int(w.numel()) for w in wss]), cur.cuda_stream,
+                                         (C.c_void_p * len(used))(*[st.cuda_stream for st in used]), len(used), _lib.side_stream(dev)))
+            for st in used:
+                cur.wait_stream(st)
+                st.wait_stream(cur)                              # (workspaces and graphs are the lanes' memory: reused there behind the launches)
+            return outs
         check(lib.tgnn_forward_many(C.byref(dims), table, k_n, arr(xs), arr(attrs), gs, 0, int(not bn_train), arr(outs), arr(wss),
                                     (C.c_size_t * k_n)(*[int(w.numel()) for w in wss]),
                                     (C.c_void_p * len(used))(*[st.cuda_stream for st in used]), len(used), _lib.side_stream(dev)))

@@ -56,6 +56,9 @@ class ML_Solver:
         # layouts at least that large take tilingnn_amd.util.algorithms.solve_by_device_greedy (batched acceptance on the GPU)
         self.device_greedy_min_nodes = None
         self.device_greedy_seed = 0
+        # solve_many / solve_many_by_device_greedy: score every round's small sub-layouts inside ONE persistent kernel launch
+        # (TilinGNN.forward_many(union=True), csrc/forward_small.hip); the same results either way
+        self.union_forward = False
 
     @staticmethod
     def _no_edges(index) -> bool:
@@ -144,7 +147,9 @@ class ML_Solver:
         same seed (default: `device_greedy_seed`), whatever `device_greedy_min_nodes` says.  Returns a list of
         (output_layout, score) in input order; `predict`, `predict_order` as in `solve`; `predict_probs` = the first round's
         probabilities (the first round's sub-layout IS the layout: what `self.predict(layout)` returns, without K more forwards).
-        In train mode the BatchNorm running statistics are left untouched (see `TilinGNN.forward_many`)."""
+        In train mode the BatchNorm running statistics are left untouched (see `TilinGNN.forward_many`).
+        `self.union_forward = True`: every round's small sub-layouts are scored inside one persistent kernel launch
+        (`TilinGNN.forward_many(union=True)`): the same results, fewer launches per round."""
         from ...util.algorithms import solve_many_by_device_greedy
         brick_layouts = list(brick_layouts)
         if not brick_layouts:

@@ -298,17 +298,18 @@ class PackedLayouts:
                             None if inverse is None else inverse[n0:n0 + n])
 
 
-def _forward_many_checked(network, subs, streams):
+def _forward_many_checked(network, subs, streams, union=False):
     """`forward_many` + what `forward_checked` adds to a forward, ONCE for all layouts: a stale-result status of an earlier
     unchecked forward is answered by queueing the forwards again; the health word of the persistent kernels is polled (this
     synchronises the current stream) and, if set, the forwards are repeated on the general launch schedule."""
     args = [(s.node_feature, s.align_edge_index, s.align_edge_features, s.collide_edge_index) for s in subs]
+    kw = {"union": True} if union else {}                       # (union: after a starved kernel the fall-back window keeps every layout out of it)
     try:
-        outs = network.forward_many(args, streams=streams)
+        outs = network.forward_many(args, streams=streams, **kw)
     except _lib.TgnnError as exc:
         if exc.code != _lib.ERR_STALE_RESULT:
             raise
-        outs = network.forward_many(args, streams=streams)
+        outs = network.forward_many(args, streams=streams, **kw)
     dev = subs[0].node_feature.device
     code = C.c_uint32(0)
     check(lib.tgnn_spin_error_poll(_lib.current_stream(dev), C.byref(code)))
@@ -317,7 +318,7 @@ def _forward_many_checked(network, subs, streams):
         warnings.warn("tilingnn_amd: a persistent forward kernel gave up waiting for its blocks (another process holds compute "
                       f"units; reason bits {code.value}); the forwards are repeated on the general launch schedule, which the "
                       "next forwards of this process take as well", RuntimeWarning)
-        outs = network.forward_many(args, streams=streams)
+        outs = network.forward_many(args, streams=streams, **kw)
     return outs
 
 
@@ -334,7 +335,9 @@ def solve_many_by_device_greedy(ml_solver, layouts, seed=0, seeds=None, score_fn
     `layouts`: a list of DeviceLayouts / BrickLayout-like numpy layouts, or a PackedLayouts; seeds: one per layout (default:
     `seed` for all).  Returns a list of K (selection, score, predict_order); `.last_rounds` = the K round counts,
     `.last_first_probs` = the first round's probabilities per layout ([n_k] float32 on the device: what predict_on_device
-    gives for the whole layout)."""
+    gives for the whole layout).  `ml_solver.union_forward = True` (an attribute like `device_greedy_seed`, default False): every
+    round's small sub-layouts are scored inside one persistent kernel launch (`forward_many(union=True)`) -- the same bits, fewer
+    launches."""
     device = ml_solver.device
     originals = None if isinstance(layouts, PackedLayouts) else list(layouts)
     solve_many_by_device_greedy.last_rounds = []
@@ -387,6 +390,7 @@ def solve_many_by_device_greedy(ml_solver, layouts, seed=0, seeds=None, score_fn
     words_h[:K] = 0
     meta.copy_(meta_h, non_blocking=True)
     network = ml_solver.network
+    union_forward = bool(getattr(ml_solver, "union_forward", False))
     rnd = 0
 
     def raise_errors(words):
@@ -435,7 +439,7 @@ def solve_many_by_device_greedy(ml_solver, layouts, seed=0, seeds=None, score_fn
         if need_net:
             views = [subs[k] for k in need_net]
             if hasattr(network, "forward_many"):
-                outs = _forward_many_checked(network, views, streams)
+                outs = _forward_many_checked(network, views, streams, union_forward)
             else:
                 outs = [ml_solver.predict_on_device(v).reshape(-1, 1) for v in views]
             for k, sub, out in zip(need_net, views, outs):
