@@ -586,6 +586,42 @@ int tgnn_graph_prep_small(const int64_t *adj_edge_index, int64_t n_adj_edges, co
                           int32_t *col_slot_src, int32_t *tmp, int32_t *result, uint32_t *counters, int32_t *result_host,
                           tgnn_stream_t stream);
 
+/* K small layouts prepared in ONE launch per group of at most (compute units - 16) blocks, behind ONE read-back: the union form of
+ * tgnn_graph_prep_small.  Layout j is a TEAM of blocks of the launch -- exactly the block count the solo call picks for it, its
+ * own barrier / exit counter pair on its own 128-byte line -- that runs the solo kernel's body with the team's block index and
+ * size in place of the grid's: every output is the solo call's, bit for bit.  A layout's arguments (those of tgnn_graph_prep_small;
+ * tmp: tgnn_graph_prep_small_tmp_ints() ints of its own): */
+typedef struct tgnn_small_prep_layout {
+    const int64_t *adj_edge_index;
+    const float *adj_edge_attr;
+    const int64_t *col_edge_index;
+    int64_t n_adj_edges, n_col_edges, n_nodes;
+    int32_t *adj_rowptr, *adj_src, *adj_eid, *adj_type, *edge_type, *type_rep_edge;
+    int32_t *col_rowptr, *col_src, *col_eid;
+    int32_t *tile_col_ptr, *col_meta, *col_slot_src;
+    int32_t *tmp;
+    int32_t fe, reserved_;
+} tgnn_small_prep_layout;
+/* Every layout is checked as tgnn_graph_prep_small checks it; if one fails nothing is queued.  On `stream`, in order: one copy of
+ * the device table and the groups' prefix arrays (staged in pinned memory), the zeroing of the k counter lines, one launch per
+ * group (tgnn_graph_prep_small_many_plan with the device's capacity), one copy of results_dev [k][32] (words 0 - 6 as
+ * tgnn_graph_prep_small's result, 7 - 31 zero) into results_host (pinned, [k][32]) and one event.  Table, prefix arrays and
+ * counters are the library's (per device, grow only, a ring of sets each guarded by an event).
+ * tgnn_graph_prep_small_many_wait(stream): same host thread, the stream the call was given; waits for that event -- the call's one
+ * host synchronisation.  An out-of-range edge end sets word 1 / 2 of ITS layout; the edge is skipped, the other layouts' outputs
+ * are what they would be without it. */
+int tgnn_graph_prep_small_many(const tgnn_small_prep_layout *layouts_host, int32_t k, int32_t *results_dev, int32_t *results_host,
+                               tgnn_stream_t stream);
+int tgnn_graph_prep_small_many_wait(tgnn_stream_t stream);
+/* The teams and the grouping alone (host only, no device needed): blocks_out[j] = the blocks the solo call launches for layout j,
+ * max(ceil(max(ea, ec) / 2048), ceil(ea / 8192), 1) capped at 16; group_out[j] = the launch it rides in -- consecutive from 0,
+ * greedy in input order, at most capacity_blocks blocks each -- or -1 where tgnn_graph_prep_small would reject the layout by size
+ * (blocks_out[j] = 0).  Returns the number of groups, or TGNN_ERR_INVALID_ARG (k < 1, capacity_blocks < 16, a negative count). */
+int tgnn_graph_prep_small_many_plan(const int64_t *n_adj_edges, const int64_t *n_col_edges, const int64_t *n_nodes, int32_t k,
+                                    int32_t capacity_blocks, int32_t *blocks_out, int32_t *group_out);
+/* out[0] = launches queued by tgnn_graph_prep_small_many so far in this process, out[1] = layouts prepared inside them. */
+void tgnn_graph_prep_small_many_counts(int64_t out[2]);
+
 /* The same at any size: one call that queues every launch of the preparation itself (no host round trip in the middle:
  * the column structure reads the type count from the device).  result [32] as above; word 6 = 1: the layout has more than
  * 4 096 distinct attribute rows -- more than the one-block numbering of the types takes: edge_type / adj_type / the column

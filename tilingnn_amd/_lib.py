@@ -38,6 +38,17 @@ class Graph(C.Structure):
                 ("nn_tile_grp_ptr", C.c_void_p), ("nn_grp", C.c_void_p), ("nn_mid_verdict", C.c_void_p)]
 
 
+class SmallPrepLayout(C.Structure):
+    """tgnn_small_prep_layout"""
+    _fields_ = [("adj_edge_index", C.c_void_p), ("adj_edge_attr", C.c_void_p), ("col_edge_index", C.c_void_p),
+                ("n_adj_edges", C.c_int64), ("n_col_edges", C.c_int64), ("n_nodes", C.c_int64),
+                ("adj_rowptr", C.c_void_p), ("adj_src", C.c_void_p), ("adj_eid", C.c_void_p), ("adj_type", C.c_void_p),
+                ("edge_type", C.c_void_p), ("type_rep_edge", C.c_void_p),
+                ("col_rowptr", C.c_void_p), ("col_src", C.c_void_p), ("col_eid", C.c_void_p),
+                ("tile_col_ptr", C.c_void_p), ("col_meta", C.c_void_p), ("col_slot_src", C.c_void_p),
+                ("tmp", C.c_void_p), ("fe", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class TrainSave(C.Structure):
     """tgnn_train_save"""
     _fields_ = [("init_a", C.c_void_p * 2), ("init_stat", C.c_void_p * 2), ("a1", C.c_void_p), ("a2", C.c_void_p),
@@ -158,6 +169,10 @@ def _load() -> C.CDLL:
         "tgnn_graph_prep_workspace_bytes": (sz, [i64, i64, i64, i32]),
         "tgnn_graph_prep": (C.c_int, [p, i64, p, i32, p, i64, i64, i64] + [p] * 17 + [sz, p, p, p]),
         "tgnn_graph_prep_wait": (C.c_int, [p]),
+        "tgnn_graph_prep_small_many": (C.c_int, [C.POINTER(SmallPrepLayout), i32, p, p, p]),
+        "tgnn_graph_prep_small_many_wait": (C.c_int, [p]),
+        "tgnn_graph_prep_small_many_plan": (C.c_int, [p, p, p, i32, i32, p, p]),
+        "tgnn_graph_prep_small_many_counts": (None, [p]),
         "tgnn_set_nnconv_eg": (i32, [i32]),
         "tgnn_set_dense_rows_mode": (i32, [i32]),
         "tgnn_set_lean_head": (i32, [i32]),
@@ -256,7 +271,7 @@ EXPORTED_SYMBOLS = (
     "tgnn_spin_error_poll", "tgnn_set_spin_budget_us", "tgnn_persist_fallback", "tgnn_spin_error_peek", "tgnn_gin_fwd", "tgnn_dense_act_fwd", "tgnn_dense_act_slots_fwd", "tgnn_dense_act_slots_f16_fwd", "tgnn_bn_finalize", "tgnn_bn_apply",
     "tgnn_merge_fwd", "tgnn_param_count", "tgnn_param_name", "tgnn_forward_workspace_bytes", "tgnn_forward", "tgnn_forward_begin", "tgnn_forward_resume",
     "tgnn_forward_profiled", "tgnn_forward_profiled_two_stream", "tgnn_forward_stamped", "tgnn_forward_many", "tgnn_forward_union", "tgnn_forward_union_plan", "tgnn_forward_union_counts", "tgnn_graph_prep_small_max_nodes", "tgnn_graph_prep_small_max_edges", "tgnn_graph_prep_small_tmp_ints",
-    "tgnn_graph_prep_small", "tgnn_graph_prep_workspace_bytes", "tgnn_graph_prep", "tgnn_graph_prep_wait", "tgnn_set_small_layout_limit", "tgnn_get_small_layout_limit", "tgnn_set_split_precision", "tgnn_set_gin_fused", "tgnn_set_gin_mlp_f16", "tgnn_set_mid_tail", "tgnn_set_nnconv_eg", "tgnn_set_dense_rows_mode", "tgnn_set_lean_head", "tgnn_set_prep_words_poll", "tgnn_forward_begin_weights", "tgnn_forward_bf16_begin", "tgnn_forward_small_prepass", "tgnn_rccl_available", "tgnn_rccl_unique_id_bytes", "tgnn_rccl_unique_id", "tgnn_rccl_comm_create", "tgnn_rccl_comm_destroy", "tgnn_rccl_counters", "tgnn_forward_train", "tgnn_backward_workspace_bytes", "tgnn_backward", "tgnn_forward_sharded_workspace_bytes", "tgnn_forward_sharded",
+    "tgnn_graph_prep_small", "tgnn_graph_prep_workspace_bytes", "tgnn_graph_prep", "tgnn_graph_prep_wait", "tgnn_graph_prep_small_many", "tgnn_graph_prep_small_many_wait", "tgnn_graph_prep_small_many_plan", "tgnn_graph_prep_small_many_counts", "tgnn_set_small_layout_limit", "tgnn_get_small_layout_limit", "tgnn_set_split_precision", "tgnn_set_gin_fused", "tgnn_set_gin_mlp_f16", "tgnn_set_mid_tail", "tgnn_set_nnconv_eg", "tgnn_set_dense_rows_mode", "tgnn_set_lean_head", "tgnn_set_prep_words_poll", "tgnn_forward_begin_weights", "tgnn_forward_bf16_begin", "tgnn_forward_small_prepass", "tgnn_rccl_available", "tgnn_rccl_unique_id_bytes", "tgnn_rccl_unique_id", "tgnn_rccl_comm_create", "tgnn_rccl_comm_destroy", "tgnn_rccl_counters", "tgnn_forward_train", "tgnn_backward_workspace_bytes", "tgnn_backward", "tgnn_forward_sharded_workspace_bytes", "tgnn_forward_sharded",
     "tgnn_rows_gather", "tgnn_rows_scatter", "tgnn_unsupervised_loss_workspace_bytes", "tgnn_unsupervised_loss", "tgnn_solution_score_sums",
     "tgnn_sublayout_workspace_bytes", "tgnn_sublayout_compact", "tgnn_greedy_round_workspace_bytes", "tgnn_greedy_round", "tgnn_greedy_finish_max_nodes", "tgnn_greedy_finish", "tgnn_shard_alive_rows",
     "tgnn_sublayout_compact_many_workspace_bytes", "tgnn_sublayout_compact_many", "tgnn_greedy_round_many_workspace_bytes", "tgnn_greedy_round_many",
@@ -293,6 +308,26 @@ def forward_union_plan(n_nodes, capacity_blocks):
     if n_groups < 0:
         raise ValueError("tgnn_forward_union_plan: invalid arguments")
     return [int(out[i]) for i in range(k)], n_groups
+
+
+def graph_prep_small_many_counts():
+    """(launches queued by tgnn_graph_prep_small_many, layouts prepared inside them) so far in this process."""
+    out = (C.c_int64 * 2)()
+    lib.tgnn_graph_prep_small_many_counts(out)
+    return tuple(int(v) for v in out)
+
+
+def graph_prep_small_many_plan(n_adj_edges, n_col_edges, n_nodes, capacity_blocks):
+    """tgnn_graph_prep_small_many_plan: (team size of every layout, 0 = not taken; its group, -1 = not taken; number of groups)."""
+    k = len(n_nodes)
+    if not (len(n_adj_edges) == len(n_col_edges) == k):
+        raise ValueError("tgnn_graph_prep_small_many_plan: one count of each kind per layout")
+    arr = lambda vs: (C.c_int64 * max(k, 1))(*[int(v) for v in vs])
+    blocks, groups = (C.c_int32 * max(k, 1))(), (C.c_int32 * max(k, 1))()
+    n_groups = int(lib.tgnn_graph_prep_small_many_plan(arr(n_adj_edges), arr(n_col_edges), arr(n_nodes), k, int(capacity_blocks), blocks, groups))
+    if n_groups < 0:
+        raise ValueError("tgnn_graph_prep_small_many_plan: invalid arguments")
+    return [int(blocks[i]) for i in range(k)], [int(groups[i]) for i in range(k)], n_groups
 
 
 def check(rc: int) -> None:

@@ -9,6 +9,7 @@
 #include <atomic>
 #include <chrono>
 #include <mutex>
+#include <vector>
 
 #include "tgnn_common.h"
 
@@ -761,7 +762,13 @@ __device__ __forceinline__ void small_prep_barrier(unsigned *ctr, unsigned &targ
     __syncthreads();
 }
 
-__global__ __launch_bounds__(kSmallPrepThreads) void graph_prep_small_kernel(SmallPrepArgs A) {
+// The preparation itself, for a TEAM of `G` blocks of which this one is number `blk`: the whole grid of a solo launch
+// (graph_prep_small_kernel) or one layout's blocks of a union launch (graph_prep_small_union_kernel).  Nothing in here reads
+// blockIdx / gridDim: thread numbers, the block-0 writers, the barrier targets and the exit counter all go by (blk, G), so a team
+// of a union launch computes what the grid of the same size computes alone.  kUnion: the words behind the seven result words are
+// zeroed as well (the host reads all 32 of every layout from one copy), nothing is stored into host memory.
+template <bool kUnion>
+__device__ __forceinline__ void graph_prep_small_body(const SmallPrepArgs A, const int blk, const int G) {
     extern __shared__ int sm[];
     int *rpA = sm;                                    // [n + 1] row starts of the adjacency CSR (every block scans its own copy)
     int *rpC = rpA + kSmallPrepMaxNodes + 8;
@@ -769,7 +776,7 @@ __global__ __launch_bounds__(kSmallPrepThreads) void graph_prep_small_kernel(Sma
     int *gslot = ltab + kSmallPrepLocal;              // [kSmallPrepLocal] global slot of a local slot; later: the column counts
     int *misc = gslot + kSmallPrepLocal;              // [64]
     int *wave_tot = misc;
-    const int tid = threadIdx.x, NT = kSmallPrepThreads, G = gridDim.x, blk = blockIdx.x;
+    const int tid = threadIdx.x, NT = kSmallPrepThreads;
     const int gtid = blk * NT + tid, GT = G * NT;
     const int n = (int)A.n, ea = (int)A.ea, ec = (int)A.ec;
     const int emax = ea > ec ? ea : ec, nt16 = (n + kColTileRows - 1) / kColTileRows;
@@ -1104,7 +1111,7 @@ __global__ __launch_bounds__(kSmallPrepThreads) void graph_prep_small_kernel(Sma
         A.result[4] = maxdeg;
         A.result[5] = cols ? 1 : 0;
         A.result[6] = fallback ? 1 : 0;
-        if (A.result_host) {                               // [r6] no copy, no stream synchronise: the host polls word 31 (tgnn_graph_prep_wait)
+        if (!kUnion && A.result_host) {                               // [r6] no copy, no stream synchronise: the host polls word 31 (tgnn_graph_prep_wait)
             const int w[7] = {n_types, g_flags[0], g_flags[1], ec_valid, maxdeg, cols ? 1 : 0, fallback ? 1 : 0};
 #pragma unroll
             for (int k = 0; k < 7; ++k) __hip_atomic_store(A.result_host + k, w[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -1113,12 +1120,44 @@ __global__ __launch_bounds__(kSmallPrepThreads) void graph_prep_small_kernel(Sma
             __hip_atomic_store(A.result_host + 31, kPrepWordsMagic, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
+    if (kUnion && blk == 0 && tid >= 7 && tid < 32) A.result[tid] = 0;
     // the last block out re-arms the counters for the next call
     __syncthreads();
     if (tid == 0 && atomicAdd(&A.ctr[1], 1u) == (unsigned)G - 1) {
         __hip_atomic_store(&A.ctr[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(&A.ctr[1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+}
+
+__global__ __launch_bounds__(kSmallPrepThreads) void graph_prep_small_kernel(SmallPrepArgs A) {
+    graph_prep_small_body<false>(A, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// ---- K layouts in ONE launch (tgnn_graph_prep_small_many) ------------------------------------------------------------------
+// Layout j of the launch owns the blocks [first_block[j], first_block[j + 1]): a team of exactly the size the solo launcher picks
+// for the layout (small_prep_blocks), which runs graph_prep_small_body as the grid of a solo launch does -- the same shares of the
+// edges per block, the same LDS tables, the same numbering -- with its own barrier / exit counter pair (a 128-byte line per team)
+// and its own scratch.  The layout's arguments come from a device table; the address is uniform, the loads are scalar.
+__global__ __launch_bounds__(kSmallPrepThreads) void graph_prep_small_union_kernel(const SmallPrepArgs *__restrict__ tab,
+                                                                                   const int *__restrict__ first_block, int n_layouts) {
+    // the block's layout: the largest j with first_block[j] <= blockIdx.x (wave-uniform: every operand is)
+    int lo = 0, hi = n_layouts;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (first_block[mid] <= (int)blockIdx.x) lo = mid; else hi = mid;
+    }
+    const int j = __builtin_amdgcn_readfirstlane(lo);
+    const int b0 = __builtin_amdgcn_readfirstlane(first_block[j]), b1 = __builtin_amdgcn_readfirstlane(first_block[j + 1]);
+    const SmallPrepArgs *e = tab + j;
+    SmallPrepArgs A;                                   // (field by field: the struct stays in registers)
+    A.adj_ei = e->adj_ei; A.col_ei = e->col_ei; A.attr = e->attr;
+    A.n = e->n; A.ea = e->ea; A.ec = e->ec; A.fe = e->fe; A.max_col_types = e->max_col_types;
+    A.adj_rowptr = e->adj_rowptr; A.adj_src = e->adj_src; A.adj_eid = e->adj_eid; A.adj_type = e->adj_type;
+    A.edge_type = e->edge_type; A.type_rep = e->type_rep;
+    A.col_rowptr = e->col_rowptr; A.col_src = e->col_src; A.col_eid = e->col_eid;
+    A.tile_col_ptr = e->tile_col_ptr; A.col_meta = e->col_meta; A.col_slot_src = e->col_slot_src;
+    A.result_host = nullptr; A.tmp = e->tmp; A.result = e->result; A.ctr = e->ctr;
+    graph_prep_small_body<true>(A, (int)blockIdx.x - b0, b1 - b0);
 }
 
 static inline unsigned grid_for(int64_t n, int threads = 256, int cap = 256 * 16) {
@@ -1892,6 +1931,24 @@ extern "C" size_t tgnn_graph_prep_small_tmp_ints(int64_t n_nodes, int64_t n_adj_
     return (size_t)(2 * (n_nodes + 1) + 3 * n_adj_edges + 2 * n_col_edges + kSmallPrepGlobal + (n_nodes + 15) / 16 + 1 + 16 + 64);
 }
 
+// blocks of a layout's preparation (the grid of the solo launch = the team of a union launch): ~2048 edges each, and enough of
+// them that a block's share of the adjacency edges fits its LDS table
+static int small_prep_blocks(int64_t n_adj_edges, int64_t n_col_edges) {
+    const int64_t emax = n_adj_edges > n_col_edges ? n_adj_edges : n_col_edges;
+    int64_t blocks = (emax + 2047) / 2048;
+    const int64_t need = (n_adj_edges + kSmallPrepLocal - 1) / kSmallPrepLocal;
+    if (blocks < need) blocks = need;
+    if (blocks < 1) blocks = 1;
+    if (blocks > kSmallPrepMaxBlocks) blocks = kSmallPrepMaxBlocks;
+    return (int)blocks;
+}
+constexpr size_t kSmallPrepLds = (size_t)(2 * (kSmallPrepMaxNodes + 8) + 2 * kSmallPrepLocal + 64) * sizeof(int);   // one block per CU
+static bool small_prep_size_ok(int64_t n_nodes, int64_t n_adj_edges, int64_t n_col_edges) {
+    const int64_t emax_allowed = (int64_t)kSmallPrepMaxBlocks * kSmallPrepLocal;
+    return n_nodes >= 1 && n_nodes <= kSmallPrepMaxNodes && n_adj_edges >= 0 && n_adj_edges <= emax_allowed && n_col_edges >= 0 &&
+           n_col_edges <= emax_allowed;
+}
+
 extern "C" int tgnn_graph_prep_small(const int64_t *adj_edge_index, int64_t n_adj_edges, const float *adj_edge_attr, int32_t fe,
                                      const int64_t *col_edge_index, int64_t n_col_edges, int64_t n_nodes, int32_t *adj_rowptr,
                                      int32_t *adj_src, int32_t *adj_eid, int32_t *adj_type, int32_t *edge_type,
@@ -1931,14 +1988,8 @@ extern "C" int tgnn_graph_prep_small(const int64_t *adj_edge_index, int64_t n_ad
             (void)hipGetLastError();                           // (not addressable by this device: the copy + event below instead)
         }
     }
-    // blocks: ~2048 edges each, and enough of them that a block's share of the adjacency edges fits its LDS table
-    const int64_t emax = n_adj_edges > n_col_edges ? n_adj_edges : n_col_edges;
-    int64_t blocks = (emax + 2047) / 2048;
-    const int64_t need = (n_adj_edges + kSmallPrepLocal - 1) / kSmallPrepLocal;
-    if (blocks < need) blocks = need;
-    if (blocks < 1) blocks = 1;
-    if (blocks > kSmallPrepMaxBlocks) blocks = kSmallPrepMaxBlocks;
-    const size_t lds = (size_t)(2 * (kSmallPrepMaxNodes + 8) + 2 * kSmallPrepLocal + 64) * sizeof(int);
+    const int blocks = small_prep_blocks(n_adj_edges, n_col_edges);
+    const size_t lds = kSmallPrepLds;
     static LdsOptIn site;
     TGNN_CHECK_HIP(opt_in_dynamic_lds(graph_prep_small_kernel, (int)lds, site));
     // the counters are zero on entry whatever a previous call left behind (an aborted launch would otherwise make every
@@ -1961,6 +2012,198 @@ extern "C" int tgnn_graph_prep_small(const int64_t *adj_edge_index, int64_t n_ad
         TGNN_CHECK_HIP(hipEventRecord(ev_words, s));
     }
     TGNN_CHECK_LAUNCH();
+    return TGNN_OK;
+}
+
+/* ---- K small layouts: one launch per group of teams, one read-back (the union form of tgnn_graph_prep_small) ------------- */
+// teams -> consecutive groups of at most `capacity` blocks, greedy in input order (blocks[j] = 0: layout j stays out, group -1)
+static int small_prep_plan(const int32_t *blocks, int k, int capacity, int32_t *group_out) {
+    int group = -1, used = 0;
+    for (int j = 0; j < k; ++j) {
+        if (blocks[j] <= 0) {
+            group_out[j] = -1;
+            continue;
+        }
+        if (group < 0 || used + blocks[j] > capacity) {
+            ++group;
+            used = 0;
+        }
+        used += blocks[j];
+        group_out[j] = group;
+    }
+    return group + 1;
+}
+
+extern "C" int tgnn_graph_prep_small_many_plan(const int64_t *n_adj_edges, const int64_t *n_col_edges, const int64_t *n_nodes, int32_t k,
+                                               int32_t capacity_blocks, int32_t *blocks_out, int32_t *group_out) {
+    TGNN_CHECK_ARG(k >= 1 && capacity_blocks >= kSmallPrepMaxBlocks, "k / capacity_blocks");
+    TGNN_CHECK_ARG(n_adj_edges && n_col_edges && n_nodes && blocks_out && group_out, "null pointer");
+    for (int j = 0; j < k; ++j) TGNN_CHECK_ARG(n_adj_edges[j] >= 0 && n_col_edges[j] >= 0 && n_nodes[j] >= 0, "negative count");
+    for (int j = 0; j < k; ++j)
+        blocks_out[j] = small_prep_size_ok(n_nodes[j], n_adj_edges[j], n_col_edges[j]) ? small_prep_blocks(n_adj_edges[j], n_col_edges[j]) : 0;
+    return small_prep_plan(blocks_out, k, capacity_blocks, group_out);
+}
+
+static std::atomic<int64_t> g_prep_many_count[2];            // launches queued by tgnn_graph_prep_small_many / layouts prepared inside them
+extern "C" void tgnn_graph_prep_small_many_counts(int64_t *out2) {
+    for (int i = 0; i < 2; ++i) out2[i] = g_prep_many_count[i].load(std::memory_order_relaxed);
+}
+
+// the event behind the call's copy of the result words: one per host thread and device (tgnn_graph_prep_small_many_wait)
+static thread_local hipEvent_t g_prep_many_ev[64] = {};
+static hipError_t prep_many_event(hipEvent_t *ev) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+    if (!g_prep_many_ev[dev]) {
+        e = hipEventCreateWithFlags(&g_prep_many_ev[dev], hipEventDisableTiming);
+        if (e != hipSuccess) return e;
+    }
+    *ev = g_prep_many_ev[dev];
+    return hipSuccess;
+}
+
+// Table, prefix arrays and counters live in library-owned per-device buffers that only grow.  The pinned staging buffer (and with
+// it the device buffer: a later call may come on another stream) must not be rewritten while an earlier call's copy or kernels may
+// still be in flight: a RING of kPrepManyRing such sets, each with an EVENT recorded behind the call's last launch that the next user
+// of the set waits for on the host (as launch_forward_small_union's ring).
+namespace {
+constexpr int kPrepManyRing = 4;
+struct PrepManySet {
+    char *dev = nullptr, *host = nullptr;
+    size_t dev_cap = 0, host_cap = 0;
+    hipEvent_t ev = nullptr;
+};
+struct PrepManyRing {
+    PrepManySet set[kPrepManyRing];
+    unsigned next = 0;
+};
+}  // namespace
+
+extern "C" int tgnn_graph_prep_small_many(const tgnn_small_prep_layout *layouts, int32_t k, int32_t *results_dev, int32_t *results_host,
+                                          tgnn_stream_t stream) {
+    static std::mutex mu;
+    static PrepManyRing rings[64];
+    DeviceGuard guard__(stream);
+    TGNN_CHECK_ARG(k >= 1 && layouts && results_dev && results_host, "k / null pointer");
+    for (int j = 0; j < k; ++j) {                                // (every layout before anything is queued)
+        const tgnn_small_prep_layout &l = layouts[j];
+        TGNN_CHECK_ARG(l.n_nodes >= 1 && l.n_nodes <= kSmallPrepMaxNodes, "n_nodes");
+        TGNN_CHECK_ARG(small_prep_size_ok(l.n_nodes, l.n_adj_edges, l.n_col_edges), "edge counts");
+        TGNN_CHECK_ARG(l.fe >= 1, "fe");
+        TGNN_CHECK_ARG(l.adj_rowptr && l.col_rowptr && l.tile_col_ptr && l.col_meta && l.col_slot_src && l.tmp, "null pointer");
+        TGNN_CHECK_ARG(l.n_adj_edges == 0 || (l.adj_edge_index && l.adj_edge_attr && l.adj_src && l.adj_eid && l.adj_type && l.edge_type &&
+                                              l.type_rep_edge), "null adjacency pointer");
+        TGNN_CHECK_ARG(l.n_col_edges == 0 || (l.col_edge_index && l.col_src && l.col_eid), "null collision pointer");
+    }
+    int dev = 0;
+    TGNN_CHECK_HIP(hipGetDevice(&dev));
+    TGNN_CHECK_ARG(dev >= 0 && dev < 64, "device index");
+    const int capacity = device_cus() - 16;                    // (what spin_kernel_chain admits beside nothing else; one block per CU)
+    TGNN_CHECK_ARG(capacity >= kSmallPrepMaxBlocks, "the device has too few compute units for a team of 16 blocks");
+    std::vector<int32_t> blocks((size_t)k), group((size_t)k);
+    for (int j = 0; j < k; ++j) blocks[(size_t)j] = small_prep_blocks(layouts[j].n_adj_edges, layouts[j].n_col_edges);
+    const int n_groups = small_prep_plan(blocks.data(), k, capacity, group.data());
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipEvent_t ev_words = nullptr;
+    TGNN_CHECK_HIP(prep_many_event(&ev_words));
+    static LdsOptIn site;
+    TGNN_CHECK_HIP(opt_in_dynamic_lds(graph_prep_small_union_kernel, (int)kSmallPrepLds, site));
+    // device: counters [k][32] | tables;  tables (= the staging buffer): arguments [k] | first blocks [k + n_groups]
+    const size_t ctr_bytes = (size_t)k * 128, arg_bytes = align_up((size_t)k * sizeof(SmallPrepArgs), 256);
+    const size_t tab_bytes = arg_bytes + align_up((size_t)(k + n_groups) * sizeof(int), 256), dev_bytes = ctr_bytes + tab_bytes;
+    std::lock_guard<std::mutex> lock(mu);
+    PrepManyRing &ring = rings[dev];
+    PrepManySet &u = ring.set[ring.next++ % kPrepManyRing];
+    if (!u.ev) TGNN_CHECK_HIP(hipEventCreateWithFlags(&u.ev, hipEventDisableTiming));
+    else TGNN_CHECK_HIP(hipEventSynchronize(u.ev));
+    if (u.dev_cap < dev_bytes) {                                 // (nothing of this set is in flight: see above)
+        if (u.dev) (void)hipFree(u.dev);
+        u.dev = nullptr;
+        u.dev_cap = 0;
+        TGNN_CHECK_HIP(hipMalloc(reinterpret_cast<void **>(&u.dev), dev_bytes * 2));
+        u.dev_cap = dev_bytes * 2;
+    }
+    if (u.host_cap < tab_bytes) {
+        if (u.host) (void)hipHostFree(u.host);
+        u.host = nullptr;
+        u.host_cap = 0;
+        TGNN_CHECK_HIP(hipHostMalloc(reinterpret_cast<void **>(&u.host), tab_bytes * 2, hipHostMallocDefault));
+        u.host_cap = tab_bytes * 2;
+    }
+    unsigned *ctr = reinterpret_cast<unsigned *>(u.dev);
+    char *tab_dev = u.dev + ctr_bytes;
+    SmallPrepArgs *args = reinterpret_cast<SmallPrepArgs *>(u.host);
+    int *fb = reinterpret_cast<int *>(u.host + arg_bytes);
+    const SmallPrepArgs *args_dev = reinterpret_cast<const SmallPrepArgs *>(tab_dev);
+    const int *fb_dev = reinterpret_cast<const int *>(tab_dev + arg_bytes);
+    struct Group { int first, count, blocks, fb_at; };
+    std::vector<Group> groups((size_t)n_groups, Group{0, 0, 0, 0});
+    const int max_col_types = tgnn_nnconv_cols_max_types();
+    int fb_at = 0;
+    for (int j = 0; j < k; ++j) {
+        const tgnn_small_prep_layout &l = layouts[j];
+        SmallPrepArgs A{};
+        A.adj_ei = l.adj_edge_index; A.col_ei = l.col_edge_index; A.attr = l.adj_edge_attr;
+        A.n = l.n_nodes; A.ea = l.n_adj_edges; A.ec = l.n_col_edges; A.fe = l.fe;
+        A.max_col_types = max_col_types;
+        A.adj_rowptr = l.adj_rowptr; A.adj_src = l.adj_src; A.adj_eid = l.adj_eid; A.adj_type = l.adj_type;
+        A.edge_type = l.edge_type; A.type_rep = l.type_rep_edge;
+        A.col_rowptr = l.col_rowptr; A.col_src = l.col_src; A.col_eid = l.col_eid;
+        A.tile_col_ptr = l.tile_col_ptr; A.col_meta = l.col_meta; A.col_slot_src = l.col_slot_src;
+        A.tmp = l.tmp;
+        A.result = results_dev + (size_t)j * 32;
+        A.ctr = ctr + (size_t)j * 32;                          // (a 128-byte line per team)
+        args[j] = A;
+        Group &G = groups[(size_t)group[(size_t)j]];
+        if (G.count == 0) {
+            G.first = j;
+            G.fb_at = fb_at++;                                  // its prefix array: count + 1 words
+            fb[G.fb_at] = 0;
+        }
+        G.blocks += blocks[(size_t)j];
+        G.count += 1;
+        fb[fb_at++] = G.blocks;
+    }
+    TGNN_CHECK_HIP(hipMemcpyAsync(tab_dev, u.host, tab_bytes, hipMemcpyHostToDevice, s));
+    int rc = TGNN_OK;
+    int64_t launched = 0, prepared = 0;
+    for (const Group &G : groups) {
+        // the teams' counters are zero on entry whatever an earlier call left behind (an aborted launch must not make a later one
+        // hang or pass its barriers early); every block resident: on the per-device chain of spin-barrier kernels
+        if (hipMemsetAsync(ctr + (size_t)G.first * 32, 0, (size_t)G.count * 128, s) != hipSuccess) {
+            set_error("tgnn_graph_prep_small_many: hipMemsetAsync of the counters failed");
+            rc = TGNN_ERR_LAUNCH;
+            break;
+        }
+        struct Ctx { const SmallPrepArgs *tab; const int *fb; int count, blocks; } ctx{args_dev + G.first, fb_dev + G.fb_at, G.count, G.blocks};
+        rc = spin_kernel_chain(s, [](void *c, hipStream_t st) {
+            Ctx *x = static_cast<Ctx *>(c);
+            graph_prep_small_union_kernel<<<dim3(x->blocks), dim3(kSmallPrepThreads), kSmallPrepLds, st>>>(x->tab, x->fb, x->count);
+        }, &ctx, G.blocks);
+        if (rc != TGNN_OK) break;
+        ++launched;
+        prepared += G.count;
+    }
+    if (rc == TGNN_OK && hipMemcpyAsync(results_host, results_dev, (size_t)k * 32 * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess) {
+        set_error("tgnn_graph_prep_small_many: the copy of the result words could not be queued");
+        rc = TGNN_ERR_LAUNCH;
+    }
+    (void)hipEventRecord(ev_words, s);
+    (void)hipEventRecord(u.ev, s);                             // (whatever was queued: the set is free again behind it)
+    g_prep_many_count[0].fetch_add(launched, std::memory_order_relaxed);
+    g_prep_many_count[1].fetch_add(prepared, std::memory_order_relaxed);
+    if (rc != TGNN_OK) return rc;
+    TGNN_CHECK_LAUNCH();
+    return TGNN_OK;
+}
+
+extern "C" int tgnn_graph_prep_small_many_wait(tgnn_stream_t stream) {
+    DeviceGuard guard__(stream);                             // (the event slot of the device the call recorded on: the stream's)
+    hipEvent_t ev = nullptr;
+    TGNN_CHECK_HIP(prep_many_event(&ev));
+    TGNN_CHECK_HIP(hipEventSynchronize(ev));
     return TGNN_OK;
 }
 

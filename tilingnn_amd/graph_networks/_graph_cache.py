@@ -43,13 +43,29 @@ def clear():
     _entries.clear()
 
 
+def _full_key(n_nodes, ts):
+    # (what a prepared graph carries depends on the size range of the mid-size persistent kernel and on the schedule its
+    #  size is run by -- type columns and mid-size batches, or edge groups: part of the key)
+    return ("full", n_nodes, ops.mid_layout_range(), ops.GROUPS and ops.runs_general_schedule(n_nodes)) + _key(*ts)
+
+
+def peek_full(n_nodes, adj_e_index, adj_e_features, col_e_idx):
+    """The cached graph `get_full` would return, or None (a miss, or the cache is off): nothing is built."""
+    ts = (adj_e_index, adj_e_features, col_e_idx)
+    hit = _entries.get(_full_key(n_nodes, ts)) if enabled else None
+    return hit[1] if hit is not None and all(a is b for a, b in zip(hit[0], ts)) else None
+
+
+def put_full(n_nodes, adj_e_index, adj_e_features, col_e_idx, graph):
+    """Enter a graph somebody else prepared (TilinGNN.forward_many: K layouts in one call) under the key `get_full` uses."""
+    return get_full(n_nodes, adj_e_index, adj_e_features, col_e_idx, build=lambda: graph)
+
+
 def get_full(n_nodes, adj_e_index, adj_e_features, col_e_idx, build=None):
     """build: what prepares the graph on a miss (default: ops.prepare_graph) -- TilinGNN.forward passes a builder that queues the
     forward's graph-independent head beside the preparation."""
     ts = (adj_e_index, adj_e_features, col_e_idx)
-    # (what a prepared graph carries depends on the size range of the mid-size persistent kernel and on the schedule its
-    #  size is run by -- type columns and mid-size batches, or edge groups: part of the key)
-    return _lookup(("full", n_nodes, ops.mid_layout_range(), ops.GROUPS and ops.runs_general_schedule(n_nodes)) + _key(*ts), ts,
+    return _lookup(_full_key(n_nodes, ts), ts,
                    build or (lambda: ops.prepare_graph(n_nodes, adj_e_index, adj_e_features, col_e_idx)))
 
 

@@ -145,7 +145,7 @@ class TilinGNN(Tracked, nn.Module):
         return state
 
     # ---- forward ----------------------------------------------------------------------------
-    def forward_many(self, layouts, streams: int = 3, union: bool = False):
+    def forward_many(self, layouts, streams: int = 3, union: bool = False, union_prep: bool = False):
         """K independent layouts, every one a batch of its own (own BatchNorm statistics: exactly what K forward() calls
         compute, bit for bit) scored SIDE BY SIDE -- the reference's crop loop (Tiling-Shape.py:52-64) and the first rounds of
         several greedy solves hand over layouts of ~1 000 nodes that fill a third of the chip each.  layouts: sequence of
@@ -160,6 +160,11 @@ class TilinGNN(Tracked, nn.Module):
         and BatchNorm population, behind one parameter pack, one edge-weight launch and one table copy for all of them
         (tgnn_forward_union, csrc/forward_small.hip); the preparation stays per layout on the lanes, every other layout takes
         its lane as before.  The same bits either way.
+        union_prep=True (honoured only together with union=True): the layouts of up to 4 096 nodes / 131 072 edges per set that
+        are not in the graph cache are prepared by ONE library call on the current stream -- every layout a team of blocks of one
+        launch, one read-back and one host synchronisation for all of them (ops.prepare_graphs_small) -- instead of one call and
+        one synchronisation each on the lanes; their workspaces and outputs are allocated on the current stream.  The same graphs,
+        bit for bit; a layout that call does not take is prepared on its lane as before.
         Returns the list of probs tensors, ready on the current stream."""
         table, dev = self._param_table()
         layouts = list(layouts)
@@ -175,12 +180,40 @@ class TilinGNN(Tracked, nn.Module):
             st.wait_stream(cur)
         dims = self._dims()
         xs, attrs, graphs, outs, wss = [], [], [], [], []
-        for k, (x, adj, attr, col) in enumerate(layouts):
-            n = int(x.shape[0])
+
+        def check_shapes(x, attr):
             if x.dim() != 2 or x.shape[1] != self.node_features_dim or attr.dim() != 2 or attr.shape[1] != self.adj_edge_features_dim:
                 raise ValueError("forward_many: layout shapes (see forward)")
-            if bn_train and n < 2:
+            if bn_train and int(x.shape[0]) < 2:
                 raise ValueError("Expected more than 1 value per channel when training")
+        ready = {}                                               # layout -> its graph, prepared on the current stream
+        if union and union_prep:
+            max_n, max_e = ops._small_prep_limits()
+            todo = []
+            for k, (x, adj, attr, col) in enumerate(layouts):
+                check_shapes(x, attr)
+                n = int(x.shape[0])
+                if n <= max_n and max(int(adj.shape[-1]), int(col.shape[-1])) <= max_e and \
+                        not (self.cache_graph and _graph_cache.peek_full(n, adj, attr, col) is not None):
+                    todo.append(k)
+            if todo:
+                made = ops.prepare_graphs_small([(int(layouts[k][0].shape[0]),) + tuple(layouts[k][1:4]) for k in todo])
+                for k, graph in zip(todo, made):
+                    if graph is not None:
+                        ready[k] = graph
+                        if self.cache_graph:
+                            _graph_cache.put_full(graph.n_nodes, *layouts[k][1:4], graph)
+                for st in used:                                  # (what the current stream just allocated and filled may be read on a lane)
+                    st.wait_stream(cur)
+        for k, (x, adj, attr, col) in enumerate(layouts):
+            n = int(x.shape[0])
+            check_shapes(x, attr)
+            if k in ready:
+                xf, ea, graph = ops._f32c(x, "x"), ops._f32c(attr, "adj_e_features"), ready[k]
+                ws = torch.empty(lib.tgnn_forward_workspace_bytes(C.byref(dims), n, graph.n_types), dtype=torch.uint8, device=dev)
+                probs = torch.empty(n, self.output_dim, dtype=torch.float32, device=dev)
+                xs.append(xf); attrs.append(ea); graphs.append(graph); outs.append(probs); wss.append(ws)
+                continue
             with torch.cuda.stream(lanes[k % streams]):          # preparation and buffers belong to the layout's stream
                 xf, ea = ops._f32c(x, "x"), ops._f32c(attr, "adj_e_features")
                 graph = _graph_cache.get_full(n, adj, attr, col) if self.cache_graph else ops.prepare_graph(n, adj, attr, col)

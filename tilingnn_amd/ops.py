@@ -414,6 +414,106 @@ def _prepare_graph_fused(n_nodes: int, adj: Tensor, attr: Tensor, col: Tensor, s
     return g
 
 
+def _pinned_many_words(dev, k: int) -> Tensor:
+    """This thread's pinned [k][32] result words of prepare_graphs_small (grow only; free again when the call returns)."""
+    import threading
+    key = (threading.get_ident(), dev.index, "many")
+    host = _pinned_words.get(key)
+    if host is None or host.numel() < 32 * k:
+        host = _pinned_words[key] = torch.empty(32 * max(2 * k, 16), dtype=torch.int32, pin_memory=True)
+    return host
+
+
+def _small_many_eligible(n_nodes: int, adj: Tensor, attr: Tensor, col: Tensor) -> bool:
+    """What ops.prepare_graph sends to tgnn_graph_prep_small (the one-launch preparation builds type columns)."""
+    max_n, max_e = _small_prep_limits()
+    return COLS_MIN_NODES == 0 and 1 <= n_nodes <= max_n and max(int(adj.shape[1]), int(col.shape[1])) <= max_e and \
+        attr.dim() == 2 and attr.shape[1] >= 1 and not (GROUPS and runs_general_schedule(n_nodes))
+
+
+def _prepare_graphs_small_queue(items):
+    """The binding below prepare_graphs_small: `items` = checked (n_nodes, adj, attr, col) of eligible layouts on one device.  One
+    allocation pass, ONE tgnn_graph_prep_small_many call, ONE wait.  -> (words: k lists of 32 ints, pieces: k tuples of the twelve
+    output tensors).  Nothing is raised for a layout's index errors: that is the caller's reading of words 1 / 2."""
+    k = len(items)
+    dev = items[0][1].device
+    table = (_lib.SmallPrepLayout * k)()
+    pieces, keep, tmp_at, at_all = [], [], [], 0
+    for n_nodes, adj, attr, col in items:                       # the scratch of all layouts: one tensor
+        tmp_at.append(at_all)
+        at_all += (int(lib.tgnn_graph_prep_small_tmp_ints(n_nodes, int(adj.shape[1]), int(col.shape[1]))) + 63) // 64 * 64
+    tmp = torch.empty(at_all, dtype=torch.int32, device=dev)
+    res = torch.empty(k, 32, dtype=torch.int32, device=dev)
+    for j, (n_nodes, adj, attr, col) in enumerate(items):
+        ea, ec = int(adj.shape[1]), int(col.shape[1])
+        ntiles = (n_nodes + 15) // 16
+        e1, c1 = max(ea, 1), max(ec, 1)
+        cap = int(lib.tgnn_nnconv_cols_max_columns(n_nodes, ea))
+        # a layout's persistent outputs share ONE long-lived allocation (as _prepare_graph_fused lays them out)
+        sizes = [n_nodes + 1, e1, e1, e1, e1, e1, n_nodes + 1, c1, c1, ntiles + 1, cap, cap * 16]
+        offs, at = [], 0
+        for sz in sizes:
+            offs.append(at)
+            at += (sz + 63) // 64 * 64
+        buf = torch.empty(at, dtype=torch.int32, device=dev)
+        v = tuple(buf[o:o + sz] for o, sz in zip(offs, sizes))
+        pieces.append(v)
+        keep.append((adj, attr, col))
+        table[j] = _lib.SmallPrepLayout(adj.data_ptr(), attr.data_ptr(), col.data_ptr(), ea, ec, n_nodes,
+                                        *[t.data_ptr() for t in v], tmp.data_ptr() + 4 * tmp_at[j], int(attr.shape[1]), 0)
+    host = _pinned_many_words(dev, k)
+    stream = _stream(items[0][1])
+    check(lib.tgnn_graph_prep_small_many(table, k, ptr(res), C.c_void_p(host.data_ptr()), stream))
+    check(lib.tgnn_graph_prep_small_many_wait(stream))          # the call's one synchronisation
+    words = host[:32 * k].view(k, 32).tolist()
+    return words, pieces
+
+
+def prepare_graphs_small(layouts):
+    """prepare_graph for K small layouts -- (n_nodes, adj_e_index, adj_e_features, col_e_idx) each -- as ONE library call: every
+    layout a team of blocks of one launch per ~240 blocks (tgnn_graph_prep_small_many), one copy of the K x 32 result words and one
+    host synchronisation for all of them.  Every graph is the one `prepare_graph` builds for the layout, bit for bit.
+    -> a list of K entries: the PreparedGraph, or None where the layout is not the one-launch preparation's (more than 4 096 nodes
+    or 131 072 edges in a set, a layout of the general schedule) or where it reports the fall-back (more than 1 024 distinct
+    attribute rows): the caller prepares that layout with `prepare_graph`.  An edge end out of range raises IndexError -- naming the
+    layout and the edge set -- after the read-back; the kernel skips such an edge, the other layouts are not affected."""
+    layouts = list(layouts)
+    out = [None] * len(layouts)
+    items, where = [], []
+    for j, (n_nodes, adj_e_index, adj_e_features, col_e_idx) in enumerate(layouts):
+        adj = _check_edge_index(adj_e_index, "adj_e_index")
+        col = _check_edge_index(col_e_idx, "col_e_idx")
+        if adj_e_features.shape[0] != int(adj.shape[1]):
+            raise ValueError(f"layout {j}: adj_e_features has {adj_e_features.shape[0]} rows for {int(adj.shape[1])} edges")
+        n_nodes = int(n_nodes)
+        if not _small_many_eligible(n_nodes, adj, adj_e_features, col):
+            continue
+        if items and adj.device != items[0][1].device:
+            raise ValueError("prepare_graphs_small: the layouts of a call live on one device")
+        items.append((n_nodes, adj, _f32c(adj_e_features, "adj_e_features"), col))
+        where.append(j)
+    if not items:
+        return out
+    words, pieces = _prepare_graphs_small_queue(items)
+    for j, host, item in zip(where, words, items):
+        if host[1] or host[2]:
+            raise IndexError(f"layout {j}: edge index out of range [0, {item[0]}) in {'adj_e_index' if host[1] else 'col_e_idx'}")
+    for j, host, item, v in zip(where, words, items, pieces):
+        out[j] = _small_graph_from_words(item, host, v)
+    return out
+
+
+def _small_graph_from_words(item, host, v) -> Optional[PreparedGraph]:
+    """The PreparedGraph of one layout of prepare_graphs_small from its result words and output tensors (None: fall back)."""
+    if host[6]:
+        return None
+    n_nodes, adj, _, col = item
+    a_rowptr, a_src, a_eid, adj_type, edge_type, rep, c_rowptr, c_src, c_eid, tile_col_ptr, col_meta, col_slot_src = v
+    cols = NNConvColumns(tile_col_ptr, col_meta, col_slot_src) if host[5] else None
+    return PreparedGraph(n_nodes, int(adj.shape[1]), int(host[3]), int(host[0]), a_rowptr, a_src, a_eid, adj_type, edge_type, rep,
+                         c_rowptr, c_src, c_eid, cols, int(host[4]), None, None)
+
+
 def prepare_graph(n_nodes: int, adj_e_index: Tensor, adj_e_features: Tensor, col_e_idx: Tensor,
                   tile_width: int = 32, n_src_nodes: Optional[int] = None, columns: Optional[bool] = None,
                   groups=None, after_enqueue=None) -> PreparedGraph:

@@ -59,6 +59,9 @@ class ML_Solver:
         # solve_many / solve_many_by_device_greedy: score every round's small sub-layouts inside ONE persistent kernel launch
         # (TilinGNN.forward_many(union=True), csrc/forward_small.hip); the same results either way
         self.union_forward = False
+        # ... and, with union_forward, prepare their graphs by ONE library call and one read-back per round instead of one of each per
+        # sub-layout (TilinGNN.forward_many(union=True, union_prep=True), csrc/graph_prep.hip); the same graphs either way
+        self.union_prep = False
 
     @staticmethod
     def _no_edges(index) -> bool:
@@ -149,7 +152,8 @@ class ML_Solver:
         probabilities (the first round's sub-layout IS the layout: what `self.predict(layout)` returns, without K more forwards).
         In train mode the BatchNorm running statistics are left untouched (see `TilinGNN.forward_many`).
         `self.union_forward = True`: every round's small sub-layouts are scored inside one persistent kernel launch
-        (`TilinGNN.forward_many(union=True)`): the same results, fewer launches per round."""
+        (`TilinGNN.forward_many(union=True)`): the same results, fewer launches per round.  `self.union_prep = True` beside it: the
+        sub-layouts' graphs come from one library call and one read-back per round (`forward_many(..., union_prep=True)`)."""
         from ...util.algorithms import solve_many_by_device_greedy
         brick_layouts = list(brick_layouts)
         if not brick_layouts:

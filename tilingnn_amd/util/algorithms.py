@@ -298,12 +298,14 @@ class PackedLayouts:
                             None if inverse is None else inverse[n0:n0 + n])
 
 
-def _forward_many_checked(network, subs, streams, union=False):
+def _forward_many_checked(network, subs, streams, union=False, union_prep=False):
     """`forward_many` + what `forward_checked` adds to a forward, ONCE for all layouts: a stale-result status of an earlier
     unchecked forward is answered by queueing the forwards again; the health word of the persistent kernels is polled (this
     synchronises the current stream) and, if set, the forwards are repeated on the general launch schedule."""
     args = [(s.node_feature, s.align_edge_index, s.align_edge_features, s.collide_edge_index) for s in subs]
     kw = {"union": True} if union else {}                       # (union: after a starved kernel the fall-back window keeps every layout out of it)
+    if union and union_prep:
+        kw["union_prep"] = True                                 # (the sub-layouts' graphs from one library call: forward_many)
     try:
         outs = network.forward_many(args, streams=streams, **kw)
     except _lib.TgnnError as exc:
@@ -337,7 +339,8 @@ def solve_many_by_device_greedy(ml_solver, layouts, seed=0, seeds=None, score_fn
     `.last_first_probs` = the first round's probabilities per layout ([n_k] float32 on the device: what predict_on_device
     gives for the whole layout).  `ml_solver.union_forward = True` (an attribute like `device_greedy_seed`, default False): every
     round's small sub-layouts are scored inside one persistent kernel launch (`forward_many(union=True)`) -- the same bits, fewer
-    launches."""
+    launches.  `ml_solver.union_prep = True` beside it: their graphs are prepared by one library call and one read-back per round
+    (`forward_many(union=True, union_prep=True)`) -- the same graphs."""
     device = ml_solver.device
     originals = None if isinstance(layouts, PackedLayouts) else list(layouts)
     solve_many_by_device_greedy.last_rounds = []
@@ -391,6 +394,7 @@ def solve_many_by_device_greedy(ml_solver, layouts, seed=0, seeds=None, score_fn
     meta.copy_(meta_h, non_blocking=True)
     network = ml_solver.network
     union_forward = bool(getattr(ml_solver, "union_forward", False))
+    union_prep = bool(getattr(ml_solver, "union_prep", False))
     rnd = 0
 
     def raise_errors(words):
@@ -439,7 +443,7 @@ def solve_many_by_device_greedy(ml_solver, layouts, seed=0, seeds=None, score_fn
         if need_net:
             views = [subs[k] for k in need_net]
             if hasattr(network, "forward_many"):
-                outs = _forward_many_checked(network, views, streams, union_forward)
+                outs = _forward_many_checked(network, views, streams, union_forward, union_prep)
             else:
                 outs = [ml_solver.predict_on_device(v).reshape(-1, 1) for v in views]
             for k, sub, out in zip(need_net, views, outs):
