@@ -1053,6 +1053,25 @@ int tgnn_union_area(const double *ring_xy, const int32_t *ring_ptr, int64_t n_ti
                     const int32_t *col_idx, const int32_t *alive, int64_t n_masks, double tol, double *area_out,
                     int32_t *err_flag, void *ws, size_t ws_bytes, tgnn_stream_t stream);
 
+/* ---- the disjoint union of B layouts of a packed set (csrc/batch_union.hip): what PyG's DataLoader hands the reference's training
+ * step for batch_size B (Batch.from_data_list: arrays concatenated, edge ends shifted by the member's node offset).  ONE launch,
+ * no host synchronisation, no atomics: the same bits on every call.
+ *   the packed set (device): x [sum N][fx]; adj / col flat int64, layout k's index its own [2][E_k] block at element
+ *   2 * adj_ptr[k] (2 * col_ptr[k]) in the layout's LOCAL numbering; attr [sum Ea][fe]; node_ptr / adj_ptr / col_ptr [K + 1] on the
+ *   device and the same tables on the host (`*_host`: what the arguments are checked against).
+ *   table [4 B + 3] int64 = ids [B] | node_off [B + 1] | adj_off [B + 1] | col_off [B + 1]: the members (a gather: any order,
+ *   repeats allowed) and where each starts in the outputs, computed by the caller from the host tables and copied to the device
+ *   ONCE (`table`; `table_host` = the same words on the host).  An id outside [0, K), a table that does not start at 0 or a member
+ *   whose span differs from its layout's size is TGNN_ERR_INVALID_ARG before anything is queued.
+ *   x_out [N_b][fx], attr_out [Ea_b][fe], adj_out [2][Ea_b], col_out [2][Ec_b] (row 0 and row 1 each contiguous over the whole
+ *   batch), N_b = node_off[B] etc.; an array of a kind the batch has nothing of may be NULL.  Edge ends are trusted (shifted, not
+ *   range-checked: the graph preparation checks them). */
+int tgnn_batch_union(const float *x, const int64_t *adj, const float *attr, const int64_t *col, const int64_t *node_ptr,
+                     const int64_t *adj_ptr, const int64_t *col_ptr, const int64_t *node_ptr_host, const int64_t *adj_ptr_host,
+                     const int64_t *col_ptr_host, int32_t n_layouts, int32_t fx, int32_t fe, const int64_t *table_host,
+                     const int64_t *table, int32_t batch, float *x_out, float *attr_out, int64_t *adj_out, int64_t *col_out,
+                     tgnn_stream_t stream);
+
 int tgnn_rows_gather(const float *src, int64_t ld_src, const int32_t *idx, int64_t n_idx, int32_t c,
                      float *out, int64_t ld_out, tgnn_stream_t stream);
 int tgnn_rows_scatter(const float *in, const int32_t *idx, int64_t n_idx, int32_t c, float *dst,

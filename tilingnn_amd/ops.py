@@ -813,3 +813,50 @@ def bn_stat_from_sums(sums: Tensor, n_rows_total: int, bn: torch.nn.BatchNorm1d,
                                ptr(bn.running_mean if upd else None), ptr(bn.running_var if upd else None),
                                ptr(bn.num_batches_tracked if upd else None), ptr(stat), _stream(sums)))
     return stat
+
+
+# ----------------------------------------------------------------------------------------------
+# mini-batches: the disjoint union of B layouts of a packed set
+# ----------------------------------------------------------------------------------------------
+def batch_union(packed, ids, _offsets=None):
+    """The disjoint union of the layouts `ids` of `packed` (a util.algorithms.PackedLayouts) as ONE DeviceLayout -- what PyG's
+    DataLoader makes of B layouts (Batch.from_data_list): node features, adjacency attributes and both edge indices
+    concatenated in the order of `ids`, every edge end shifted by its member's node offset.  `ids` is a gather: any order,
+    repeats allowed.  One copy of the id / offset table to the device, one launch (csrc/batch_union.hip), no synchronisation;
+    the outputs are new tensors.  `_offsets` (tests): (node_off, adj_off, col_off) instead of the ones computed here."""
+    from .util.algorithms import DeviceLayout
+    ids = [int(i) for i in ids]
+    b = len(ids)
+    if b == 0:
+        raise ValueError("batch_union needs at least one layout id")
+    dev = packed.device
+    if dev.type != "cuda":
+        raise RuntimeError("tilingnn_amd has no CPU path: batch_union runs on the GPU the packed layouts live on")
+    host = packed.ptr_tables_c()
+    if _offsets is None:
+        offs = []
+        for p in (packed.node_ptr_h, packed.adj_ptr_h, packed.col_ptr_h):
+            off = [0]
+            for i in ids:                                       # (an id out of range is the library's to report: size 0 here)
+                off.append(off[-1] + (p[i + 1] - p[i] if 0 <= i < packed.k else 0))
+            offs.append(off)
+    else:
+        offs = [[int(v) for v in o] for o in _offsets]
+        if any(len(o) != b + 1 for o in offs) or len(offs) != 3:
+            raise ValueError("three offset tables of len(ids) + 1 entries")
+    # (pinned, and dropped right after a non-blocking copy: torch's caching host allocator records the copy's stream event on the
+    #  block and does not hand it out again before that event has passed)
+    table_h = torch.tensor(ids + offs[0] + offs[1] + offs[2], dtype=torch.int64).pin_memory()
+    n, ea, ec = (max(int(o[-1]), 0) for o in offs)
+    fx, fe = int(packed.fx), int(packed.fe)
+    with torch.cuda.device(dev):
+        table = table_h.to(dev, non_blocking=True)              # the ONE host-to-device copy of the batch
+        x_out = torch.empty(n, fx, dtype=torch.float32, device=dev)
+        attr_out = torch.empty(ea, fe, dtype=torch.float32, device=dev)
+        adj_out = torch.empty(2, ea, dtype=torch.int64, device=dev)
+        col_out = torch.empty(2, ec, dtype=torch.int64, device=dev)
+        check(lib.tgnn_batch_union(ptr(packed.x), ptr(packed.adj), ptr(packed.attr), ptr(packed.col), ptr(packed.node_ptr),
+                                   ptr(packed.adj_ptr), ptr(packed.col_ptr), host[0], host[1], host[2], packed.k, fx, fe,
+                                   C.c_void_p(table_h.data_ptr()), ptr(table), b, ptr(x_out), ptr(attr_out), ptr(adj_out),
+                                   ptr(col_out), _lib.current_stream(dev)))
+    return DeviceLayout(x_out, adj_out, attr_out, col_out)

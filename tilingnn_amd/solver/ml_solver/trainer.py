@@ -13,9 +13,12 @@ Here: the same loop with
     steps), the loss and its gradient on the GPU (solver/ml_solver/losses.py),
   * the caller's optimizer untouched (`optimizer.step()` on the `.grad`s, as in network_train.py).
 `create_data` (trainer.py:39-50, :126-165) judges its random target shapes on the GPU (csrc/region.hip) instead of with
-shapely in a 16-process pool.  Not mirrored: the per-checkpoint debug plots (`ml_solver.save_debug_info`, trainer.py:113-121).  batch_size must be 1, the only
-value the reference configures; a larger one would need PyG's disjoint-union batching.
+shapely in a 16-process pool.  Not mirrored: the per-checkpoint debug plots (`ml_solver.save_debug_info`, trainer.py:113-121).  `train` takes batch_size 1, the only
+value the reference configures; mini-batches -- PyG's disjoint-union batching, the `batch_size` of the reference's signature
+(trainer.py:55, :60) -- are `train_batches`: per step the union of B layouts is written by one launch (`ops.batch_union`,
+csrc/batch_union.hip) and goes through the same `train_step`.
 """
+import contextlib
 import glob
 import os
 import traceback
@@ -23,8 +26,9 @@ import traceback
 import numpy as np
 import torch
 
+from ... import ops
 from ...util import data_util
-from ...util.algorithms import DeviceLayout
+from ...util.algorithms import DeviceLayout, PackedLayouts
 from .losses import Losses
 
 
@@ -33,6 +37,8 @@ class LayoutDataset:
 
     def __init__(self, root, device):
         self.files = sorted(glob.glob(os.path.join(root, "raw", "*.pkl")))
+        self.device = device
+        self._packed = None
         self.layouts = []
         for f in self.files:
             _, x, col_idx, col_feat, adj_idx, adj_feat, *_ = data_util.load_brick_layout_data(f)
@@ -47,6 +53,14 @@ class LayoutDataset:
 
     def __getitem__(self, i):
         return self.layouts[i]
+
+    @property
+    def packed(self):
+        """The resident layouts as one `PackedLayouts` (built on first use: a second copy of the arrays, concatenated): what
+        `ops.batch_union` gathers mini-batches from."""
+        if self._packed is None:
+            self._packed = PackedLayouts(self.layouts, self.device)
+        return self._packed
 
 
 class _Arrays:
@@ -69,6 +83,53 @@ def cal_avg_loss(network, layouts):
                 loss, _, _ = Losses.calculate_unsupervised_loss(probs, lay.node_feature, lay.collide_edge_index,
                                                                 lay.align_edge_index, lay.align_edge_features)
             losses.append(float(loss))
+    finally:
+        network.autograd = was
+    return float(np.mean(losses)) if losses else float("nan")
+
+
+def batch_chunks(order, batch_size):
+    """DataLoader(batch_size=B, drop_last=False) over an index order: consecutive chunks of B, the short last one kept."""
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError("batch_size must be at least 1")
+    order = [int(i) for i in order]
+    return [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
+
+
+def _union_is_trainable(packed, ids):
+    """What `train_step` needs of a batch, from the host tables: 2 nodes (BatchNorm), both edge sets non-empty."""
+    size = lambda p: sum(p[i + 1] - p[i] for i in ids)
+    return size(packed.node_ptr_h) >= 2 and size(packed.adj_ptr_h) > 0 and size(packed.col_ptr_h) > 0
+
+
+@contextlib.contextmanager
+def _graph_cache_bypassed(network):
+    """A union is a new graph every step: prepared beside the cache, so that an epoch of them does not evict the per-layout
+    graphs `LayoutDataset` reserved room for (and the cache does not pin B layouts' worth of arrays per step)."""
+    was = network.cache_graph
+    network.cache_graph = False
+    try:
+        yield
+    finally:
+        network.cache_graph = was
+
+
+def cal_avg_loss_batches(network, packed, chunks):
+    """`cal_avg_loss` over disjoint-union batches (the reference evaluates `loader_train`, whose batches are unions)."""
+    losses = []
+    was = network.autograd
+    network.autograd = False
+    try:
+        with _graph_cache_bypassed(network), torch.no_grad():
+            for ids in chunks:
+                if not _union_is_trainable(packed, ids):
+                    continue
+                lay = ops.batch_union(packed, ids)
+                probs, _ = network(lay.node_feature, lay.align_edge_index, lay.align_edge_features, lay.collide_edge_index)
+                loss, _, _ = Losses.calculate_unsupervised_loss(probs, lay.node_feature, lay.collide_edge_index,
+                                                                lay.align_edge_index, lay.align_edge_features)
+                losses.append(float(loss))
     finally:
         network.autograd = was
     return float(np.mean(losses)) if losses else float("nan")
@@ -178,6 +239,61 @@ class Trainer:
             finally:
                 self.network.autograd = False
             loss_train = cal_avg_loss(self.network, train_set)
+            log(f"epoch {epoch}: training loss: {loss_train}")
+            loss_test = cal_avg_loss(self.network, test_set)
+            log(f"epoch {epoch}: testing loss: {loss_test}")
+            history.append((loss_train, loss_test))
+            if loss_test < min_test_loss or epoch % save_model_per_epoch == 0:      # trainer.py:96-108
+                min_test_loss = min(min_test_loss, loss_test)
+                model_file = os.path.join(self.model_save_path, f"model_{epoch}_{loss_test}.pth")
+                torch.save(self.network.state_dict(), model_file)
+                torch.save(optimizer.state_dict(), os.path.join(self.model_save_path, f"optimizer_{epoch}_{loss_test}.pth"))
+                log(f"model saved at epoch {epoch}")
+                if ml_solver is not None:
+                    ml_solver.load_saved_network(model_file)
+        log("Training Done!!!")
+        return history
+
+    def train_batch_step(self, packed, ids, optimizer):
+        """One mini-batch step: the disjoint union of the layouts `ids` of `packed` (one launch, `ops.batch_union`) through
+        `train_step` -- BatchNorm statistics over all rows of the union, one loss, one optimizer step, as the reference's loop
+        body on a PyG batch.  `network.autograd` must be on (as for `train_step`).  Returns the loss, or None for a batch
+        `train_step` cannot run (fewer than 2 nodes, or an edge set empty over the whole batch)."""
+        if not _union_is_trainable(packed, ids):
+            return None
+        with _graph_cache_bypassed(self.network):
+            return self.train_step(ops.batch_union(packed, ids), optimizer)
+
+    def train_batches(self, ml_solver, optimizer, batch_size=32, training_epoch=10000, save_model_per_epoch=5,
+                      shuffle_seed=None, log=print):
+        """The loop of `train` on mini-batches (the reference's `train` with its `batch_size`, trainer.py:52-124): every epoch's
+        permutation is cut into consecutive chunks of `batch_size` (the short last one kept: DataLoader's drop_last=False) and
+        every chunk is one `train_batch_step`.  After the epoch the training loss is the mean over the batches of the training
+        split (in file order, same `batch_size`: the reference evaluates `loader_train`), the test loss the mean over single
+        layouts (`loader_test` has batch_size 1); checkpoints as in `train`."""
+        if int(batch_size) < 1:
+            raise ValueError("batch_size must be at least 1")
+        chunks_of = lambda order: batch_chunks(order, batch_size)
+        train_set = LayoutDataset(self.training_path, self.device)
+        test_set = LayoutDataset(self.testing_path, self.device)
+        packed = train_set.packed
+        eval_chunks = chunks_of(range(len(train_set)))
+        rng = np.random.default_rng(shuffle_seed)
+        log("Training Start!!!")
+        min_test_loss = float("inf")
+        history = []
+        for epoch in range(training_epoch):
+            self.network.train()
+            self.network.autograd = True
+            try:
+                for ids in chunks_of(rng.permutation(len(train_set))):   # DataLoader(batch_size, shuffle=True), trainer.py:60
+                    try:
+                        self.train_batch_step(packed, ids, optimizer)
+                    except Exception:                                    # trainer.py:85-87: report and go on
+                        log(traceback.format_exc())
+            finally:
+                self.network.autograd = False
+            loss_train = cal_avg_loss_batches(self.network, packed, eval_chunks)
             log(f"epoch {epoch}: training loss: {loss_train}")
             loss_test = cal_avg_loss(self.network, test_set)
             log(f"epoch {epoch}: testing loss: {loss_test}")

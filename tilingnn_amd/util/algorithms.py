@@ -287,6 +287,15 @@ class PackedLayouts:
     def nodes(self, k: int) -> int:
         return self.node_ptr_h[k + 1] - self.node_ptr_h[k]
 
+    def ptr_tables_c(self):
+        """(node_ptr, adj_ptr, col_ptr) [K + 1] as C int64 arrays on the host, built once: what `tgnn_batch_union` checks its
+        arguments against (ops.batch_union)."""
+        tables = getattr(self, "_ptr_tables_c", None)
+        if tables is None:
+            tables = self._ptr_tables_c = tuple((C.c_int64 * (self.k + 1))(*p) for p in
+                                                (self.node_ptr_h, self.adj_ptr_h, self.col_ptr_h))
+        return tables
+
     def layout(self, k: int) -> DeviceLayout:
         """Layout k as a view of the packed arrays."""
         return self.view(k, self.x, self.adj, self.attr, self.col, *(p[k + 1] - p[k] for p in (self.node_ptr_h, self.adj_ptr_h, self.col_ptr_h)))
