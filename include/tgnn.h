@@ -866,6 +866,26 @@ int tgnn_solution_score_sums_many(int32_t n_layouts, const int32_t *active, cons
                                   int64_t ld_area, const float *perimeter, const int64_t *adj_edge_index, const float *adj_edge_len,
                                   int64_t ld_len, double *sums, void *ws, size_t ws_bytes, tgnn_stream_t stream);
 
+/* tgnn_unsupervised_loss for K layouts on packed arrays (see tgnn_sublayout_compact_many; the offset tables hold absolute
+ * offsets, so node_ptr + k0 works on a contiguous group of a larger packed set).  counts (may be NULL): device int64 [K][3] =
+ * {N'_k, Ea'_k, Ec'_k}, the compacted sub-layouts tgnn_sublayout_compact_many left at the layouts' offsets (index rows E'_k
+ * apart).  probs: DEVICE table of K device pointers, probs[k] = layout k's [n_k, ld_probs] probabilities (what forward_many
+ * returned).  losses (device double [K][n_maps]) and terms (device double [K][n_maps][3], may be NULL): per layout and map the
+ * bits of the single-layout call -- same element expressions, same number of blocks per layout, same strides, same reduction.
+ * A layout with active[k] == 0 or without nodes gets nothing written (the caller pre-fills its rows).  err (device int32 [K],
+ * cleared by the call): 1 for a layout with an offset, a count or an edge end out of range or a NULL probs entry; its loss and
+ * term rows are NaN, nothing is read or written out of range, no other layout is affected.  Four queue entries whatever K:
+ * the err memset, a plan launch, a partial launch over (blocks of all layouts, n_maps), a final launch; no host
+ * synchronisation. */
+size_t tgnn_unsupervised_loss_many_workspace_bytes(int32_t n_layouts, int32_t n_maps);
+int tgnn_unsupervised_loss_many(int32_t n_layouts, const int32_t *active, const int64_t *node_ptr, const int64_t *adj_ptr,
+                                const int64_t *col_ptr, int64_t total_nodes, int64_t total_adj_edges, int64_t total_col_edges,
+                                const int64_t *counts, const float *const *probs, int64_t ld_probs, int32_t n_maps,
+                                const float *area_ratio, int64_t ld_area, const int64_t *adj_edge_index,
+                                const float *adj_edge_len, int64_t ld_len, const int64_t *col_edge_index, float collision_weight,
+                                float align_length_weight, float avg_area_weight, double *losses, double *terms, int32_t *err,
+                                void *ws, size_t ws_bytes, tgnn_stream_t stream);
+
 /* ---- the training step: adjoints of the forward kernels ---------------------------------
  * Trainer.train (solver/ml_solver/trainer.py:68-84) = forward in train mode, the unsupervised loss, loss.backward(),
  * optimizer.step().  torch.autograd derives the backward there; these are the same adjoints per forward kernel

@@ -160,6 +160,9 @@ def _load() -> C.CDLL:
         "tgnn_greedy_finish_many": (C.c_int, [i32, p, p, p, i64, i64, p, p, p, i32, i32, p, p, p, p, p, p, p, p]),
         "tgnn_solution_score_sums_many_workspace_bytes": (sz, [i32]),
         "tgnn_solution_score_sums_many": (C.c_int, [i32, p, p, p, i64, i64, p, p, i64, p, p, p, i64, p, p, sz, p]),
+        "tgnn_unsupervised_loss_many_workspace_bytes": (sz, [i32, i32]),
+        "tgnn_unsupervised_loss_many": (C.c_int, [i32, p, p, p, p, i64, i64, i64, p, p, i64, i32, p, i64, p, p, i64, p, f32, f32, f32,
+                                                  p, p, p, p, sz, p]),
         "tgnn_unsupervised_loss_workspace_bytes": (sz, [i32]),
         "tgnn_unsupervised_loss": (C.c_int, [p, i64, i32, p, i64, i64, p, i64, p, i64, p, i64, f32, f32, f32, p, p, p, sz, p]),
         "tgnn_solution_score_sums": (C.c_int, [p, p, i64, p, i64, p, i64, p, i64, p, p, sz, p]),
@@ -277,6 +280,7 @@ EXPORTED_SYMBOLS = (
     "tgnn_sublayout_workspace_bytes", "tgnn_sublayout_compact", "tgnn_greedy_round_workspace_bytes", "tgnn_greedy_round", "tgnn_greedy_finish_max_nodes", "tgnn_greedy_finish", "tgnn_shard_alive_rows",
     "tgnn_sublayout_compact_many_workspace_bytes", "tgnn_sublayout_compact_many", "tgnn_greedy_round_many_workspace_bytes", "tgnn_greedy_round_many",
     "tgnn_greedy_finish_many", "tgnn_solution_score_sums_many_workspace_bytes", "tgnn_solution_score_sums_many",
+    "tgnn_unsupervised_loss_many_workspace_bytes", "tgnn_unsupervised_loss_many",
     "tgnn_tiles_in_region", "tgnn_region_edge_counts", "tgnn_union_area_workspace_bytes", "tgnn_union_area", "tgnn_batch_union",
     "tgnn_transpose", "tgnn_swap_leading", "tgnn_gin_aggregate", "tgnn_sigmoid_bwd", "tgnn_add_into", "tgnn_reduce_workspace_bytes", "tgnn_colsum",
     "tgnn_bn_bwd_reduce", "tgnn_bn_bwd_apply", "tgnn_merge_bwd_reduce", "tgnn_wgrad_workspace_bytes", "tgnn_wgrad", "tgnn_wgrad_slots",

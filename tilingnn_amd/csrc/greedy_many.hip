@@ -1,6 +1,8 @@
 // K independent greedy solves in ONE loop (tilingnn_amd.util.algorithms.solve_many_by_device_greedy): the bookkeeping of a round --
 // sub-layout compaction (graph_prep.hip: tgnn_sublayout_compact), batched acceptance and the one-launch finish (greedy.hip), the
-// sums of the solution score (loss.hip: tgnn_solution_score_sums) -- for K layouts per launch instead of per layout.
+// sums of the solution score (loss.hip: tgnn_solution_score_sums) -- for K layouts per launch instead of per layout; and the
+// unsupervised loss (loss.hip: tgnn_unsupervised_loss) of K layouts per call, for the best-map pick of a round and for the
+// evaluation of a split (solver/ml_solver/trainer.py: cal_avg_loss_many).
 //
 // Reference: the crop loop of /root/reference/Tiling-Shape.py:60-64 calls solver.solve(layout) once per crop; the layouts have
 // nothing to do with each other.
@@ -38,19 +40,44 @@ struct ManyDesc {
 };
 
 // full size of set `s` of layout k, 0 (and bad = true) when the offset table is not 0 <= ptr[k] <= ptr[k + 1] <= total
-__device__ __forceinline__ int64_t many_full_size(const ManyDesc &d, int s, int k, bool &bad) {
+__host__ __device__ __forceinline__ int64_t many_full_size(const ManyDesc &d, int s, int k, bool &bad) {
     const int64_t a = d.ptr[s][k], b = d.ptr[s][k + 1];
     if (a < 0 || b < a || b > d.total[s] || b - a >= (1ll << 31) - 1) { bad = true; return 0; }
     return b - a;
 }
 // the size this call works on: 0 for an inactive layout; the sub-layout count (checked against the full size) when counts are given
-__device__ __forceinline__ int64_t many_size(const ManyDesc &d, int s, int k, bool &bad) {
+__host__ __device__ __forceinline__ int64_t many_size(const ManyDesc &d, int s, int k, bool &bad) {
     if (d.active && d.active[k] == 0) return 0;
     const int64_t full = many_full_size(d, s, k, bad);
     if (!d.counts) return full;
     const int64_t c = d.counts[(int64_t)k * 3 + s];
     if (c < 0 || c > full) { bad = true; return 0; }
     return c;
+}
+
+// ---- the unsupervised loss of K layouts (loss.hip per layout): what a layout contributes, where its arrays start.  Host and
+// device: scratch/loss_many_host_check.cpp walks these on random offset tables under AddressSanitizer.
+struct LossManyView {
+    int64_t n, ec, ea;                                      // sizes this call works on (the sub-layout's with counts)
+    int64_t np, ap, cp;                                     // first node / adjacency edge / collision edge in the packed arrays
+};
+// false: nothing to compute -- inactive or without nodes (bad stays false), or an offset / count out of range (bad = true).
+// Every offset is checked against the packed sizes before it is returned.
+__host__ __device__ __forceinline__ bool loss_many_view(const ManyDesc &d, int k, LossManyView &v, bool &bad) {
+    bad = false;
+    v.n = many_size(d, 0, k, bad);
+    v.ea = many_size(d, 1, k, bad);
+    v.ec = many_size(d, 2, k, bad);
+    if (bad || v.n == 0) return false;
+    v.np = d.ptr[0][k]; v.ap = d.ptr[1][k]; v.cp = d.ptr[2][k];
+    return true;
+}
+// loss.hip: loss_blocks(n, ec, ea)
+__host__ __device__ __forceinline__ int loss_many_blocks(int64_t n, int64_t ec, int64_t ea) {
+    int64_t work = n > ec ? n : ec;
+    if (ea > work) work = ea;
+    int64_t b = (work + kChunk - 1) / kChunk;
+    return (int)(b < 1 ? 1 : (b > 512 ? 512 : b));
 }
 
 // exclusive scan of one int per thread over the block (kMnThreads = 4 wavefronts); sh: >= 4 ints of LDS
@@ -72,7 +99,8 @@ __device__ __forceinline__ int block_excl_scan(int v, int *sh, int &total) {
 }
 
 // start[s * (K + 1) + k] = number of blocks of set s in front of layout k (start[..K] = all of them).  mode 0: chunks of kChunk
-// items; mode 1 (set 0 only): the block count of the score sums, loss.hip: loss_blocks(n, 0, ea).
+// items; mode 1 (set 0 only): the block count of the score sums, loss.hip: loss_blocks(n, 0, ea); mode 2 (set 0 only): the block
+// count of the unsupervised loss, loss_blocks(n, ec, ea) over the sizes this call works on (0 for a layout without nodes).
 __global__ __launch_bounds__(kMnThreads) void many_plan_kernel(ManyDesc d, int n_sets, int mode, int *__restrict__ start,
                                                                int *__restrict__ err) {
     __shared__ int sh[4];
@@ -86,6 +114,9 @@ __global__ __launch_bounds__(kMnThreads) void many_plan_kernel(ManyDesc d, int n
                 bool bad = false;
                 if (mode == 0) {
                     blocks = (int)((many_size(d, s, k, bad) + kChunk - 1) / kChunk);
+                } else if (mode == 2) {
+                    LossManyView v;
+                    blocks = loss_many_view(d, k, v, bad) ? loss_many_blocks(v.n, v.ec, v.ea) : 0;
                 } else if (!(d.active && d.active[k] == 0)) {
                     const int64_t n = many_full_size(d, 0, k, bad), ea = many_full_size(d, 1, k, bad);
                     int64_t b = ((n > ea ? n : ea) + kChunk - 1) / kChunk;
@@ -486,6 +517,114 @@ __global__ __launch_bounds__(64) void score_many_final_kernel(int K, const int32
     if (lane < 3) sums[(int64_t)k * 3 + lane] = err[k] ? __longlong_as_double(0x7ff8000000000000ll) : s[lane];
 }
 
+// ------------------------------------------------------------------------------------------ unsupervised loss (loss.hip, per layout)
+constexpr float kLossManyEps = 1e-7f;                       // loss.hip: kLossEps
+struct LossManyArgs {
+    const float *const *probs;                              // [K] device pointers: layout k's [n_k, ldp]
+    int64_t ldp;
+    int n_maps;
+    const float *area;
+    int64_t lda;
+    const int64_t *adj;
+    const float *len;
+    int64_t ldl;
+    const int64_t *col;
+    float wc, wl, wa;
+    double *losses, *terms;
+    int32_t *err;
+    const int *start;                                       // workspace
+    double *partial;                                        // [K][n_maps][512][3]
+};
+
+// what thread t0 of a grid of `stride` threads adds up: loss_partial_kernel's three loops on one layout's arrays (p: the map's
+// column, area / col / adj / len: the layout's own blocks).  An edge end outside [0, n) is skipped and reported.
+__host__ __device__ __forceinline__ void loss_many_accumulate(const LossManyView &v, const float *p, int64_t ldp, const float *area,
+                                                              int64_t lda, const int64_t *col, const int64_t *adj, const float *len,
+                                                              int64_t ldl, int64_t t0, int64_t stride, double &s_area, double &s_feas,
+                                                              double &s_align, bool &bad) {
+    const int64_t n = v.n, ec = v.ec, ea = v.ea;
+    for (int64_t i = t0; i < n; i += stride) s_area += (double)(area[i * lda] * p[i * ldp]);
+    for (int64_t e = t0; e < ec; e += stride) {
+        const int64_t i = col[e], j = col[ec + e];
+        if (i < 0 || i >= n || j < 0 || j >= n) { bad = true; continue; }
+        float pp = p[i * ldp] * p[j * ldp];
+        pp = fminf(fmaxf(pp, kLossManyEps), 1.0f - kLossManyEps);
+        s_feas += (double)logf(1.0f - pp);
+    }
+    for (int64_t e = t0; e < ea; e += stride) {
+        const int64_t i = adj[e], j = adj[ea + e];
+        if (i < 0 || i >= n || j < 0 || j >= n) { bad = true; continue; }
+        float pp = p[i * ldp] * p[j * ldp] * len[e * ldl];
+        pp = fmaxf(pp, kLossManyEps);
+        s_align += (double)(logf(pp) / 2.302585092994046f);
+    }
+}
+
+// grid = (upper bound of blocks over all layouts, maps); partial[((k * n_maps + m) * 512 + block of the layout) * 3 + {0,1,2}]
+__global__ __launch_bounds__(kMnThreads) void loss_many_partial_kernel(ManyDesc d, LossManyArgs a) {
+    int k, bl;
+    if (!many_find(a.start, d.K, blockIdx.x, k, bl)) return;
+    const int nb = a.start[k + 1] - a.start[k], m = blockIdx.y;
+    LossManyView v;
+    bool bad;
+    if (!loss_many_view(d, k, v, bad) || bl >= kScoreMaxBlocks) return;      // (the plan gives such a layout no block)
+    const float *p = a.probs[k];
+    if (!p) {                                               // (uniform over the block)
+        if (threadIdx.x == 0) a.err[k] = 1;
+        return;
+    }
+    double s_area = 0.0, s_feas = 0.0, s_align = 0.0;
+    loss_many_accumulate(v, p + m, a.ldp, a.area + v.np * a.lda, a.lda, a.col + 2 * v.cp, a.adj + 2 * v.ap, a.len + v.ap * a.ldl, a.ldl,
+                         (int64_t)bl * kMnThreads + threadIdx.x, (int64_t)nb * kMnThreads, s_area, s_feas, s_align, bad);
+    if (bad) a.err[k] = 1;
+    __shared__ double red[3][kMnThreads];
+    red[0][threadIdx.x] = s_area; red[1][threadIdx.x] = s_feas; red[2][threadIdx.x] = s_align;
+    __syncthreads();
+    for (int s = kMnThreads / 2; s >= 1; s >>= 1) {
+        if ((int)threadIdx.x < s)
+            for (int c = 0; c < 3; ++c) red[c][threadIdx.x] += red[c][threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x < 3)
+        a.partial[(((int64_t)k * a.n_maps + m) * kScoreMaxBlocks + bl) * 3 + threadIdx.x] = red[threadIdx.x][0];
+}
+
+// one wavefront per (layout, map): loss_final_kernel on the layout's partial rows
+__global__ __launch_bounds__(64) void loss_many_final_kernel(ManyDesc d, LossManyArgs a) {
+    const int k = blockIdx.x, m = blockIdx.y, lane = threadIdx.x;
+    LossManyView v;
+    bool bad;
+    const bool live = loss_many_view(d, k, v, bad);
+    if (!live && !bad) return;                              // inactive or without nodes: the caller's rows stay
+    const int64_t row = (int64_t)k * a.n_maps + m;
+    if (bad || a.err[k]) {                                  // NaN = "offset, count or edge index out of range"
+        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        if (lane == 0) {
+            if (bad) a.err[k] = 1;
+            a.losses[row] = nan;
+            if (a.terms) { a.terms[row * 3] = nan; a.terms[row * 3 + 1] = nan; a.terms[row * 3 + 2] = nan; }
+        }
+        return;
+    }
+    const int n_blocks = a.start[k + 1] - a.start[k];
+    const double *partial = a.partial + row * kScoreMaxBlocks * 3;
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int b = lane; b < n_blocks; b += 64)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s[c] += partial[(int64_t)b * 3 + c];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int t = 32; t >= 1; t >>= 1) s[c] += __shfl_xor(s[c], t, 64);
+    if (lane == 0) {
+        const double t0 = log(fmax(s[0] / (double)v.n, (double)kLossManyEps));
+        const double t1 = v.ec > 0 ? s[1] / (double)v.ec : 0.0;
+        const double t2 = v.ea > 0 ? s[2] / (double)v.ea : 0.0;
+        if (a.terms) { a.terms[row * 3] = t0; a.terms[row * 3 + 1] = t1; a.terms[row * 3 + 2] = t2; }
+        a.losses[row] = (1.0 - (double)a.wa * t0) * (1.0 - (double)a.wc * t1) * (1.0 - (double)a.wl * t2);
+    }
+}
+
 static int many_blocks_ub(int64_t total, int64_t k) { return (int)(total / kChunk + k); }
 
 }  // namespace tgnn
@@ -648,6 +787,50 @@ extern "C" int tgnn_solution_score_sums_many(int32_t n_layouts, const int32_t *a
     score_many_partial_kernel<<<ub, kMnThreads, 0, s>>>(d, start, predict, area_ratio, ld_area, perimeter, adj_edge_index, adj_edge_len,
                                                         ld_len, partial, err);
     score_many_final_kernel<<<K, 64, 0, s>>>(K, active, start, partial, err, sums);
+    TGNN_CHECK_LAUNCH();
+    return TGNN_OK;
+}
+
+extern "C" size_t tgnn_unsupervised_loss_many_workspace_bytes(int32_t n_layouts, int32_t n_maps) {
+    const size_t k = n_layouts > 0 ? (size_t)n_layouts : 1, m = n_maps > 0 ? (size_t)n_maps : 1;
+    return align_up((k + 1) * sizeof(int), 256) + align_up(k * m * kScoreMaxBlocks * 3 * sizeof(double), 256) + 256;
+}
+
+extern "C" int tgnn_unsupervised_loss_many(int32_t n_layouts, const int32_t *active, const int64_t *node_ptr, const int64_t *adj_ptr,
+                                           const int64_t *col_ptr, int64_t total_nodes, int64_t total_adj_edges,
+                                           int64_t total_col_edges, const int64_t *counts, const float *const *probs,
+                                           int64_t ld_probs, int32_t n_maps, const float *area_ratio, int64_t ld_area,
+                                           const int64_t *adj_edge_index, const float *adj_edge_len, int64_t ld_len,
+                                           const int64_t *col_edge_index, float collision_weight, float align_length_weight,
+                                           float avg_area_weight, double *losses, double *terms, int32_t *err, void *ws,
+                                           size_t ws_bytes, tgnn_stream_t stream) {
+    DeviceGuard guard__(stream);
+    TGNN_MANY_CHECK_K(n_layouts);
+    TGNN_CHECK_ARG(many_totals_ok(total_nodes, total_adj_edges, total_col_edges), "totals must fit int32");
+    TGNN_CHECK_ARG(n_maps >= 1 && n_maps <= 65535 && ld_probs >= n_maps && ld_area >= 1, "maps / strides");
+    if (n_layouts == 0) return TGNN_OK;
+    TGNN_CHECK_ARG(node_ptr && adj_ptr && col_ptr, "null offset table");
+    TGNN_CHECK_ARG(probs && losses && err && (total_nodes == 0 || area_ratio), "null pointer");
+    TGNN_CHECK_ARG(total_adj_edges == 0 || (adj_edge_index && adj_edge_len && ld_len >= 1), "adjacency edges");
+    TGNN_CHECK_ARG(total_col_edges == 0 || col_edge_index, "collision edges");
+    if (!ws || ws_bytes < tgnn_unsupervised_loss_many_workspace_bytes(n_layouts, n_maps)) {
+        set_error("tgnn_unsupervised_loss_many: workspace too small");
+        return TGNN_ERR_WORKSPACE;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int K = n_layouts;
+    Carver cv(ws, ws_bytes);
+    int *start = cv.take<int>((size_t)K + 1);
+    double *partial = cv.take<double>((size_t)K * n_maps * kScoreMaxBlocks * 3);
+    TGNN_CHECK_HIP(hipMemsetAsync(err, 0, (size_t)K * sizeof(int32_t), s));
+    ManyDesc d{K, {node_ptr, adj_ptr, col_ptr}, {total_nodes, total_adj_edges, total_col_edges}, active, counts};
+    LossManyArgs a{probs, ld_probs, n_maps, area_ratio, ld_area, adj_edge_index, adj_edge_len, ld_len, col_edge_index,
+                   collision_weight, align_length_weight, avg_area_weight, losses, terms, err, start, partial};
+    many_plan_kernel<<<1, kMnThreads, 0, s>>>(d, 1, 2, start, err);
+    // blocks of layout k: clamp(ceil(max(n, ec, ea) / kChunk), 1, 512) <= (n + ec + ea) / kChunk + 1
+    const int ub = many_blocks_ub(total_nodes + total_adj_edges + total_col_edges, K);
+    loss_many_partial_kernel<<<dim3(ub, n_maps), kMnThreads, 0, s>>>(d, a);
+    loss_many_final_kernel<<<dim3(K, n_maps), 64, 0, s>>>(d, a);
     TGNN_CHECK_LAUNCH();
     return TGNN_OK;
 }

@@ -3,7 +3,9 @@
 on the GPU through `tgnn_unsupervised_loss` (csrc/loss.hip).  Same arguments and the same three return values as the
 reference: (min loss as a 0-dim tensor, arg-min as numpy, all losses as numpy).  When `probs` requires grad (the
 training step, trainer.py:76-80) the returned loss is differentiable: its backward is `tgnn_unsupervised_loss_bwd`
-(csrc/backward.hip) on the arg-min map -- the path torch.min's gradient takes in the reference (losses.py:108)."""
+(csrc/backward.hip) on the arg-min map -- the path torch.min's gradient takes in the reference (losses.py:108).
+`unsupervised_losses_many` is the same loss for K packed layouts in one library call (`tgnn_unsupervised_loss_many`,
+csrc/greedy_many.hip) without a host synchronisation; `many_outputs` / `read_back_many` / `results_many` around it."""
 import ctypes as C
 import math
 
@@ -56,6 +58,148 @@ class Losses:
                                          ptr(adj) if e_adj else None, e_adj, len_ptr, int(attr.shape[1]) if e_adj else 1,
                                          wc, wl, wa, ptr(losses), ptr(terms), ptr(ws), ws_bytes, _lib.current_stream(dev)))
         return losses, terms
+
+    @staticmethod
+    def many_outputs(g, m, device):
+        """(buffer, losses [g, m], terms [g, m, 3], err [g]): the outputs of `unsupervised_losses_many` as views of ONE float64
+        buffer, losses and terms pre-filled with NaN -- so that `read_back_many` brings all three to the host in one copy."""
+        g, m = int(g), int(m)
+        buf = torch.full((4 * g * m + (g + 1) // 2,), float("nan"), dtype=torch.float64, device=device)
+        err = buf[4 * g * m:].view(torch.int32)[:g]
+        err.zero_()
+        return buf, buf[:g * m].view(g, m), buf[g * m:4 * g * m].view(g, m, 3), err
+
+    @staticmethod
+    def read_back_many(buf, g, m):
+        """The buffer of `many_outputs` on the host, in one copy behind one synchronisation: numpy (losses, terms, err)."""
+        g, m = int(g), int(m)
+        host = torch.empty(buf.shape, dtype=buf.dtype, pin_memory=True)
+        host.copy_(buf, non_blocking=True)
+        torch.cuda.current_stream(buf.device).synchronize()
+        h = host.numpy()
+        return h[:g * m].reshape(g, m), h[g * m:4 * g * m].reshape(g, m, 3), h[4 * g * m:].view(np.int32)[:g]
+
+    @staticmethod
+    def unsupervised_losses_many(probs, packed, first=0, count=None, buffers=None, counts=None, active=None, weights=None,
+                                 out=None):
+        """`unsupervised_losses` for the layouts first .. first + count of a `PackedLayouts` in ONE library call
+        (`tgnn_unsupervised_loss_many`, csrc/greedy_many.hip): per layout and map the bits of the single-layout call.
+        probs: one [n_k, M] float32 CUDA tensor per layout of the group (what `forward_many` returned), None = skipped.
+        buffers = (x, adj, attr, col): buffers laid out like the packed arrays instead of them, with counts = the device int64
+        [K][3] table of the sub-layouts' sizes (what `tgnn_sublayout_compact_many` left: the solve loop's x_out ..).
+        active: one truth value per layout of the group (None: all); a layout is skipped when it is inactive or has no probs.
+        out = (losses, terms, err) to write into (rows of `many_outputs`); else new tensors, skipped rows pre-filled with NaN.
+        -> (losses [G, M] float64, terms [G, M, 3] float64, err [G] int32) on the device; nothing is synchronised.  A layout
+        with an offset, count or edge end out of range has err 1 and NaN rows (`results_many` raises for it)."""
+        first = int(first)
+        g = packed.k - first if count is None else int(count)
+        if first < 0 or g < 0 or first + g > packed.k:
+            raise ValueError(f"layouts {first} .. {first + g} of {packed.k}")
+        probs = list(probs)
+        if len(probs) != g:
+            raise ValueError(f"probs: one entry per layout of the group ({g}), got {len(probs)}")
+        words = [p is not None for p in probs] if active is None else [bool(a) and p is not None for a, p in zip(active, probs)]
+        if len(words) != g:
+            raise ValueError(f"active: one entry per layout of the group ({g})")
+        dev = packed.device
+        m = ld = None
+        kept = []
+        for i, p in enumerate(probs):
+            if p is None:
+                continue
+            if not p.is_cuda:
+                raise RuntimeError("tilingnn_amd has no CPU path: the loss runs on the GPU the probabilities live on")
+            if p.dim() != 2 or p.dtype != torch.float32:
+                raise ValueError(f"probs[{i}] must be [N, M] float32, got {tuple(p.shape)} {p.dtype}")
+            full = packed.nodes(first + i)
+            if (counts is None and int(p.shape[0]) != full) or int(p.shape[0]) > full:
+                raise ValueError(f"probs[{i}] has {int(p.shape[0])} rows, layout {first + i} has {full} nodes")
+            if m is None:
+                m = int(p.shape[1])
+            if int(p.shape[1]) != m:
+                raise ValueError(f"probs[{i}] has {int(p.shape[1])} maps, the first has {m}")
+            rows_matter = int(p.shape[0]) > 1
+            if (m > 1 and p.stride(1) != 1) or (rows_matter and p.stride(0) < m):
+                p = p.contiguous()
+            if rows_matter:
+                if ld is None:
+                    ld = int(p.stride(0))
+                elif int(p.stride(0)) != ld:                    # one row stride for the call
+                    p = p.contiguous()
+                    if ld != m:
+                        raise ValueError("probs: the members must share one row stride")
+            kept.append(p)
+            probs[i] = p
+        if m is None:
+            m = 1 if out is None else int(out[0].shape[1])
+        if ld is None:
+            ld = m
+        if out is None:
+            _, losses, terms, err = Losses.many_outputs(g, m, dev)
+        else:
+            losses, terms, err = out
+            if tuple(losses.shape) != (g, m) or tuple(terms.shape) != (g, m, 3) or tuple(err.shape) != (g,) or \
+                    losses.dtype != torch.float64 or terms.dtype != torch.float64 or err.dtype != torch.int32 or \
+                    not (losses.is_contiguous() and terms.is_contiguous() and err.is_contiguous()):
+                raise ValueError("out: (losses [G, M] float64, terms [G, M, 3] float64, err [G] int32), contiguous")
+        if not any(words):                                      # nothing to evaluate: the rows stay as they are
+            return losses, terms, err
+        x, adj, attr, col = buffers if buffers is not None else (packed.x, packed.adj, packed.attr, packed.col)
+        x = ops._f32c(x, "node features")
+        if x.dim() != 2 or int(x.shape[1]) != packed.fx or int(x.shape[0]) < packed.n:
+            raise ValueError(f"node features must be [>= {packed.n}, {packed.fx}], got {tuple(x.shape)}")
+        if packed.ea and (attr.dtype != torch.float32 or not attr.is_contiguous() or attr.numel() < packed.ea * packed.fe or
+                          adj.dtype != torch.int64 or not adj.is_contiguous() or adj.numel() < 2 * packed.ea or packed.fe < 2):
+            raise ValueError("adjacency buffers must be laid out like the packed arrays (int64 [2 Ea], float32 [Ea, Fe >= 2])")
+        if packed.ec and (col.dtype != torch.int64 or not col.is_contiguous() or col.numel() < 2 * packed.ec):
+            raise ValueError("collision buffer must be laid out like the packed array (int64 [2 Ec])")
+        if counts is not None and (counts.dtype != torch.int64 or not counts.is_contiguous() or counts.numel() < 3 * packed.k or
+                                   counts.device != x.device):
+            raise ValueError("counts: device int64 [K][3]")
+        # pointer table [G] | active words [G] int32: one upload
+        meta_h = torch.zeros(g + (g + 1) // 2, dtype=torch.int64, pin_memory=True)
+        meta_h[:g] = torch.tensor([p.data_ptr() if (p is not None and w) else 0 for p, w in zip(probs, words)], dtype=torch.int64)
+        meta_h[g:].view(torch.int32)[:g] = torch.tensor([int(w) for w in words], dtype=torch.int32)
+        meta = torch.empty(meta_h.shape, dtype=torch.int64, device=dev)
+        meta.copy_(meta_h, non_blocking=True)
+        wc, wl, wa = weights if weights is not None else loss_weights()
+        ws_bytes = int(lib.tgnn_unsupervised_loss_many_workspace_bytes(g, m))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        at = lambda t, off: C.c_void_p(t.data_ptr() + off)
+        with torch.cuda.device(dev):
+            check(lib.tgnn_unsupervised_loss_many(
+                g, at(meta, 8 * g), at(packed.node_ptr, 8 * first), at(packed.adj_ptr, 8 * first), at(packed.col_ptr, 8 * first),
+                packed.n, packed.ea, packed.ec, None if counts is None else at(counts, 24 * first), ptr(meta), ld, m,
+                at(x, 4 * (packed.fx - 1)), packed.fx, ptr(adj) if packed.ea else None, at(attr, 4) if packed.ea else None,
+                packed.fe, ptr(col) if packed.ec else None, wc, wl, wa, ptr(losses), ptr(terms), ptr(err), ptr(ws), ws_bytes,
+                _lib.current_stream(dev)))
+        del kept
+        return losses, terms, err
+
+    @staticmethod
+    def results_many(losses, terms, err, present=None, first=0):
+        """Read-back (losses [G, M], terms [G, M, 3], err [G]) of `unsupervised_losses_many` (numpy or CPU tensors) -> per layout
+        what `_calculate` returns, (loss as a 0-dim float32 tensor, arg-min as numpy, all losses as float32 numpy, terms), with
+        its checks; None for a layout that was skipped (present[i] false; default: every layout was evaluated).  `first`: the
+        number of the group's first layout, for the messages."""
+        losses, terms, err = (t.numpy() if torch.is_tensor(t) else np.asarray(t) for t in (losses, terms, err))
+        results = []
+        for i in range(losses.shape[0]):
+            if present is not None and not present[i]:
+                results.append(None)
+                continue
+            host = losses[i]
+            if err[i] or np.isnan(host).any():                  # the kernel's report of an offset, count or edge end out of range
+                raise IndexError(f"layout {first + i}: edge index out of range in collide_edge_index / adj_edges_index, or offsets "
+                                 "that do not fit the packed arrays (torch.gather raises here in the reference, "
+                                 "losses.py:70-73,85-88)")
+            # the reference asserts these signs (losses.py:100-102,108)
+            assert (terms[i] <= 0).all(), "loss terms must be non-positive"
+            assert (host >= 1.0).all()
+            min_index = np.argmin(host)
+            loss = torch.from_numpy(np.ascontiguousarray(host))[int(min_index)].to(torch.float32)
+            results.append((loss, np.asarray(min_index), host.astype(np.float32), terms[i]))
+        return results
 
     @staticmethod
     def calculate_unsupervised_loss(probs, node_feature, collide_edge_index, adj_edges_index, adj_edge_features):

@@ -16,7 +16,9 @@ Here: the same loop with
 shapely in a 16-process pool.  Not mirrored: the per-checkpoint debug plots (`ml_solver.save_debug_info`, trainer.py:113-121).  `train` takes batch_size 1, the only
 value the reference configures; mini-batches -- PyG's disjoint-union batching, the `batch_size` of the reference's signature
 (trainer.py:55, :60) -- are `train_batches`: per step the union of B layouts is written by one launch (`ops.batch_union`,
-csrc/batch_union.hip) and goes through the same `train_step`.
+csrc/batch_union.hip) and goes through the same `train_step`.  The evaluation of the single-layout splits after an epoch runs one
+layout at a time (`cal_avg_loss`) or, with `eval_group=G`, G layouts per forward / loss call behind one read-back per split
+(`cal_avg_loss_many`: the same float).
 """
 import contextlib
 import glob
@@ -28,7 +30,7 @@ import torch
 
 from ... import ops
 from ...util import data_util
-from ...util.algorithms import DeviceLayout, PackedLayouts
+from ...util.algorithms import DeviceLayout, PackedLayouts, _forward_many_checked
 from .losses import Losses
 
 
@@ -86,6 +88,68 @@ def cal_avg_loss(network, layouts):
     finally:
         network.autograd = was
     return float(np.mean(losses)) if losses else float("nan")
+
+
+def eval_groups(n, group):
+    """range(n) cut into contiguous groups of `group`, the short last one kept: what one `unsupervised_losses_many` call covers."""
+    group = int(group)
+    if group < 1:
+        raise ValueError("group must be at least 1")
+    return [range(i, min(i + group, int(n))) for i in range(0, int(n), group)]
+
+
+def _split_layouts(split, device=None):
+    """(PackedLayouts, one DeviceLayout per member) of a LayoutDataset, a PackedLayouts or a list of layouts.  A data set's own
+    layouts are the ones its prepared graphs are cached under; the views of a PackedLayouts are made once and kept with it."""
+    if isinstance(split, LayoutDataset):
+        return split.packed, split.layouts
+    if not isinstance(split, PackedLayouts):
+        split = list(split)
+        if not split:
+            return None, []
+        split = PackedLayouts(split, device if device is not None else split[0].node_feature.device)
+    views = getattr(split, "_member_views", None)
+    if views is None:
+        views = split._member_views = [split.layout(k) for k in range(split.k)]
+    return split, views
+
+
+def cal_avg_loss_many(network, dataset_or_packed, group=32, union=True):
+    """`cal_avg_loss` with the work of `group` layouts per call: the members of every contiguous group (file order) that have both
+    edge sets are scored by `network.forward_many(..., union=union)` -- the solo forward's bits --, the persistent kernels'
+    health word is polled once per group, and ONE `Losses.unsupervised_losses_many` call per group (the solo loss's bits) writes
+    into one device buffer that is read back once per split.  The same float as `cal_avg_loss(network, split)`: the per-layout
+    minimum cast to float32, then np.mean over Python floats; NaN for an empty split.  One difference that reaches no output: in
+    train mode `forward_many` leaves the BatchNorm running statistics untouched where `cal_avg_loss` updates them once per
+    layout; train-mode outputs do not read them."""
+    packed, lays = _split_layouts(dataset_or_packed, getattr(dataset_or_packed, "device", None))
+    n = len(lays)
+    if n == 0:
+        return float("nan")
+    m = int(network.output_dim)
+    buf, losses, terms, err = Losses.many_outputs(n, m, packed.device)
+    present = [False] * n
+    was = network.autograd
+    network.autograd = False
+    try:
+        with torch.no_grad():
+            for ids in eval_groups(n, group):
+                keep = [k for k in ids if lays[k].align_edge_index.numel() != 0 and lays[k].collide_edge_index.numel() != 0]
+                outs = _forward_many_checked(network, [lays[k] for k in keep], 3, union=bool(union)) if keep else []
+                probs = [None] * len(ids)
+                for k, out in zip(keep, outs):
+                    probs[k - ids[0]] = out
+                    present[k] = True
+                rows = slice(ids[0], ids[0] + len(ids))
+                Losses.unsupervised_losses_many(probs, packed, first=ids[0], count=len(ids),
+                                                out=(losses[rows], terms[rows], err[rows]))
+                del outs, probs
+    finally:
+        network.autograd = was
+    if not any(present):
+        return float("nan")
+    results = Losses.results_many(*Losses.read_back_many(buf, n, m), present=present)      # the split's ONE read-back
+    return float(np.mean([float(r[0]) for r in results if r is not None]))
 
 
 def batch_chunks(order, batch_size):
@@ -218,7 +282,10 @@ class Trainer:
         return loss.detach()
 
     def train(self, ml_solver, optimizer, batch_size=1, training_epoch=10000, save_model_per_epoch=5, shuffle_seed=None,
-              log=print):
+              log=print, eval_group=None):
+        """eval_group: None = the splits are evaluated one layout at a time (`cal_avg_loss`); an integer = `eval_group` layouts
+        per forward_many / loss call (`cal_avg_loss_many`: the same losses, BatchNorm running statistics left untouched)."""
+        evaluate = cal_avg_loss if eval_group is None else (lambda net, split: cal_avg_loss_many(net, split, group=eval_group))
         if batch_size != 1:
             raise NotImplementedError("batch_size 1 only (inputs/config.py:44)")
         train_set = LayoutDataset(self.training_path, self.device)
@@ -238,9 +305,9 @@ class Trainer:
                         log(traceback.format_exc())
             finally:
                 self.network.autograd = False
-            loss_train = cal_avg_loss(self.network, train_set)
+            loss_train = evaluate(self.network, train_set)
             log(f"epoch {epoch}: training loss: {loss_train}")
-            loss_test = cal_avg_loss(self.network, test_set)
+            loss_test = evaluate(self.network, test_set)
             log(f"epoch {epoch}: testing loss: {loss_test}")
             history.append((loss_train, loss_test))
             if loss_test < min_test_loss or epoch % save_model_per_epoch == 0:      # trainer.py:96-108
@@ -265,12 +332,13 @@ class Trainer:
             return self.train_step(ops.batch_union(packed, ids), optimizer)
 
     def train_batches(self, ml_solver, optimizer, batch_size=32, training_epoch=10000, save_model_per_epoch=5,
-                      shuffle_seed=None, log=print):
+                      shuffle_seed=None, log=print, eval_group=None):
         """The loop of `train` on mini-batches (the reference's `train` with its `batch_size`, trainer.py:52-124): every epoch's
         permutation is cut into consecutive chunks of `batch_size` (the short last one kept: DataLoader's drop_last=False) and
         every chunk is one `train_batch_step`.  After the epoch the training loss is the mean over the batches of the training
         split (in file order, same `batch_size`: the reference evaluates `loader_train`), the test loss the mean over single
-        layouts (`loader_test` has batch_size 1); checkpoints as in `train`."""
+        layouts (`loader_test` has batch_size 1); checkpoints as in `train`.  eval_group: as in `train`, for the test split."""
+        evaluate = cal_avg_loss if eval_group is None else (lambda net, split: cal_avg_loss_many(net, split, group=eval_group))
         if int(batch_size) < 1:
             raise ValueError("batch_size must be at least 1")
         chunks_of = lambda order: batch_chunks(order, batch_size)
@@ -295,7 +363,7 @@ class Trainer:
                 self.network.autograd = False
             loss_train = cal_avg_loss_batches(self.network, packed, eval_chunks)
             log(f"epoch {epoch}: training loss: {loss_train}")
-            loss_test = cal_avg_loss(self.network, test_set)
+            loss_test = evaluate(self.network, test_set)
             log(f"epoch {epoch}: testing loss: {loss_test}")
             history.append((loss_train, loss_test))
             if loss_test < min_test_loss or epoch % save_model_per_epoch == 0:      # trainer.py:96-108

@@ -349,7 +349,9 @@ def solve_many_by_device_greedy(ml_solver, layouts, seed=0, seeds=None, score_fn
     gives for the whole layout).  `ml_solver.union_forward = True` (an attribute like `device_greedy_seed`, default False): every
     round's small sub-layouts are scored inside one persistent kernel launch (`forward_many(union=True)`) -- the same bits, fewer
     launches.  `ml_solver.union_prep = True` beside it: their graphs are prepared by one library call and one read-back per round
-    (`forward_many(union=True, union_prep=True)`) -- the same graphs."""
+    (`forward_many(union=True, union_prep=True)`) -- the same graphs.  A network with several probability maps: the best map of
+    every sub-layout of a round comes from ONE loss call and one read-back (`Losses.unsupervised_losses_many` over the round's
+    compacted buffers) -- the single-layout losses' bits, hence the same picks."""
     device = ml_solver.device
     originals = None if isinstance(layouts, PackedLayouts) else list(layouts)
     solve_many_by_device_greedy.last_rounds = []
@@ -455,8 +457,9 @@ def solve_many_by_device_greedy(ml_solver, layouts, seed=0, seeds=None, score_fn
                 outs = _forward_many_checked(network, views, streams, union_forward, union_prep)
             else:
                 outs = [ml_solver.predict_on_device(v).reshape(-1, 1) for v in views]
+            best_of = _best_prob_maps_many(pk, need_net, outs, (x_out, adj_out, attr_out, col_out), counts) if outs[0].shape[1] > 1 else None
             for k, sub, out in zip(need_net, views, outs):
-                best = ml_solver._best_prob_map(out, sub) if out.shape[1] > 1 else 0
+                best = best_of[k] if best_of is not None else 0
                 meta_h[k] = out.data_ptr() + 4 * best
                 if rnd == 1:
                     first_probs[k] = out[:, best].detach().contiguous()
@@ -496,6 +499,21 @@ def solve_many_by_device_greedy(ml_solver, layouts, seed=0, seeds=None, score_fn
     solve_many_by_device_greedy.last_rounds = rounds
     solve_many_by_device_greedy.last_first_probs = first_probs
     return [empty[k] if k in empty else (selections[k], scores[k], orders[k]) for k in range(K)]
+
+
+def _best_prob_maps_many(pk, members, outs, buffers, counts):
+    """`ML_Solver._best_prob_map` (get_best_prob_map, ml_solver.py:133-136) for the sub-layouts `members` of a round at once: ONE
+    `Losses.unsupervised_losses_many` call over the round's compacted buffers, one read-back, then the reference's pick on the
+    float32 losses -- per layout the losses, the checks and the pick of the single-layout call.  -> {layout: map}."""
+    from ..solver.ml_solver.losses import Losses
+    probs, live = [None] * pk.k, [False] * pk.k
+    for k, out in zip(members, outs):
+        probs[k], live[k] = out, True
+    m = int(outs[0].shape[1])
+    buf, losses, terms, err = Losses.many_outputs(pk.k, m, pk.device)
+    Losses.unsupervised_losses_many(probs, pk, buffers=buffers, counts=counts, active=live, out=(losses, terms, err))
+    results = Losses.results_many(*Losses.read_back_many(buf, pk.k, m), present=live)
+    return {k: int(np.argsort(results[k][2])[0]) for k in members}
 
 
 def _scores_many(pk, selections, originals, score_fn, device):
