@@ -4,6 +4,9 @@ product path refuses to run without a GPU instead of falling back."""
 import copy
 import os
 import re
+import shutil
+import struct
+import subprocess
 
 import numpy as np
 import pytest
@@ -12,11 +15,34 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def header_functions():
+def header_functions(debug_hooks=False):
     text = open(os.path.join(REPO, "include", "tgnn.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"#ifdef TGNN_DEBUG.*?#endif", "", text, flags=re.S)       # the test hooks of libtgnn_debug.so
+    if debug_hooks:                                                           # the test hooks of libtgnn_debug.so alone
+        text = "".join(re.findall(r"#ifdef TGNN_DEBUG(.*?)#endif", text, flags=re.S))
+    else:
+        text = re.sub(r"#ifdef TGNN_DEBUG.*?#endif", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b(tgnn_[a-z0-9_]+)\s*\(", text)))
+
+
+def dynamic_symbols(path):
+    """Names the shared library at `path` defines in its dynamic symbol table (ELF64, little endian: .dynsym / .dynstr)."""
+    data = open(path, "rb").read()
+    assert data[:6] == b"\x7fELF\x02\x01", "not a little-endian ELF64 file"
+    shoff, = struct.unpack_from("<Q", data, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", data, 0x3A)
+    sections = [struct.unpack_from("<IIQQQQIIQQ", data, shoff + i * shentsize) for i in range(shnum)]
+    names = set()
+    for sec in sections:
+        if sec[1] != 11:                                                      # SHT_DYNSYM
+            continue
+        _, _, _, _, off, size, link, _, _, entsize = sec
+        stroff = sections[link][4]
+        for k in range(size // entsize):
+            st_name, _, _, st_shndx = struct.unpack_from("<IBBH", data, off + k * entsize)
+            if st_shndx != 0:                                                 # (SHN_UNDEF: imported, not defined here)
+                names.add(data[stroff + st_name:data.index(b"\0", stroff + st_name)].decode())
+    return names
 
 
 def test_library_exports_every_declared_symbol():
@@ -27,9 +53,34 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(_lib.lib, name), f"{name} is declared in include/tgnn.h but not exported by libtgnn.so"
     assert sorted(_lib.EXPORTED_SYMBOLS) == declared, "ctypes binding table and header disagree"
     assert _lib.lib.tgnn_version() == 100
-    # the production library carries no test hook (they live in libtgnn_debug.so: make -C tilingnn_amd/csrc debug)
-    if not os.environ.get("TGNN_LIB_PATH"):
-        assert not any(hasattr(_lib.lib, n) for n in ("tgnn_debug_spin_fault", "tgnn_debug_set_csr_bucket_cap", "tgnn_debug_set_block_caps"))
+    # ... and nothing else: every tgnn_* name in the dynamic symbol table is a declared one.  The production library carries no
+    # test hook; libtgnn_debug.so (make -C tilingnn_amd/csrc debug) only the ones the header declares under TGNN_DEBUG
+    exported = sorted(n for n in dynamic_symbols(_lib.LIB_PATH) if n.startswith("tgnn_"))
+    allowed = set(declared) | (set(header_functions(debug_hooks=True)) if os.environ.get("TGNN_LIB_PATH") else set())
+    stray = [n for n in exported if n not in allowed]
+    assert not stray, f"exported by {_lib.LIB_PATH} but not declared in include/tgnn.h: {stray}"
+    assert set(declared) <= set(exported)
+
+
+def test_forward_plan_invariants_host_program():
+    """tests/host/forward_plan_test.cpp: plan_forward (csrc/forward_plan.h) over the cross product of its facts with a fake probe,
+    built with the host compiler alone (no HIP header) under AddressSanitizer + UBSan."""
+    import tempfile
+    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    # (the sanitizers' runtime linked into the program itself: it then runs under whatever the environment preloads)
+    clang = "clang" in subprocess.run([cxx, "--version"], capture_output=True, text=True).stdout
+    static_rt = ["-static-libsan"] if clang else ["-static-libasan", "-static-libubsan"]
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = os.path.join(tmp, "forward_plan_test")
+        build = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                                "-fno-sanitize-recover=undefined", *static_rt, "-I", os.path.join(REPO, "include"),
+                                "-I", os.path.join(REPO, "tilingnn_amd", "csrc"),
+                                os.path.join(REPO, "tests", "host", "forward_plan_test.cpp"), "-o", exe], capture_output=True, text=True)
+        assert build.returncode == 0, build.stderr[-4000:]
+        run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0, (run.stdout + run.stderr)[-4000:]
+    assert re.search(r"forward_plan_test: \d{7,} combinations, 0 failures", run.stdout), run.stdout
 
 
 def test_param_table_names_are_the_reference_state_dict_keys():

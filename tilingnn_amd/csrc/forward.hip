@@ -20,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "forward_plan.h"
 #include "tgnn_common.h"
 
 namespace tgnn {
@@ -131,10 +132,10 @@ struct Prof {
 };
 
 static const int kFinalDims[4] = {256, 128, 64, 0};  // TilinGNN.py:46 hidden_layer_dims; [3] = C
-constexpr int kCarveTypes = 16;                      // (= tgnn_nnconv_cols_max_types(): what the matrix-core NNConv kernels take)
+static_assert(kPlanMaxDepth == kMaxDepth, "forward_plan.h plans for the depth the kernels take");
 static std::atomic<int> g_split_f16{1};              // tgnn_set_split_precision
 static std::atomic<int> g_nnconv_eg{1};              // tgnn_set_nnconv_eg
-static std::atomic<int> g_lean_head{3};              // tgnn_set_lean_head: bit 0 the head without memsets / early edge-weight event, bit 1 the fused init MLP
+static std::atomic<int> g_lean_head{3};              // tgnn_set_lean_head: bit 0 the head without memsets / early edge-weight event, bit 1 the fused init MLP, bit 2 the final MLP's folded BatchNorm records
 static std::atomic<int64_t> g_path_count[3];          // forwards queued on the general schedule / small-layout kernel / mid-size kernel
 static std::atomic<int64_t> g_union_count[2];         // tgnn_forward_union: persistent launches / layouts scored inside them
 
@@ -198,7 +199,7 @@ extern "C" int32_t tgnn_set_nnconv_eg(int32_t on) {
     return g_nnconv_eg.exchange(on);
 }
 extern "C" int32_t tgnn_set_lean_head(int32_t bits) {
-    if (bits < 0 || bits > 31) return g_lean_head.load();
+    if (bits < 0 || bits > 7) return g_lean_head.load();
     return g_lean_head.exchange(bits);
 }
 extern "C" const char *tgnn_last_error(void) { return g_err; }
@@ -239,6 +240,39 @@ extern "C" size_t tgnn_forward_sharded_workspace_bytes(const tgnn_model_dims *di
         if (rc__ != TGNN_OK) return rc__; \
     } while (0)
 
+// ---- what the entry points share in front of their launches: each with its caller's name in the message -------------------
+static int check_params(const tgnn_model_dims *dims, const void *const *params_host, const char *who) {
+    const int np = tgnn_param_count(dims);
+    for (int i = 0; i < np; ++i)
+        if (!params_host[i]) {
+            set_error("%s: params_host[%d] is null", who, i);
+            return TGNN_ERR_INVALID_ARG;
+        }
+    return TGNN_OK;
+}
+// (who == NULL: the code alone, no message)
+static int carve_checked(const tgnn_model_dims &d, int64_t n, int64_t nr, int32_t n_types, void *ws, size_t ws_bytes, const char *who,
+                         Workspace *w) {
+    *w = carve(d, n, nr, n_types, ws, ws_bytes);
+    if (!ws || w->bytes > ws_bytes) {
+        if (who) set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, w->bytes);
+        return TGNN_ERR_WORKSPACE;
+    }
+    return TGNN_OK;
+}
+// the edge MLP of every layer and the layers' root matrices, as launch_edge_weight_table_batched / launch_forward_scales take them
+struct EdgeMlpTable {
+    EdgeMlpLayers layers{};
+    const float *roots[kMaxDepth];
+    EdgeMlpTable(const Params &P, int D) {
+        for (int i = 0; i < D; ++i) {
+            const int b = P.layer(i);
+            layers.l[i] = EdgeMlpLayer{P.f(b), P.f(b + 1), P.f(b + 2), P.f(b + 3), P.f(b + 4), P.f(b + 5)};
+            roots[i] = P.f(b + 6);
+        }
+    }
+};
+
 // [r6] What the general schedule does in front of its first layer that needs NOTHING of the graph: the operands' bounds, the init
 // MLP (middle[0] and its bound), the final MLP's bounds and operand images.  Either inside forward_impl or -- tgnn_forward_begin --
 // before the layout is prepared, on the side stream, beside the preparation's launches.
@@ -256,6 +290,52 @@ struct SmallPre {
     int64_t n = 0;
 };
 static thread_local SmallPre g_small_pre[64];
+
+// The ONE place a forward consumes the two hand-over records of its thread and device.  Today's rules, unchanged:
+//  - the small pre-pass record is cleared by ANY forward that gets this far (a match or not) -- but a forward that failed an
+//    argument check, the stale-result check or the workspace check in front of this call leaves it standing;
+//  - the head record is looked at by tgnn_forward_resume alone; a resume that does not match fails and leaves it standing; a
+//    matching one clears it and makes `s` wait for the head's event.
+struct HandOver {
+    bool small_pre_match = false;    // tgnn_forward_small_prepass queued for this workspace and node count
+    bool weights_early = false;      // tgnn_forward_begin_weights queued behind the matching tgnn_forward_begin
+};
+static int consume_handover(const void *ws, int64_t n, bool head_done, hipStream_t s, HandOver *out) {
+    {
+        int devp = 0;
+        if (hipGetDevice(&devp) == hipSuccess && devp >= 0 && devp < 64 && g_small_pre[devp].ws) {
+            out->small_pre_match = g_small_pre[devp].ws == ws && g_small_pre[devp].n == n;
+            g_small_pre[devp].ws = nullptr;
+        }
+    }
+    if (head_done) {
+        int dev = 0;
+        TGNN_CHECK_HIP(hipGetDevice(&dev));
+        TGNN_CHECK_ARG(dev >= 0 && dev < 64 && g_head[dev].ev && g_head[dev].ws == ws && g_head[dev].n == n,
+                       "tgnn_forward_resume without a matching tgnn_forward_begin (same thread, device, workspace, node count)");
+        g_head[dev].ws = nullptr;
+        out->weights_early = g_head[dev].weights;
+        g_head[dev].weights = false;
+        TGNN_CHECK_HIP(hipStreamWaitEvent(s, g_head[dev].ev, 0));   // middle[0], the bounds, the final MLP's images: done long ago (the preparation ran meanwhile)
+    }
+    return TGNN_OK;
+}
+
+// Events of the two-chain schedule, per calling thread and device; created once, never destroyed.
+// [0] init done, [1 + i] GIN_i done, [1 + kMaxDepth + i] merge_i done, then: fork at entry, edge weights done
+constexpr int kEvPerDev = 3 + 2 * kMaxDepth, kEvFork = 1 + 2 * kMaxDepth, kEvWeights = 2 + 2 * kMaxDepth;
+static int two_chain_events(hipEvent_t **ev) {
+    static thread_local hipEvent_t ev_cache[64][kEvPerDev] = {};
+    int dev = 0;
+    TGNN_CHECK_HIP(hipGetDevice(&dev));
+    TGNN_CHECK_ARG(dev >= 0 && dev < 64, "device index");
+    if (!ev_cache[dev][0])
+        for (int k = 0; k < kEvPerDev; ++k)
+            TGNN_CHECK_HIP(hipEventCreateWithFlags(&ev_cache[dev][k], hipEventDisableTiming));
+    *ev = ev_cache[dev];
+    return TGNN_OK;
+}
+
 // words of w.bounds holding (max |W_l|, bound of |BN(input of l)|) of the final MLP's layer l = 1 .. 3 (3: lean head only)
 static inline unsigned *final_bound_word(const Workspace &w, int D, int l) { return w.bounds + (l <= 2 ? 2 * D + 2 + 2 * (l - 1) : 2 * D + 8); }
 static int forward_head_bounds_images(const tgnn_model_dims *dims, const Params &P, const Workspace &w, int64_t n, int64_t n_total,
@@ -313,16 +393,622 @@ static int forward_head_init(const tgnn_model_dims *dims, const Params &P, const
 
 // the buffer-addressed gathers of the column NNConv (width 32, the gathered buffers below 2 GB) over the layout's column structure
 static bool forward_cols_ok(const tgnn_model_dims *dims, const tgnn_graph *graph, int64_t nr) {
-    return graph->nn_tile_col_ptr && dims->network_width == 32 && (int64_t)nr * dims->network_width * 4 < (int64_t(1) << 31);
+    return graph->nn_tile_col_ptr && addr32_ok(dims->network_width, nr);
 }
 // What a forward must be to take the one persistent kernel of forward_small.hip at all -- single device, inference, train-mode
-// BatchNorm, not profiled --, whatever the layout's size: forward_impl and tgnn_forward_union both ask here, then
+// BatchNorm, not profiled --, whatever the layout's size: plan_forward (forward_plan.h) and tgnn_forward_union both ask this, then
 // small_layout_teams / small_union_tiles about the layout itself.
 static bool small_path_open(const tgnn_model_dims *dims, const tgnn_graph *graph, int64_t n, int64_t nr, bool sharded, bool keep,
                             bool use_running_stats, bool profiled) {
     return forward_cols_ok(dims, graph, nr) && !sharded && !keep && !use_running_stats && !profiled && nr == n;
 }
 
+// the three questions of plan_forward that need the device (two of them count the fall-back window down: forward_small.hip)
+struct DeviceProbe {
+    const tgnn_model_dims *dims;
+    const tgnn_graph *graph;
+    int small_layout_teams() { return tgnn::small_layout_teams(dims, graph->n_nodes, graph->n_types, graph->nn_max_in_degree); }
+    int mid_layout_tiles_per_block(int *blocks) { return tgnn::mid_layout_tiles_per_block(dims, graph, graph->n_nodes, blocks); }
+    int mid_tail_tiles_per_block(int *blocks) { return tgnn::mid_tail_tiles_per_block(dims, graph->n_nodes, blocks); }
+};
+
+// One forward being queued: what every phase reads, the phases in the order forward_impl calls them.
+// Two-chain schedule: the collision branch is a chain of its own -- CollConv_i reads only CollConv_{i-1} (TilinGNN.py:63); the
+// branches meet in the product of :64 only.  With a side stream (s2) the whole GIN chain runs free beside the NNConv chain and fills
+// the GPU wherever the latter leaves it idle (1-block BN finalizes, the HBM-bound merge, kernel tails); it is held back only by the
+// two-deep buffers it shares with merge.
+struct Forward {
+    const tgnn_model_dims *dims;
+    const Params P;
+    Workspace w;
+    const tgnn_graph *graph;
+    const tgnn_shard *sh;
+    const tgnn_train_save *keep;
+    const ForwardPlan plan;
+    const float *x, *adj_edge_attr;
+    float *probs;
+    const int32_t update_running, use_running_stats;
+    hipStream_t s, s2;               // main / side (NULL: one chain)
+    hipEvent_t *ev;
+    Prof &prof;
+    // derived
+    const int c, D, fx, fe, T;
+    const int64_t n, nr, n_total, n_halo;
+    const int fin_mode;
+    const float eps = 1e-5f, momentum = 0.1f;                // torch.nn.BatchNorm1d defaults
+    hipStream_t sw;                  // where the edge weights and the final MLP's operands are queued: s, or s2 behind the fork
+    unsigned *slot_max, *root_max, *dense_max, *fold_ctr, *weights_done;
+    unsigned weights_target;
+    bool weights_recorded = false;
+    bool dimg_ok[4] = {false, false, false, false};
+    int32_t np1 = 0, np2 = 0;
+
+    Forward(const tgnn_model_dims *dims_, const void *const *params_host, const Workspace &w_, const tgnn_graph *graph_, const tgnn_shard *sh_,
+            const tgnn_train_save *keep_, const ForwardPlan &plan_, const float *x_, const float *adj_edge_attr_, float *probs_,
+            int32_t update_running_, int32_t use_running_stats_, hipStream_t s_, hipStream_t s2_, hipEvent_t *ev_, Prof &prof_)
+        : dims(dims_), P{params_host, dims_->network_depth}, w(w_), graph(graph_), sh(sh_), keep(keep_), plan(plan_), x(x_),
+          adj_edge_attr(adj_edge_attr_), probs(probs_), update_running(update_running_), use_running_stats(use_running_stats_), s(s_),
+          s2(s2_), ev(ev_), prof(prof_), c(dims_->network_width), D(dims_->network_depth), fx(dims_->node_features_dim),
+          fe(dims_->adj_edge_features_dim), T(graph_->n_types), n(graph_->n_nodes), nr(sh_ ? sh_->n_rows : n),
+          n_total(sh_ ? sh_->n_total : n), n_halo(nr - n), fin_mode(use_running_stats_ ? 3 : 0), sw(s_) {
+        // fp16-pair operands: the kernels that write a slot of the skip buffer leave its largest magnitude (w.bounds), one launch up
+        // front those of the root matrices and of the final MLP's first Linear
+        slot_max = plan.f16 ? w.bounds : nullptr;
+        root_max = plan.f16 ? w.bounds + D + 1 : nullptr;
+        dense_max = plan.f16 ? w.bounds + 2 * D + 1 : nullptr;
+        // (17 words: gin32_mlp_kernel folds the collision branch's BatchNorm in two levels -- a ticket per row group and one over the groups)
+        fold_ctr = plan.lean_head ? w.bounds + 2 * D + 10 : w.small_ctr + 32;
+        // (the mid path's counter is a word of w.bounds that launch_forward_scales zeroes anyway: no launch of its own)
+        weights_done = plan.weights_done == WeightsDoneWord::MidBounds  ? w.bounds + 2 * D + 6
+                       : plan.weights_done == WeightsDoneWord::SmallCtr ? w.small_ctr + 16
+                                                                        : nullptr;
+        weights_target = edge_weight_table_blocks(T, fe, D, c, plan.tiled);
+    }
+
+    // ---- BatchNorm records, collectives ------------------------------------------------------------------------------------
+    BnJob bn_job(double *part, int nparts, const BnPtrs &bp, float *stat) const {
+        const bool run_stats = update_running || use_running_stats;
+        return BnJob{part, nparts, nullptr, bp.gamma, bp.beta, run_stats ? bp.rm : nullptr, run_stats ? bp.rv : nullptr,
+                     (update_running && !use_running_stats) ? bp.nbt : nullptr, stat};
+    }
+    // the two collectives: RCCL calls of the library's own when the shard carries a communicator, else the caller's callbacks
+    int allreduce(double *buf, int64_t count, hipStream_t st) {
+        if (sh->rccl_comm) return rccl_allreduce_f64(sh->rccl_comm, buf, count, st);
+        if (sh->allreduce_f64(sh->ctx, buf, count, st) != 0) {
+            set_error("tgnn_forward_sharded: the all-reduce callback failed");
+            return TGNN_ERR_INVALID_ARG;
+        }
+        return TGNN_OK;
+    }
+    int alltoall(const float *send, float *recv, int row_floats, int extra_rows, hipStream_t st) {
+        if (sh->rccl_comm) {
+            void *comm = (st != s && sh->rccl_comm_side) ? sh->rccl_comm_side : sh->rccl_comm;
+            return rccl_alltoall_rows(comm, send, recv, sh->send_counts, sh->recv_counts, sh->world, row_floats, extra_rows, st);
+        }
+        if (sh->alltoall_rows(sh->ctx, send, recv, row_floats, extra_rows, st) != 0) {
+            set_error("tgnn_forward_sharded: the all-to-all callback failed");
+            return TGNN_ERR_INVALID_ARG;
+        }
+        return TGNN_OK;
+    }
+    // BatchNorm statistics from the producers' partial rows.  Sharded: partials -> local sums (mode 1) -> all-reduce over the
+    // shards (both BatchNorms of a layer travel in one message) -> stat record (mode 2).
+    int finalize_jobs(BnJobs jobs, int nj, int f) {
+        if (nj == 0) return TGNN_OK;
+        if (!sh) {
+            prof.begin(4);
+            launch_bn_finalize(jobs, nj, fin_mode, f, n, eps, momentum, s);
+            prof.end();
+            return TGNN_OK;
+        }
+        for (int j = 0; j < nj; ++j) jobs.job[j].sums = sh->sum_buf + (size_t)j * 2 * f;
+        launch_bn_finalize(jobs, nj, 1, f, n_total, eps, momentum, s);
+        TGNN_TRY(allreduce(sh->sum_buf, (int64_t)nj * 2 * f, s));
+        launch_bn_finalize(jobs, nj, 2, f, n_total, eps, momentum, s);
+        return TGNN_OK;
+    }
+    int finalize1(double *part, int nparts, int f, const BnPtrs &b, float *stat) {
+        BnJobs jobs{};
+        jobs.job[0] = bn_job(part, nparts, b, stat);
+        return finalize_jobs(jobs, 1, f);
+    }
+    // one collision BatchNorm's own 1-block finalize, on the chain the GIN ran on (single device)
+    void finalize_collision(int i, hipStream_t st) {
+        BnJobs j2{};
+        j2.job[0] = bn_job(w.part2, np2, P.bn(P.layer(i) + 20), w.stat2[i & 1]);
+        launch_bn_finalize(j2, 1, fin_mode, c, n, eps, momentum, st);
+    }
+    // Halo exchange: the rows other shards need (send_idx) of slot `slot` of the skip buffer and, from layer 1 on, of the collision
+    // branch's pre-BN activations travel in ONE all-to-all (64 floats per row) and land behind the owned rows.
+    int exchange(int slot, const float *a2_own, float *a2_halo_dst) {
+        if (!sh) return TGNN_OK;
+        const int rf = a2_own ? 2 * c : c;                     // floats per exchanged row
+        float *slot_rows = w.mid + (size_t)slot * nr * c;
+        if (sh->n_send > 0) {
+            TGNN_TRY(tgnn_rows_gather(slot_rows, c, sh->send_idx, sh->n_send, c, sh->send_buf, rf, s));
+            if (a2_own) TGNN_TRY(tgnn_rows_gather(a2_own, c, sh->send_idx, sh->n_send, c, sh->send_buf + c, rf, s));
+        }
+        TGNN_TRY(alltoall(sh->send_buf, sh->recv_buf, rf, 0, s));
+        if (n_halo > 0) {
+            TGNN_CHECK_HIP(hipMemcpy2DAsync(slot_rows + (size_t)n * c, (size_t)c * 4, sh->recv_buf, (size_t)rf * 4,
+                                            (size_t)c * 4, (size_t)n_halo, hipMemcpyDeviceToDevice, s));
+            if (a2_own)
+                TGNN_CHECK_HIP(hipMemcpy2DAsync(a2_halo_dst + (size_t)n * c, (size_t)c * 4, sh->recv_buf + c, (size_t)rf * 4,
+                                                (size_t)c * 4, (size_t)n_halo, hipMemcpyDeviceToDevice, s));
+        }
+        return TGNN_OK;
+    }
+    // message sizes of the one-all-to-all schemes: the rows plus 4 sums rows per peer
+    int64_t shard_rows_out() const { return sh->n_send + 4 * (int64_t)sh->world; }
+    int64_t shard_rows_in() const { return n_halo + 4 * (int64_t)sh->world; }
+    float *slot(int k) const { return w.mid + (size_t)k * nr * c; }
+    const float *residual(int i) const { return i >= 2 ? slot(i - 2) : nullptr; }
+
+    // ---- the head: operand bounds, the fork, the edge weights, the final MLP's operands, the parameter packs ----------------
+    // [r6] the general schedule's head: no memset anywhere (a hipMemsetAsync is two fill kernels and ~10 us in front of the first
+    // launch) -- the scales kernel clears the words, among them the collision branch's fold counter; the first Linear's bound is
+    // taken on the side stream with the other two (nobody needs it before the final MLP)
+    int queue_head() {
+        if (plan.weights_done == WeightsDoneWord::SmallCtr) TGNN_CHECK_HIP(hipMemsetAsync(weights_done, 0, 4, s));
+        if (plan.scales == ScalesKernel::Lean || plan.scales == ScalesKernel::Full) {
+            const float *roots[kMaxDepth];
+            for (int i = 0; i < D; ++i) roots[i] = P.f(P.layer(i) + 6);
+            if (plan.scales == ScalesKernel::Lean)
+                launch_forward_scales(w.bounds, 2 * D + 95, roots, D, root_max, nullptr, 0, nullptr, s);
+            else
+                launch_forward_scales(w.bounds, 2 * D + 7, roots, D, root_max, P.f(P.fin(0)), (int64_t)c * (D + 1) * kFinalDims[0], dense_max,
+                                      s);   // (before the fork: both chains see the zeroed words)
+        }                                   // (ScalesKernel::Begin: tgnn_forward_begin's, on the side stream)
+        return TGNN_OK;
+    }
+    // [r6] tgnn_forward_resume picking up tgnn_forward_begin's work: `stream` has nothing to do in front of the first NNConv but wait
+    // for the preparation's last launches, so the edge weights go on IT, straight behind them (no cross-queue hand-over in front of
+    // them and none in front of the first NNConv: ~12 us each), and the collision chain is released first -- its first aggregate
+    // runs beside them instead of behind them.  Otherwise the edge weights go on the side stream when there is one: it idles until
+    // the init MLP is through, and these ~30 us (serial 3-layer MLP per (layer, type) + the bf16 image) then leave the critical chain
+    int fork_side() {
+        if (plan.small_pre_used) {
+            // (everything in front of the persistent kernel is on `stream`)
+        } else if (plan.weights_on_main) {
+            TGNN_CHECK_HIP(hipEventRecord(ev[0], s));            // middle[0] (the head's event, waited for above) and the layout are complete
+            TGNN_CHECK_HIP(hipStreamWaitEvent(s2, ev[0], 0));
+        } else if (plan.weights_on_side) {
+            TGNN_CHECK_HIP(hipEventRecord(ev[kEvFork], s));     // everything the caller queued on `stream` so far
+            TGNN_CHECK_HIP(hipStreamWaitEvent(s2, ev[kEvFork], 0));
+            sw = s2;
+        }
+        return TGNN_OK;
+    }
+    // ---- K1: per-type NNConv matrices of all layers, one launch: the edge MLP of every (layer, type) and, for the matrix-core
+    //      NNConv, its operand images (root = pseudo-type T)
+    // (first on the side stream: the layer loop waits for these, the final MLP's bounds and images have the whole loop's time)
+    // [r6] weights_queued: tgnn_forward_begin_weights has queued exactly this launch behind the preparation already
+    int queue_edge_weights() {
+        if (plan.queue_weights) {
+            const EdgeMlpTable em(P, D);
+            prof.begin(0);
+            launch_edge_weight_table_batched(adj_edge_attr, graph->type_rep_edge, T, fe, em.layers, D, c, w.wtab, plan.tiled ? em.roots : nullptr,
+                                             plan.tiled ? w.wimg : nullptr, sw, weights_done, root_max, plan.eg ? kEgImageScale : 1.0f);
+            prof.end();
+        }
+        // [r6] the layer loop waits for the edge weights alone: the event sits in front of the final MLP's bounds and images (they
+        // are joined with the collision chain, which the last merge waits for) -- 12 us of idle main stream in front of the first NNConv
+        if (plan.lean_head && sw != s) {
+            TGNN_CHECK_HIP(hipEventRecord(ev[kEvWeights], s2));
+            weights_recorded = true;
+        }
+        return TGNN_OK;
+    }
+    int queue_final_operands() {
+        const int fin_dims[5] = {c * (D + 1), kFinalDims[0], kFinalDims[1], kFinalDims[2], c};   // in / out widths of the final MLP's layers
+        if (plan.final_operands == FinalOperands::Begin) {
+            dimg_ok[0] = dimg_ok[1] = dimg_ok[2] = dimg_ok[3] = c == 32 && n >= kDenseRowsKernelMin;   // (built by tgnn_forward_begin)
+        } else if (plan.final_operands == FinalOperands::Lean) {
+            // bounds of the three Linears' weights (+ of layers 1, 2's inputs from their BatchNorm parameters), then the three operand
+            // images in ONE launch
+            bool ok = false;
+            TGNN_TRY(forward_head_bounds_images(dims, P, w, n, n_total, sw, &ok));
+            dimg_ok[0] = dimg_ok[1] = dimg_ok[2] = dimg_ok[3] = ok;
+        } else if (plan.final_operands == FinalOperands::Split) {
+            // the final MLP's layers 1 and 2 (256 -> 128 -> 64): weights' bounds and, from the BatchNorm parameters alone, their inputs'
+            const float *bw[2], *bg[2], *bb[2];
+            int64_t bwn[2];
+            int bf[2];
+            unsigned *bwm[2], *bam[2];
+            for (int l = 1; l <= 2; ++l) {
+                const BnPtrs bp = P.bn(P.fin(l - 1) + 2);
+                bw[l - 1] = P.f(P.fin(l));
+                bwn[l - 1] = (int64_t)fin_dims[l] * fin_dims[l + 1];
+                bg[l - 1] = bp.gamma; bb[l - 1] = bp.beta; bf[l - 1] = fin_dims[l];
+                bwm[l - 1] = w.bounds + 2 * D + 2 + 2 * (l - 1);
+                bam[l - 1] = w.bounds + 2 * D + 3 + 2 * (l - 1);
+            }
+            launch_dense_bounds(2, bw, bwn, bg, bb, bf, bwm, bam, n_total, sw);   // (side stream: off the critical chain; the final MLP is behind every join)
+            // the three Linears' operand images for the rows-per-wave kernel (dense.hip), behind their weights' bounds on the same stream
+            for (int l = 0; l < 3; ++l) {
+                const unsigned *wm = l == 0 ? dense_max : w.bounds + 2 * D + 2 + 2 * (l - 1);
+                dimg_ok[l] = c == 32 && n >= kDenseRowsKernelMin && dense_f16_image_build(P.f(P.fin(l)), fin_dims[l], fin_dims[l + 1], wm, w.dimg[l], sw) == TGNN_OK;
+            }
+        }
+        return TGNN_OK;
+    }
+    // the persistent kernels' parameter packs, then the edge-weight event where queue_edge_weights has not recorded it yet
+    int queue_packs() {
+        if (plan.small_teams && !plan.small_pre_used) launch_small_pack(P, D, w.small_pack, w.small_ctr, s);   // on the main stream: it has nothing else to do yet
+        // (parameter vectors + GIN images of the layers; the same launch clears the barrier counter and the tagged partial rows)
+        if (plan.mid_k) launch_small_pack(P, D, w.small_pack, w.small_ctr, s, plan.tail_k > 0 || plan.mid_init, w.mid_part, mid_part_doubles() * sizeof(double), plan.tail_k > 0 ? dense_max : nullptr,
+                                          sw != s ? sw : nullptr);   // (the final MLP's images: side stream, joined behind the layer loop)
+        if (sw != s && !weights_recorded) TGNN_CHECK_HIP(hipEventRecord(ev[kEvWeights], s2));
+        return TGNN_OK;
+    }
+
+    // ---- small layouts: init MLP, the layers and the final MLP as one persistent kernel behind the pre-pass -------------------
+    int run_small() {
+        if (sw != s && !weights_done) TGNN_CHECK_HIP(hipStreamWaitEvent(s, ev[kEvWeights], 0));
+        TGNN_TRY(launch_forward_small(dims, P, x, probs, w.mid, w.a2[0], w.a2[1], w.wimg, w.small_pack, graph, w.small_part,
+                                      w.small_part_wide, w.small_runstat, w.small_ctr, weights_done, weights_target, n,
+                                      update_running, eps, momentum, s));
+        return TGNN_OK;
+    }
+
+    // ---- K10: init MLP  (TilinGNN.py:54)
+    // [r6] three launches that recompute from x instead of five that store (init_mlp.hip); the launch-per-op form stays for what
+    // keeps the activations (training), all-reduces the statistics (shards) or normalises with running statistics
+    int init_mlp() {
+        // (a layout that turns out not to take the fp16-pair path -- more than 16 edge types, an in-degree above 2 048 -- runs its head
+        //  again, the launch-per-op way; the init MLP's running statistics were updated by tgnn_forward_begin already)
+        BnPtrs ibn0 = P.bn(P.init(0) + 2), ibn1 = P.bn(P.init(1) + 2);
+        if (plan.init_stats_written) {
+            ibn0.rm = ibn0.rv = ibn1.rm = ibn1.rv = nullptr;
+            ibn0.nbt = ibn1.nbt = nullptr;
+        }
+        if (plan.head_used) {
+        } else if (plan.init_fused) {
+            prof.begin(1);
+            TGNN_TRY(forward_head_init(dims, P, x, w, n, plan.init_stats_written ? 0 : update_running, slot_max, s));
+            prof.end();
+        } else if (!plan.mid_init) {
+            prof.begin(1);
+            TGNN_TRY(tgnn_dense_act_fwd(x, fx, 32, nullptr, P.f(P.init(0)), P.f(P.init(0) + 1), n, fx, c, TGNN_ACT_LEAKY_RELU,
+                                        w.t0, c, w.partf, &np1, s));
+            prof.end();
+            TGNN_TRY(finalize1(w.partf, np1, c, ibn0, w.stat_i[0]));
+            prof.begin(1);
+            TGNN_TRY(tgnn_dense_act_fwd(w.t0, c, 32, w.stat_i[0], P.f(P.init(1)), P.f(P.init(1) + 1), n, c, c,
+                                        TGNN_ACT_LEAKY_RELU, w.a1, c, w.partf, &np1, s));
+            prof.end();
+            TGNN_TRY(finalize1(w.partf, np1, c, ibn1, w.stat_i[1]));
+            prof.begin(1);
+            launch_bn_apply(w.a1, c, w.stat_i[1], n, c, w.mid, c, slot_max, s);   // middle[0] = brch_1 = brch_2 (:55,58)
+            prof.end();
+        }
+        TGNN_TRY(exchange(0, nullptr, nullptr));
+        if (plan.f16 && n_halo > 0) launch_absmax(w.mid + (size_t)n * c, n_halo * c, slot_max, s);   // (the halo rows of middle[0])
+        return TGNN_OK;
+    }
+    int zero_fold_counter() {
+        if (plan.zero_fold_ctr) TGNN_CHECK_HIP(hipMemsetAsync(fold_ctr, 0, 17 * sizeof(unsigned), s));   // (before ev[0]: the side chain sees it)
+        return TGNN_OK;
+    }
+
+    // ---- mid-size layouts: the D layers as one persistent kernel, the final MLP as one more where it is eligible ---------------
+    // (*done: the tail kernel has written the probabilities; else the general schedule's final MLP follows)
+    int run_mid(bool *done) {
+        double *const tail_zero[2] = {w.partf, w.small_part_wide};   // the tail kernel's tagged rows: cleared by the layer loop's blocks
+        if (sw != s && !weights_done) TGNN_CHECK_HIP(hipStreamWaitEvent(s, ev[kEvWeights], 0));   // (the images of the side stream)
+        TGNN_TRY(launch_forward_mid(dims, P, w.mid, w.a1, w.a2[0], w.a2[1], w.wimg, w.small_pack, graph, w.mid_part, w.small_runstat,
+                                    w.small_ctr, w.bounds, n, plan.mid_k, plan.mid_blocks, update_running, eps, momentum, s, weights_done,
+                                    weights_target, plan.tail_k ? tail_zero : nullptr, mid_tail_part_doubles(), plan.mid_init ? x : nullptr));
+        // (the final MLP reads the side stream's bounds and operand images: behind the layer loop, where the wait costs nothing)
+        if (sw != s && weights_done) TGNN_CHECK_HIP(hipStreamWaitEvent(s, ev[kEvWeights], 0));
+        *done = plan.tail_k != 0;
+        if (plan.tail_k)
+            TGNN_TRY(launch_forward_tail(dims, P, w.mid, w.small_pack, probs, w.partf, w.small_part_wide, slot_max, dense_max, n, plan.tail_k,
+                                         plan.tail_blocks, update_running, eps, momentum, s, graph->nn_mid_verdict));
+        return TGNN_OK;
+    }
+
+    // ---- main loop (TilinGNN.py:59-71) -------------------------------------------------------------------------------------
+    // the side chain is released behind middle[0]; the main chain waits for the side stream's edge weights
+    int release_side_chain() {
+        if (s2 && !plan.weights_on_main) {
+            TGNN_CHECK_HIP(hipEventRecord(ev[0], s));            // middle[0] is complete
+            TGNN_CHECK_HIP(hipStreamWaitEvent(s2, ev[0], 0));
+            if (sw != s) TGNN_CHECK_HIP(hipStreamWaitEvent(s, ev[kEvWeights], 0));
+        }
+        return TGNN_OK;
+    }
+    // training forward: layer i's own buffers (kernels already queued keep theirs)
+    void bind_layer_buffers(int i) {
+        if (!keep) return;
+        w.a1 = keep->a1 + (size_t)i * n * c;
+        w.a2[i & 1] = keep->a2 + (size_t)i * n * c;
+        w.t0 = keep->u + (size_t)i * n * c;
+        w.stat1 = keep->stat1 + (size_t)i * 4 * c;
+        w.stat2[i & 1] = keep->stat2 + (size_t)i * 4 * c;
+    }
+    // CollConv (:63): input = BN_{i-1}(a2_{i-1}) folded into the gather; layer 0 reads middle[0].
+    // fold_fin2: the collision branch's BatchNorm record by the LAST block of the GIN MLP kernel (gin.hip: GinFin) instead of a
+    // 1-block finalize launch behind it -- 20 launches less on that chain (measured by leaving them out: 0.07 ms of 1.95).  Single
+    // device, width 32, batch statistics.
+    int gin_layer(int i, hipStream_t gs) {
+        const int b = P.layer(i);
+        const float *gin_in = i == 0 ? w.mid : w.a2[(i - 1) & 1];
+        const float *gin_stat = i == 0 ? nullptr : w.stat2[(i - 1) & 1];
+        if (plan.fold_fin2) {
+            GinFin fin{};
+            fin.counter = fold_ctr;
+            fin.job = bn_job(nullptr, 0, P.bn(b + 20), w.stat2[i & 1]);
+            fin.n_total = n;
+            fin.eps = eps;
+            fin.momentum = momentum;
+            prof.begin(3);
+            const int rc = gin32_fwd_folded(gin_in, c, gin_stat, graph->col_rowptr, graph->col_src, P.f(b + 13), P.f(b + 14), P.f(b + 15),
+                                            P.f(b + 16), P.f(b + 17), P.f(b + 18), P.f(b + 19), n, TGNN_ACT_LEAKY_RELU, w.a2[i & 1],
+                                            w.t0, w.part2, &np2, fin, gs, keep != nullptr);
+            prof.end();
+            return rc;                                         // (TGNN_ERR_UNSUPPORTED: the workspace is aligned, cannot happen)
+        }
+        prof.begin(3);
+        if (keep && c != 32) {
+            // training at width 64: the generic kernel (the one inference runs at this width) also stores the aggregate, keep->u
+            TGNN_TRY(gin_generic_fwd_keep(gin_in, c, gin_stat, graph->col_rowptr, graph->col_src, P.f(b + 13), P.f(b + 14),
+                                          P.f(b + 15), P.f(b + 16), P.f(b + 17), P.f(b + 18), P.f(b + 19), n, c, TGNN_ACT_LEAKY_RELU,
+                                          w.a2[i & 1], w.t0, w.part2, &np2, gs));
+            prof.end();
+            return TGNN_OK;
+        }
+        TGNN_TRY(tgnn_gin_fwd(gin_in, c, gin_stat, graph->col_rowptr, graph->col_src, P.f(b + 13), P.f(b + 14),
+                              P.f(b + 15), P.f(b + 16), P.f(b + 17), P.f(b + 18), P.f(b + 19), n, c,
+                              TGNN_ACT_LEAKY_RELU, w.a2[i & 1], w.t0, w.part2, &np2, gs));
+        prof.end();
+        return TGNN_OK;
+    }
+    // the GIN MLP behind an aggregate that ran on the side stream (sharded: the MLP finds no CU beside an NNConv block)
+    int gin_mlp_on_main(int i) {
+        const int b = P.layer(i);
+        return launch_gin32_mlp(w.t0, P.f(b + 14), P.f(b + 15), P.f(b + 16), P.f(b + 17), P.f(b + 18), P.f(b + 19), n, TGNN_ACT_LEAKY_RELU,
+                                w.a2[i & 1], w.part2, &np2, s, nullptr, true);
+    }
+    // single device: GIN_i and, unless its kernel leaves the record itself, its 1-block finalize -- all on `st`
+    int collision_layer(int i, hipStream_t st) {
+        TGNN_TRY(gin_layer(i, st));
+        if (!plan.fold_fin2) finalize_collision(i, st);
+        return TGNN_OK;
+    }
+    // ---- collision chain, layer i, on the side stream: a2[i & 1] / stat2[i & 1] were last read by merge_{i-2}
+    int side_collision_layer(int i) {
+        const int b = P.layer(i);
+        if (plan.split) {
+            // split exchange: the whole collision branch of layer i -- GIN, then ITS OWN all-to-all (halo rows of a2 + the
+            // BatchNorm sums, 32 floats per row) and the statistics -- on the side stream: it needs nothing of the adjacency
+            // branch, so the chain runs ahead of the NNConv / merge chain as it does on a single device, held back only by
+            // the two-deep buffers (a2[i & 1] / stat2[i & 1] were last read by merge_{i-2})
+            if (i >= 2) TGNN_CHECK_HIP(hipStreamWaitEvent(s2, ev[1 + kMaxDepth + i - 2], 0));
+            TGNN_TRY(gin_layer(i, s2));
+            if (i + 1 < D) {
+                BnJob j2 = bn_job(w.part2, np2, P.bn(b + 20), w.stat2[i & 1]);
+                j2.sums = sh->sum_buf + 64;
+                const int64_t n_out = shard_rows_out(), n_in = shard_rows_in();
+                float *sb2 = sh->send_buf + (size_t)n_out * c, *rb2 = sh->recv_buf + (size_t)n_in * c;
+                launch_shard_pack1(w.a2[i & 1], sh->send_idx_fused, n_out, j2, sb2, s2);
+                TGNN_TRY(alltoall(sb2, rb2, c, 4, s2));
+                launch_shard_unpack1(rb2, sh->recv_idx_fused, n_in, n, w.a2[i & 1], j2, sh->world, sh->rank, n_total, eps,
+                                     momentum, s2);
+            }
+        } else if (sh) {
+            // (sharded: the halo rows and the statistics GIN_i reads arrive with the exchange of layer i-1, so the chain cannot run
+            //  ahead; only the HBM-bound neighbourhood sum goes beside the merge / NNConv -- the MLP, which finds no CU beside an
+            //  NNConv block, follows on the main stream: 52 us beside the NNConv against 19 us behind it, measured)
+            if (i >= 1) TGNN_CHECK_HIP(hipStreamWaitEvent(s2, ev[1 + kMaxDepth + i - 1], 0));
+            const float *gin_in = i == 0 ? w.mid : w.a2[(i - 1) & 1];
+            TGNN_TRY(tgnn_gin_aggregate(gin_in, c, i == 0 ? nullptr : w.stat2[(i - 1) & 1], graph->col_rowptr, graph->col_src,
+                                        P.f(b + 13), n, c, w.t0, s2));
+        } else {
+            if (i >= 2) TGNN_CHECK_HIP(hipStreamWaitEvent(s2, ev[1 + kMaxDepth + i - 2], 0));
+            TGNN_TRY(collision_layer(i, s2));
+        }
+        TGNN_CHECK_HIP(hipEventRecord(ev[1 + i], s2));
+        return TGNN_OK;
+    }
+    // GraphConv (:62): NNConv mean + LeakyReLU; BN statistics emitted as partials
+    // [r6] sharded, split exchange: the pack of the adjacency branch's message inside the NNConv (nnconv_eg.hip: SHARD)
+    bool pack_in_nnconv(int i) const { return plan.pack_in_nnconv && i + 1 < D; }
+    int adjacency_nnconv(int i) {
+        const int b = P.layer(i);
+        const float *h1 = slot(i);
+        prof.begin(2);
+        if (plan.eg) {
+            EgShardPack pk{};
+            if (pack_in_nnconv(i))
+                pk = EgShardPack{sh->send_row_ptr, sh->send_row_slot, sh->send_buf, sh->send_idx_fused, shard_rows_out(),
+                                 sh->sum_buf, w.bounds + 2 * D + 27, w.small_part_wide + (size_t)4 * 16 * 512};
+            TGNN_TRY(launch_nnconv_eg(h1, graph->nn_tile_grp_ptr, graph->nn_grp, w.wimg + (size_t)i * (T + 1) * kWtTypeF16, T,
+                                      P.f(b + 7), n, TGNN_ACT_LEAKY_RELU, w.a1, w.part1, &np1, s, slot_max + i, root_max + i,
+                                      prof.stamps ? prof.stamps + 2 * i : nullptr, pack_in_nnconv(i) ? &pk : nullptr));
+        } else if (plan.tiled) {
+            TGNN_TRY(launch_nnconv_cols(h1, c, graph->nn_tile_col_ptr, graph->nn_col_meta, graph->nn_col_src,
+                                        w.wimg + (size_t)i * (T + 1) * (plan.f16 ? kWtTypeF16 : kWtType), T, P.f(b + 7), n,
+                                        TGNN_ACT_LEAKY_RELU, w.a1, w.part1, &np1, s, plan.f16 ? slot_max + i : nullptr,
+                                        plan.f16 ? root_max + i : nullptr, graph->nn_max_in_degree,
+                                        prof.stamps ? prof.stamps + 2 * i : nullptr));
+        } else {
+            TGNN_TRY(tgnn_nnconv_mean_fwd(h1, c, graph->adj_rowptr, graph->adj_src, graph->adj_type,
+                                      w.wtab + (size_t)i * T * c * c, T, P.f(b + 6), P.f(b + 7), n, c,
+                                      TGNN_ACT_LEAKY_RELU, w.a1, w.part1, &np1, s));
+        }
+        prof.end();
+        return TGNN_OK;
+    }
+
+    // ---- join of the two branches and merge (:64-71): middle[i+1] = BN1(a1) * BN2(a2) (+ middle[i-2]); one per scheme ----------
+    // Single device.  Few partial rows: merge derives the first BatchNorm's record from them itself -- one launch less on the
+    // critical chain of a launch-latency-bound forward.  (With the 256 rows of a 100k-node layout the repeated reduction costs
+    // every merge block more than the separate 1-block finalize: measured.)
+    // (round 2: with 1024-thread blocks -- one batch of independent loads per thread -- the repeated reduction pays at every
+    //  size: the launch it replaces sits on the critical NNConv -> merge chain.  TGNN_BN_MAX_PARTIALS rows at most.)
+    int merge_single(int i) {
+        const int b = P.layer(i);
+        const bool fused_bn1 = plan.fused_bn1_ok && np1 <= TGNN_BN_MAX_PARTIALS;
+        if (s2) {
+            if (!fused_bn1) {
+                BnJobs j1{};
+                j1.job[0] = bn_job(w.part1, np1, P.bn(b + 8), w.stat1);
+                launch_bn_finalize(j1, 1, fin_mode, c, n, eps, momentum, s);
+            }
+            TGNN_CHECK_HIP(hipStreamWaitEvent(s, ev[1 + i], 0));
+        } else {
+            TGNN_TRY(gin_layer(i, s));
+            BnJobs jobs{};
+            int nj = 0;
+            if (!fused_bn1) jobs.job[nj++] = bn_job(w.part1, np1, P.bn(b + 8), w.stat1);
+            if (!plan.fold_fin2) jobs.job[nj++] = bn_job(w.part2, np2, P.bn(b + 20), w.stat2[i & 1]);
+            TGNN_TRY(finalize_jobs(jobs, nj, c));
+        }
+        prof.begin(5);
+        if (fused_bn1) {
+            launch_merge_bn1(w.a1, bn_job(w.part1, np1, P.bn(b + 8), w.stat1), n, eps, momentum, w.a2[i & 1],
+                             w.stat2[i & 1], residual(i), n, slot(i + 1), s, plan.f16 ? slot_max + i + 1 : nullptr);
+        } else if (plan.f16) {
+            launch_merge(w.a1, w.stat1, w.a2[i & 1], w.stat2[i & 1], residual(i), n, c, slot(i + 1), nullptr, slot_max + i + 1, s);
+        } else {
+            TGNN_TRY(tgnn_merge_fwd(w.a1, w.stat1, w.a2[i & 1], w.stat2[i & 1], residual(i), n, c, slot(i + 1), nullptr, s));
+        }
+        prof.end();
+        if (s2) TGNN_CHECK_HIP(hipEventRecord(ev[1 + kMaxDepth + i], s));   // (a2[i & 1] / stat2[i & 1] are free for GIN_{i+2})
+        return TGNN_OK;
+    }
+    // Sharded, all-reduce + all-to-all: both BatchNorms' sums in one all-reduce, the merge over the own rows, then the halo
+    // exchange of the new slot and of a2.  Also the LAST layer of the two one-all-to-all schemes (nobody reads its halo rows).
+    int merge_sharded_allreduce(int i) {
+        const int b = P.layer(i);
+        if (s2) {
+            TGNN_CHECK_HIP(hipStreamWaitEvent(s, ev[1 + i], 0));
+            if (!plan.split) TGNN_TRY(gin_mlp_on_main(i));
+        } else {
+            TGNN_TRY(gin_layer(i, s));
+        }
+        BnJobs jobs{};
+        jobs.job[0] = bn_job(w.part1, np1, P.bn(b + 8), w.stat1);
+        jobs.job[1] = bn_job(w.part2, np2, P.bn(b + 20), w.stat2[i & 1]);
+        TGNN_TRY(finalize_jobs(jobs, 2, c));
+        prof.begin(5);
+        if (plan.f16)
+            launch_merge(w.a1, w.stat1, w.a2[i & 1], w.stat2[i & 1], residual(i), n, c, slot(i + 1), nullptr, slot_max + i + 1, s);
+        else
+            TGNN_TRY(tgnn_merge_fwd(w.a1, w.stat1, w.a2[i & 1], w.stat2[i & 1], residual(i), n, c, slot(i + 1), nullptr, s));
+        prof.end();
+        if (i + 1 < D) TGNN_TRY(exchange(i + 1, w.a2[i & 1], w.a2[i & 1]));
+        if (s2) TGNN_CHECK_HIP(hipEventRecord(ev[1 + kMaxDepth + i], s));     // (the next GIN also reads the halo rows)
+        return TGNN_OK;
+    }
+    // Sharded, fused (one all-to-all per layer instead of all-reduce + all-to-all, see tgnn_shard in tgnn.h): local sums -> ONE
+    // all-to-all (raw halo rows of both branches + the sums) -> the sums of all shards added in rank order -> statistics -> merge
+    // of the own AND the halo rows.  One chain: with a side stream these tables run the split scheme (plan.split).
+    int merge_sharded_fused(int i) {
+        const int b = P.layer(i);
+        TGNN_TRY(gin_layer(i, s));
+        BnJobs jobs{};
+        jobs.job[0] = bn_job(w.part1, np1, P.bn(b + 8), w.stat1);
+        jobs.job[1] = bn_job(w.part2, np2, P.bn(b + 20), w.stat2[i & 1]);
+        double *own = sh->sum_buf;
+        jobs.job[0].sums = own;
+        jobs.job[1].sums = own + 64;
+        const int64_t n_out = shard_rows_out(), n_in = shard_rows_in();
+        launch_shard_pack_sums(w.a1, w.a2[i & 1], sh->send_idx_fused, n_out, jobs, sh->send_buf, s);
+        TGNN_TRY(alltoall(sh->send_buf, sh->recv_buf, 2 * c, 4, s));
+        launch_shard_unpack_finalize(sh->recv_buf, sh->recv_idx_fused, n_in, n, w.a1, w.a2[i & 1], jobs, sh->world,
+                                     sh->rank, n_total, eps, momentum, s);
+        if (plan.f16)
+            launch_merge(w.a1, w.stat1, w.a2[i & 1], w.stat2[i & 1], residual(i), nr, c, slot(i + 1), nullptr, slot_max + i + 1, s);
+        else
+            TGNN_TRY(tgnn_merge_fwd(w.a1, w.stat1, w.a2[i & 1], w.stat2[i & 1], residual(i), nr, c, slot(i + 1), nullptr, s));
+        return TGNN_OK;
+    }
+    // Sharded, split exchange: this chain carries the adjacency branch only (rows of a1 + its BatchNorm sums); the collision
+    // branch's half arrived (or is arriving) on the side stream
+    int merge_sharded_split(int i) {
+        BnJob j1 = bn_job(w.part1, np1, P.bn(P.layer(i) + 8), w.stat1);
+        j1.sums = sh->sum_buf;
+        const int64_t n_out = shard_rows_out(), n_in = shard_rows_in();
+        if (!pack_in_nnconv(i)) launch_shard_pack1(w.a1, sh->send_idx_fused, n_out, j1, sh->send_buf, s);
+        TGNN_TRY(alltoall(sh->send_buf, sh->recv_buf, c, 4, s));
+        TGNN_CHECK_HIP(hipStreamWaitEvent(s, ev[1 + i], 0));
+        // [r6] unpack + merge as one launch: the record from the shards' sums in every block, the halo rows of a1 out of the message
+        launch_shard_unpack1_merge(sh->recv_buf, sh->recv_idx_fused, n_in, n, w.a1, j1, sh->world, sh->rank, n_total, eps, momentum,
+                                   w.a2[i & 1], w.stat2[i & 1], residual(i), nr, slot(i + 1), plan.f16 ? slot_max + i + 1 : nullptr, s);
+        TGNN_CHECK_HIP(hipEventRecord(ev[1 + kMaxDepth + i], s));       // (a2[i & 1] / stat2[i & 1] are free for GIN_{i+2})
+        return TGNN_OK;
+    }
+    int layer(int i) {
+        bind_layer_buffers(i);
+        // [r6] tgnn_forward_resume, layer 0: the NNConv's launch goes out BEFORE the collision chain's -- the host is what the first
+        // layer waits for behind a just-prepared layout, and the adjacency chain is the longer one
+        const bool nn_first = plan.nn_first && i == 0;
+        if (s2 && !nn_first) TGNN_TRY(side_collision_layer(i));
+        TGNN_TRY(adjacency_nnconv(i));
+        if (nn_first) {
+            TGNN_TRY(collision_layer(i, s2));
+            TGNN_CHECK_HIP(hipEventRecord(ev[1 + i], s2));
+        }
+        if (plan.split && i + 1 < D) return merge_sharded_split(i);
+        if (plan.fused_shard && i + 1 < D) return merge_sharded_fused(i);
+        return sh ? merge_sharded_allreduce(i) : merge_single(i);
+    }
+
+    // ---- K11: final MLP over the concatenation (TilinGNN.py:74-76); K block kb = middle[kb]
+    // [r6] fold_final: the final MLP's BatchNorm records by their producers (bn_fold_two_level in the rows / resident kernels: the same
+    // bits) instead of a 7 us bn_finalize launch behind each; 17 counter words per layer behind the collision branch's, cleared by the
+    // scales kernel (bit 2 of tgnn_set_lean_head, OFF by default: measured, every producer grew by the 6 - 8 us its finalize launch took
+    // -- all of a dense kernel's blocks finish together, so both levels of the fold are serial latency behind the last one, unlike in
+    // the collision MLP, whose row groups finish at different times: profiles/r06_tail_fold.txt)
+    int final_mlp() {
+        const int cat_dim = c * (D + 1);
+        float *fbuf[4] = {w.f1, w.f2, w.f3, w.f4};
+        int fdim[5] = {cat_dim, kFinalDims[0], kFinalDims[1], kFinalDims[2], c};
+        for (int l = 0; l < 4; ++l) {
+            const int pi = P.fin(l);
+            GinFin ff{};
+            bool folded = false;
+            if (plan.fold_final) {
+                ff.counter = w.bounds + 2 * D + 27 + 17 * l;
+                ff.job = bn_job(nullptr, 0, P.bn(pi + 2), w.stat_f[l]);
+                ff.n_total = n;
+                ff.eps = eps;
+                ff.momentum = momentum;
+            }
+            double *fold_rows = w.small_part_wide + (size_t)l * 16 * 512;
+            prof.begin(6);
+            if (l == 0) {
+                if (plan.f16)
+                    TGNN_TRY(dense_act_slots_bounded(w.mid, c, (int64_t)nr * c, P.f(pi), P.f(pi + 1), n, cat_dim, fdim[1],
+                                                     TGNN_ACT_LEAKY_RELU, fbuf[0], fdim[1], w.partf, &np1, slot_max, D + 1, dense_max, s,
+                                                     dimg_ok[0] ? w.dimg[0] : nullptr, plan.fold_final ? &ff : nullptr, fold_rows, &folded));
+                else
+                    TGNN_TRY(tgnn_dense_act_slots_fwd(w.mid, c, (int64_t)nr * c, nullptr, P.f(pi), P.f(pi + 1), n, cat_dim, fdim[1],
+                                                      TGNN_ACT_LEAKY_RELU, fbuf[0], fdim[1], w.partf, &np1, s));
+            } else if (plan.f16 && (l <= 2 || dimg_ok[l])) {   // fp16 pairs: the input's bound follows from the producer's BatchNorm parameters (dense_bounds_kernel)
+                TGNN_TRY(dense_act_bounded(fbuf[l - 1], fdim[l], 32, w.stat_f[l - 1], P.f(pi), P.f(pi + 1), n, fdim[l], fdim[l + 1],
+                                           TGNN_ACT_LEAKY_RELU, fbuf[l], fdim[l + 1], w.partf, &np1, final_bound_word(w, D, l) + 1, 1,
+                                           final_bound_word(w, D, l), s, dimg_ok[l] ? w.dimg[l] : nullptr, plan.fold_final ? &ff : nullptr,
+                                           fold_rows, &folded));
+            } else {
+                TGNN_TRY(tgnn_dense_act_fwd(fbuf[l - 1], fdim[l], 32, w.stat_f[l - 1], P.f(pi), P.f(pi + 1), n, fdim[l],
+                                            fdim[l + 1], TGNN_ACT_LEAKY_RELU, fbuf[l], fdim[l + 1], w.partf, &np1, s));
+            }
+            prof.end();
+            if (!folded) TGNN_TRY(finalize1(w.partf, np1, fdim[l + 1], P.bn(pi + 2), w.stat_f[l]));
+        }
+        prof.begin(6);
+        TGNN_TRY(tgnn_dense_act_fwd(fbuf[3], c, 32, w.stat_f[3], P.f(P.last()), P.f(P.last() + 1), n, c, dims->output_dim,
+                                    TGNN_ACT_SIGMOID, probs, dims->output_dim, nullptr, nullptr, s));
+        prof.end();
+        return TGNN_OK;
+    }
+};
+
+// The entry point behind tgnn_forward, _resume, _train, _sharded, _many, _union (every layout outside a union launch), _profiled,
+// _stamped and _profiled_two_stream: argument checks, the facts, the plan (forward_plan.h), then the phases of the plan's path.
 static int forward_impl(const tgnn_model_dims *dims, const void *const *params_host, const float *x,
                         const float *adj_edge_attr, const tgnn_graph *graph, int32_t update_running,
                         int32_t use_running_stats, float *probs, void *ws, size_t ws_bytes, tgnn_stream_t stream,
@@ -340,16 +1026,11 @@ static int forward_impl(const tgnn_model_dims *dims, const void *const *params_h
     TGNN_CHECK_ARG(graph->adj_rowptr && graph->col_rowptr, "graph pointers");
     TGNN_CHECK_ARG(graph->n_types == 0 || (adj_edge_attr && graph->type_rep_edge && graph->adj_src && graph->adj_type),
                    "adjacency pointers");
-    const int np = tgnn_param_count(dims);
-    for (int i = 0; i < np; ++i)
-        if (!params_host[i]) {
-            set_error("tgnn_forward: params_host[%d] is null", i);
-            return TGNN_ERR_INVALID_ARG;
-        }
+    TGNN_TRY(check_params(dims, params_host, "tgnn_forward"));
     // ---- sharded mode (tgnn_forward_sharded): this device owns rows [0, n) of buffers that carry nr - n halo rows
     // of other shards behind them; BatchNorm statistics are summed over all shards, halo rows are exchanged once
     // per layer.  The collectives are the caller's (callbacks, enqueued on / ordered with `stream`).
-    const int64_t nr = sh ? sh->n_rows : n, n_total = sh ? sh->n_total : n, n_halo = nr - n;
+    const int64_t nr = sh ? sh->n_rows : n, n_total = sh ? sh->n_total : n;
     if (sh) {
         TGNN_CHECK_ARG(sh->n_own == n && nr >= n && n_total >= n, "shard row counts");
         TGNN_CHECK_ARG(!use_running_stats, "sharded forward runs in train mode");
@@ -358,13 +1039,11 @@ static int forward_impl(const tgnn_model_dims *dims, const void *const *params_h
                                      : (sh->allreduce_f64 && sh->alltoall_rows), "shard communicator / callbacks");
         TGNN_CHECK_ARG(sh->n_send == 0 || sh->send_idx, "send_idx");
     }
+    hipStream_t s = static_cast<hipStream_t>(stream);
     // a persistent kernel of an earlier call that gave up and whose failure nobody collected (forward_persist.h): loud, here
-    TGNN_TRY(spin_error_collect_stale(static_cast<hipStream_t>(stream)));
-    Workspace w = carve(*dims, n, nr, graph->n_types, ws, ws_bytes);
-    if (!ws || w.bytes > ws_bytes) {
-        set_error("tgnn_forward: workspace too small (%zu < %zu)", ws_bytes, w.bytes);
-        return TGNN_ERR_WORKSPACE;
-    }
+    TGNN_TRY(spin_error_collect_stale(s));
+    Workspace w;
+    TGNN_TRY(carve_checked(*dims, n, nr, graph->n_types, ws, ws_bytes, "tgnn_forward", &w));
     if (keep) {
         // training forward (tgnn_forward_train): what the backward reads lives in the caller's buffers instead of the
         // rotating workspace ones -- the same kernels, the same schedule, only the destinations differ
@@ -381,619 +1060,73 @@ static int forward_impl(const tgnn_model_dims *dims, const void *const *params_h
         w.f1 = keep->fin_a[0]; w.f2 = keep->fin_a[1]; w.f3 = keep->fin_a[2]; w.f4 = keep->fin_a[3];
         for (int l = 0; l < 4; ++l) w.stat_f[l] = keep->fin_stat[l];
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    bool weights_early = false;
-    bool small_pre = false;
-    {
-        int devp = 0;
-        if (hipGetDevice(&devp) == hipSuccess && devp >= 0 && devp < 64 && g_small_pre[devp].ws) {
-            small_pre = g_small_pre[devp].ws == ws && g_small_pre[devp].n == n && !head_done && !sh && !keep;
-            g_small_pre[devp].ws = nullptr;
-        }
-    }
-    if (head_done) {
-        int dev = 0;
-        TGNN_CHECK_HIP(hipGetDevice(&dev));
-        TGNN_CHECK_ARG(dev >= 0 && dev < 64 && g_head[dev].ev && g_head[dev].ws == ws && g_head[dev].n == n,
-                       "tgnn_forward_resume without a matching tgnn_forward_begin (same thread, device, workspace, node count)");
-        g_head[dev].ws = nullptr;
-        weights_early = g_head[dev].weights;
-        g_head[dev].weights = false;
-        TGNN_CHECK_HIP(hipStreamWaitEvent(s, g_head[dev].ev, 0));   // middle[0], the bounds, the final MLP's images: done long ago (the preparation ran meanwhile)
-    }
-    // Two-chain schedule: the collision branch is a chain of its own -- CollConv_i reads only CollConv_{i-1}
-    // (TilinGNN.py:63); the branches meet in the product of :64 only.  With a side stream the whole GIN chain runs
-    // free beside the NNConv chain and fills the GPU wherever the latter leaves it idle (1-block BN finalizes, the
-    // HBM-bound merge, kernel tails); it is held back only by the two-deep buffers it shares with merge.
-    hipStream_t s2 = (prof.on && !prof.two_stream) ? nullptr : static_cast<hipStream_t>(sh ? sh->side_stream : stream2);
-    if (s2 == s || (sh && dims->network_width != 32)) s2 = nullptr;
-    // Events of the two-chain schedule, per calling thread and device; created once, never destroyed.
-    // [0] init done, [1 + i] GIN_i done, [1 + kMaxDepth + i] merge_i done, then: fork at entry, edge weights done
-    constexpr int kEvPerDev = 3 + 2 * kMaxDepth, kEvFork = 1 + 2 * kMaxDepth, kEvWeights = 2 + 2 * kMaxDepth;
-    static thread_local hipEvent_t ev_cache[64][kEvPerDev] = {};
+    HandOver ho;
+    TGNN_TRY(consume_handover(ws, n, head_done, s, &ho));
+
+    // ---- facts: everything the decision reads, each switch read once
+    hipStream_t side = static_cast<hipStream_t>(sh ? sh->side_stream : stream2);
+    ForwardFacts f;
+    f.c = dims->network_width; f.D = dims->network_depth; f.fx = dims->node_features_dim; f.fe = dims->adj_edge_features_dim;
+    f.n = n; f.nr = nr; f.T = graph->n_types; f.max_in_degree = graph->nn_max_in_degree;
+    f.has_cols = graph->nn_tile_col_ptr != nullptr;
+    f.has_groups = graph->nn_tile_grp_ptr && graph->nn_grp;
+    f.has_mid_verdict = graph->nn_mid_verdict != nullptr;
+    f.sharded = sh != nullptr;
+    f.shard_fused_tables = sh && sh->send_idx_fused && sh->recv_idx_fused;
+    f.shard_send_rows = sh && sh->send_row_ptr && sh->send_row_slot;
+    f.world = sh ? sh->world : 0;
+    f.keep = keep != nullptr;
+    f.use_running_stats = use_running_stats != 0;
+    f.init_running_done = init_running_done;
+    f.profiled = prof.on; f.two_stream = prof.two_stream;
+    f.head_done = head_done;
+    f.distinct_side_stream = side && side != s;
+    f.small_pre_match = ho.small_pre_match;
+    f.weights_early = ho.weights_early;
+    f.edge_table_device_count_ok = edge_weight_table_device_count_ok(f.fe, f.c);
+    f.device_cus = device_cus();
+    f.split_f16 = g_split_f16.load(); f.nnconv_eg = g_nnconv_eg.load(); f.lean_head = g_lean_head.load(std::memory_order_relaxed);
+    f.mid_init_in_kernel = mid_init_in_kernel();
+
+    hipStream_t s2 = side_stream_used(f) ? side : nullptr;
     hipEvent_t *ev = nullptr;
-    if (s2) {
-        int dev = 0;
-        TGNN_CHECK_HIP(hipGetDevice(&dev));
-        TGNN_CHECK_ARG(dev >= 0 && dev < 64, "device index");
-        if (!ev_cache[dev][0])
-            for (int k = 0; k < kEvPerDev; ++k)
-                TGNN_CHECK_HIP(hipEventCreateWithFlags(&ev_cache[dev][k], hipEventDisableTiming));
-        ev = ev_cache[dev];
-    }
+    if (s2) TGNN_TRY(two_chain_events(&ev));
     prof.s = s;
-    const int c = dims->network_width, D = dims->network_depth, fx = dims->node_features_dim,
-              fe = dims->adj_edge_features_dim, T = graph->n_types;
-    const Params P{params_host, D};
-    const float eps = 1e-5f, momentum = 0.1f;  // torch.nn.BatchNorm1d defaults
-    const int fin_mode = use_running_stats ? 3 : 0;
-    int32_t np1 = 0, np2 = 0;
-
-    // BatchNorm statistics from the producers' partial rows.  Sharded: partials -> local sums (mode 1) -> all-reduce
-    // over the shards (caller's callback; both BatchNorms of a layer travel in one message) -> stat record (mode 2).
-    // the two collectives: RCCL calls of the library's own when the shard carries a communicator, else the caller's callbacks
-    auto allreduce = [&](double *buf, int64_t count, hipStream_t st) -> int {
-        if (sh->rccl_comm) return rccl_allreduce_f64(sh->rccl_comm, buf, count, st);
-        if (sh->allreduce_f64(sh->ctx, buf, count, st) != 0) {
-            set_error("tgnn_forward_sharded: the all-reduce callback failed");
-            return TGNN_ERR_INVALID_ARG;
-        }
-        return TGNN_OK;
-    };
-    auto alltoall = [&](const float *send, float *recv, int row_floats, int extra_rows, hipStream_t st) -> int {
-        if (sh->rccl_comm) {
-            void *comm = (st != s && sh->rccl_comm_side) ? sh->rccl_comm_side : sh->rccl_comm;
-            return rccl_alltoall_rows(comm, send, recv, sh->send_counts, sh->recv_counts, sh->world, row_floats, extra_rows, st);
-        }
-        if (sh->alltoall_rows(sh->ctx, send, recv, row_floats, extra_rows, st) != 0) {
-            set_error("tgnn_forward_sharded: the all-to-all callback failed");
-            return TGNN_ERR_INVALID_ARG;
-        }
-        return TGNN_OK;
-    };
-    auto finalize_jobs = [&](BnJobs jobs, int nj, int f) -> int {
-        if (nj == 0) return TGNN_OK;
-        if (!sh) {
-            prof.begin(4);
-            launch_bn_finalize(jobs, nj, fin_mode, f, n, eps, momentum, s);
-            prof.end();
-            return TGNN_OK;
-        }
-        for (int j = 0; j < nj; ++j) jobs.job[j].sums = sh->sum_buf + (size_t)j * 2 * f;
-        launch_bn_finalize(jobs, nj, 1, f, n_total, eps, momentum, s);
-        TGNN_TRY(allreduce(sh->sum_buf, (int64_t)nj * 2 * f, s));
-        launch_bn_finalize(jobs, nj, 2, f, n_total, eps, momentum, s);
-        return TGNN_OK;
-    };
-    auto finalize1 = [&](double *part, int nparts, int f, const BnPtrs &b, float *stat) -> int {
-        BnJobs jobs{};
-        jobs.job[0] = BnJob{part, nparts, nullptr, b.gamma, b.beta, (update_running || use_running_stats) ? b.rm : nullptr,
-                            (update_running || use_running_stats) ? b.rv : nullptr,
-                            (update_running && !use_running_stats) ? b.nbt : nullptr, stat};
-        return finalize_jobs(jobs, 1, f);
-    };
-    // Halo exchange: the rows other shards need (send_idx) of slot `slot` of the skip buffer and, from layer 1 on,
-    // of the collision branch's pre-BN activations travel in ONE all-to-all (64 floats per row) and land behind the
-    // owned rows.
-    auto exchange = [&](int slot, const float *a2_own, float *a2_halo_dst) -> int {
-        if (!sh) return TGNN_OK;
-        const int rf = a2_own ? 2 * c : c;                     // floats per exchanged row
-        float *slot_rows = w.mid + (size_t)slot * nr * c;
-        if (sh->n_send > 0) {
-            TGNN_TRY(tgnn_rows_gather(slot_rows, c, sh->send_idx, sh->n_send, c, sh->send_buf, rf, s));
-            if (a2_own) TGNN_TRY(tgnn_rows_gather(a2_own, c, sh->send_idx, sh->n_send, c, sh->send_buf + c, rf, s));
-        }
-        TGNN_TRY(alltoall(sh->send_buf, sh->recv_buf, rf, 0, s));
-        if (n_halo > 0) {
-            TGNN_CHECK_HIP(hipMemcpy2DAsync(slot_rows + (size_t)n * c, (size_t)c * 4, sh->recv_buf, (size_t)rf * 4,
-                                            (size_t)c * 4, (size_t)n_halo, hipMemcpyDeviceToDevice, s));
-            if (a2_own)
-                TGNN_CHECK_HIP(hipMemcpy2DAsync(a2_halo_dst + (size_t)n * c, (size_t)c * 4, sh->recv_buf + c, (size_t)rf * 4,
-                                                (size_t)c * 4, (size_t)n_halo, hipMemcpyDeviceToDevice, s));
-        }
-        return TGNN_OK;
-    };
-
-    // ---- K1: per-type NNConv matrices of all layers, one launch -- on the side stream when there is one: it idles until
-    //      the init MLP is through, and these ~30 us (serial 3-layer MLP per (layer, type) + the bf16 image) then leave the
-    //      critical chain; the first NNConv waits for them.
-    hipStream_t sw = s;
-    constexpr bool weights_on_side = true;
-    const bool addr_ok = c == 32 && (int64_t)nr * c * 4 < (int64_t(1) << 31);   // buffer-addressed gathers
-    const bool cols_ok = forward_cols_ok(dims, graph, nr);
-    const bool groups_ok = graph->nn_tile_grp_ptr && graph->nn_grp && addr_ok && graph->nn_max_in_degree <= 2048 && g_nnconv_eg;
-    // Small layouts: the layer loop below is replaced by one persistent kernel (forward_small.hip)
-    const int small_teams = small_path_open(dims, graph, n, nr, sh != nullptr, keep != nullptr, use_running_stats != 0, prof.on)
-                                ? small_layout_teams(dims, n, T, graph->nn_max_in_degree) : 0;
-    const int64_t cat_w_floats = (int64_t)c * (D + 1) * kFinalDims[0];
-    const int fin_dims[5] = {c * (D + 1), kFinalDims[0], kFinalDims[1], kFinalDims[2], c};   // in / out widths of the final MLP's layers
-    // fp16-pair operands (3 matrix terms instead of the 6 of bf16 x 3) wherever a bound of the operand is at hand: the kernels
-    // that write a slot of the skip buffer leave its largest magnitude (w.bounds), one launch up front those of the root
-    // matrices and of the final MLP's first Linear.  General schedule, train-mode BatchNorm; needs the layout's largest
-    // in-degree.  Sharded: with one all-to-all per layer every shard merges its own AND its halo rows itself, so the bound it
-    // leaves covers every row its NNConv gathers (the shards' scales may differ -- powers of two, taken off again: each
-    // shard's results are as accurate as a single device's); the all-reduce + all-to-all scheme stays on bf16 x 3.
-    const bool fused_shard = sh && sh->send_idx_fused && sh->recv_idx_fused && sh->world >= 1 && c == 32;
-    const bool f16 = g_split_f16 && (cols_ok || groups_ok) && (!sh || fused_shard) && !small_teams && !use_running_stats &&
-                     graph->nn_max_in_degree >= 1 && D <= kMaxDepth && (cat_w_floats % 4) == 0;
-    unsigned *slot_max = f16 ? w.bounds : nullptr, *root_max = f16 ? w.bounds + D + 1 : nullptr,
-             *dense_max = f16 ? w.bounds + 2 * D + 1 : nullptr;
-    // Mid-size layouts (above the small-layout limit, up to 65 536 nodes): the D layers between the init and the final MLP are
-    // ONE persistent kernel carrying both chains (forward_mid.hip) instead of ~5 dependent launches per layer on two streams
-    int mid_blocks = 0;
-    const int mid_k = (f16 && !sh && !keep && !prof.on && nr == n) ? mid_layout_tiles_per_block(dims, graph, n, &mid_blocks) : 0;
-    // The persistent kernels, with CUs to spare for the edge-weight kernel's blocks, do not wait for the edge weights on the host's
-    // event (~12 us of cross-queue latency on a launch-bound forward) but on a counter of that kernel's finished blocks: the small
-    // kernel's init MLP, the mid kernel's first collision layer run beside them
-    // (the mid path's counter is a word of w.bounds that launch_forward_scales below zeroes anyway: no launch of its own)
-    // ... and the final MLP behind it as one more persistent kernel (forward_tail.hip) instead of 5 + 4 launches
-    int tail_blocks = 0;
-    const int tail_k = mid_k ? mid_tail_tiles_per_block(dims, n, &tail_blocks) : 0;
-    // the NNConv of the general schedule over the layout's edge groups (nnconv_eg.hip) where the graph carries them; its
-    // operand images are the fp16-pair ones with one more power of two on the weights
-    const bool eg = f16 && groups_ok && !mid_k;
-    const bool tiled = cols_ok || eg;
-    const bool mid_counter = mid_k && mid_blocks + 16 <= device_cus() && s2 && weights_on_side;
-    // the init MLP in that kernel's prologue instead of 5 launches -- where the kernel starts beside the edge-weight kernel (with
-    // a block on every CU it starts BEHIND it, a cross-queue event later, and the launches, which run beside it, win: measured at
-    // 16 384 and 32 768 nodes, profiles/r05_mid_tail.txt)
-    const bool mid_init = mid_counter && mid_init_in_kernel() && fx <= 8;
+    DeviceProbe probe{dims, graph};
+    const ForwardPlan plan = plan_forward(f, probe);
     // [r6] tgnn_graph.nn_mid_verdict: a forward queued behind a preparation whose batches are not verified yet -- honoured where the
     // mid-size forward is the two persistent kernels alone (they read the word and leave); anywhere else nothing is queued
-    if (mid_k && graph->nn_mid_verdict && !(mid_init && tail_k)) {
+    if (plan.verdict_refused) {
         set_error("tgnn_forward: nn_mid_verdict given, but the mid-size forward of this layout is not the two persistent kernels alone");
         return TGNN_ERR_UNVERIFIED;
     }
-    // [r6] a small layout whose pre-pass is on `stream` already (tgnn_forward_small_prepass): nothing to wait for, nothing to queue
-    const bool small_pre_used = small_pre && small_teams && c == 32 && T <= kCarveTypes && cols_ok && edge_weight_table_device_count_ok(fe, c);
-    unsigned *weights_done = mid_counter ? w.bounds + 2 * D + 6 : (small_teams == 2 && s2 && weights_on_side && !small_pre_used) ? w.small_ctr + 16 : nullptr;
-    if (weights_done && !mid_counter) TGNN_CHECK_HIP(hipMemsetAsync(weights_done, 0, 4, s));
-    const unsigned weights_target = edge_weight_table_blocks(T, fe, D, c, tiled);
-    // [r6] the general schedule's head: no memset anywhere (a hipMemsetAsync is two fill kernels and ~10 us in front of the first
-    // launch) -- the scales kernel clears the words, among them the collision branch's fold counter; the first Linear's bound is
-    // taken on the side stream with the other two (nobody needs it before the final MLP)
-    const bool lean_head = f16 && !mid_k && !small_teams && (g_lean_head.load(std::memory_order_relaxed) & 1);
-    // (what the init MLP's fused form needs is known here already: tgnn_forward_begin's work is used if and only if both hold)
-    const bool init_fused_early = c == 32 && fx <= 8 && !sh && !keep && !use_running_stats && (g_lean_head.load(std::memory_order_relaxed) & 2);
-    const bool head_used = head_done && lean_head && init_fused_early;
-    // (17 words: gin32_mlp_kernel folds the collision branch's BatchNorm in two levels -- a ticket per row group and one over the groups)
-    unsigned *fold_ctr = lean_head ? w.bounds + 2 * D + 10 : w.small_ctr + 32;
-    if (f16) {
-        const float *roots[kMaxDepth];
-        for (int i = 0; i < D; ++i) roots[i] = P.f(P.layer(i) + 6);
-        if (lean_head && head_done && init_fused_early)
-            ;                                                 // (tgnn_forward_begin's, on the side stream)
-        else if (lean_head)
-            launch_forward_scales(w.bounds, 2 * D + 95, roots, D, root_max, nullptr, 0, nullptr, s);
-        else
-            launch_forward_scales(w.bounds, 2 * D + 7, roots, D, root_max, P.f(P.fin(0)), cat_w_floats, dense_max, s);   // (before the fork: both chains see the zeroed words)
-    }
-    // [r6] tgnn_forward_resume picking up tgnn_forward_begin's work: `stream` has nothing to do in front of the first NNConv but wait
-    // for the preparation's last launches, so the edge weights go on IT, straight behind them (no cross-queue hand-over in front of
-    // them and none in front of the first NNConv: ~12 us each), and the collision chain is released first -- its first aggregate
-    // runs beside them instead of behind them
-    const bool weights_on_main = head_used && s2 && !sh && !keep && !mid_k && !small_teams && (g_lean_head.load(std::memory_order_relaxed) & 8) == 0;
-    if (small_pre_used) {
-        // (everything in front of the persistent kernel is on `stream`)
-    } else if (weights_on_main) {
-        TGNN_CHECK_HIP(hipEventRecord(ev[0], s));            // middle[0] (the head's event, waited for above) and the layout are complete
-        TGNN_CHECK_HIP(hipStreamWaitEvent(s2, ev[0], 0));
-    } else if (s2 && weights_on_side) {
-        TGNN_CHECK_HIP(hipEventRecord(ev[kEvFork], s));     // everything the caller queued on `stream` so far
-        TGNN_CHECK_HIP(hipStreamWaitEvent(s2, ev[kEvFork], 0));
-        sw = s2;
-    }
-    // (first on the side stream: the layer loop waits for these, the final MLP's bounds and images have the whole loop's time)
-    // [r6] tgnn_forward_begin_weights has queued exactly this launch behind the preparation already (type count read on the device)
-    const bool weights_queued = weights_early && weights_on_main && eg && T <= kCarveTypes && !weights_done && edge_weight_table_device_count_ok(fe, c);
-    if ((T > 0 || tiled) && !weights_queued && !small_pre_used) {
-        // edge MLP of every (layer, type) and, for the matrix-core NNConv, its operand images (root = pseudo-type T): one launch
-        EdgeMlpLayers layers{};
-        const float *roots[kMaxDepth];
-        for (int i = 0; i < D; ++i) {
-            const int b = P.layer(i);
-            layers.l[i] = EdgeMlpLayer{P.f(b), P.f(b + 1), P.f(b + 2), P.f(b + 3), P.f(b + 4), P.f(b + 5)};
-            roots[i] = P.f(b + 6);
-        }
-        prof.begin(0);
-        launch_edge_weight_table_batched(adj_edge_attr, graph->type_rep_edge, T, fe, layers, D, c, w.wtab, tiled ? roots : nullptr,
-                                         tiled ? w.wimg : nullptr, sw, weights_done, root_max, eg ? kEgImageScale : 1.0f);
-        prof.end();
-    }
-    // [r6] the layer loop waits for the edge weights alone: the event sits in front of the final MLP's bounds and images (they
-    // are joined with the collision chain, which the last merge waits for) -- 12 us of idle main stream in front of the first NNConv
-    bool weights_recorded = false;
-    if (lean_head && sw != s) {
-        TGNN_CHECK_HIP(hipEventRecord(ev[kEvWeights], s2));
-        weights_recorded = true;
-    }
-    bool dimg_ok[4] = {false, false, false, false};
-    if (lean_head && head_done && init_fused_early) {
-        dimg_ok[0] = dimg_ok[1] = dimg_ok[2] = dimg_ok[3] = c == 32 && n >= kDenseRowsKernelMin;   // (built by tgnn_forward_begin)
-    } else if (lean_head) {
-        // bounds of the three Linears' weights (+ of layers 1, 2's inputs from their BatchNorm parameters), then the three operand
-        // images in ONE launch
-        bool ok = false;
-        TGNN_TRY(forward_head_bounds_images(dims, P, w, n, n_total, sw, &ok));
-        dimg_ok[0] = dimg_ok[1] = dimg_ok[2] = dimg_ok[3] = ok;
-    } else if (f16 && !tail_k) {
-        // the final MLP's layers 1 and 2 (256 -> 128 -> 64): weights' bounds and, from the BatchNorm parameters alone, their inputs'
-        const float *bw[2], *bg[2], *bb[2];
-        int64_t bwn[2];
-        int bf[2];
-        unsigned *bwm[2], *bam[2];
-        for (int l = 1; l <= 2; ++l) {
-            const BnPtrs bp = P.bn(P.fin(l - 1) + 2);
-            bw[l - 1] = P.f(P.fin(l));
-            bwn[l - 1] = (int64_t)fin_dims[l] * fin_dims[l + 1];
-            bg[l - 1] = bp.gamma; bb[l - 1] = bp.beta; bf[l - 1] = fin_dims[l];
-            bwm[l - 1] = w.bounds + 2 * D + 2 + 2 * (l - 1);
-            bam[l - 1] = w.bounds + 2 * D + 3 + 2 * (l - 1);
-        }
-        launch_dense_bounds(2, bw, bwn, bg, bb, bf, bwm, bam, n_total, sw);   // (side stream: off the critical chain; the final MLP is behind every join)
-        // the three Linears' operand images for the rows-per-wave kernel (dense.hip), behind their weights' bounds on the same stream
-        for (int l = 0; l < 3; ++l) {
-            const unsigned *wm = l == 0 ? dense_max : w.bounds + 2 * D + 2 + 2 * (l - 1);
-            dimg_ok[l] = c == 32 && n >= kDenseRowsKernelMin && dense_f16_image_build(P.f(P.fin(l)), fin_dims[l], fin_dims[l + 1], wm, w.dimg[l], sw) == TGNN_OK;
-        }
-    }
-    if (small_teams && !small_pre_used) launch_small_pack(P, D, w.small_pack, w.small_ctr, s);   // on the main stream: it has nothing else to do yet
-    // (parameter vectors + GIN images of the layers; the same launch clears the barrier counter and the tagged partial rows)
-    if (mid_k) launch_small_pack(P, D, w.small_pack, w.small_ctr, s, tail_k > 0 || mid_init, w.mid_part, mid_part_doubles() * sizeof(double), tail_k > 0 ? dense_max : nullptr,
-                                 sw != s ? sw : nullptr);   // (the final MLP's images: side stream, joined behind the layer loop)
-    if (sw != s && !weights_recorded) TGNN_CHECK_HIP(hipEventRecord(ev[kEvWeights], s2));
-    g_path_count[small_teams ? 1 : mid_k ? 2 : 0].fetch_add(1, std::memory_order_relaxed);
-    if (small_teams) {
-        // init MLP, the layers and the final MLP: one persistent kernel behind the pre-pass
-        if (sw != s && !weights_done) TGNN_CHECK_HIP(hipStreamWaitEvent(s, ev[kEvWeights], 0));
-        TGNN_TRY(launch_forward_small(dims, P, x, probs, w.mid, w.a2[0], w.a2[1], w.wimg, w.small_pack, graph, w.small_part,
-                                      w.small_part_wide, w.small_runstat, w.small_ctr, weights_done, weights_target, n,
-                                      update_running, eps, momentum, s));
+
+    // ---- phases
+    Forward F(dims, params_host, w, graph, sh, keep, plan, x, adj_edge_attr, probs, update_running, use_running_stats, s, s2, ev, prof);
+    TGNN_TRY(F.queue_head());
+    TGNN_TRY(F.fork_side());
+    TGNN_TRY(F.queue_edge_weights());
+    TGNN_TRY(F.queue_final_operands());
+    TGNN_TRY(F.queue_packs());
+    g_path_count[plan.path == ForwardPath::Small ? 1 : plan.path == ForwardPath::General ? 0 : 2].fetch_add(1, std::memory_order_relaxed);
+    if (plan.path == ForwardPath::Small) {
+        TGNN_TRY(F.run_small());
         TGNN_CHECK_LAUNCH();
         return TGNN_OK;
     }
-
-    // ---- K10: init MLP  (TilinGNN.py:54)
-    // [r6] three launches that recompute from x instead of five that store (init_mlp.hip); the launch-per-op form stays for what
-    // keeps the activations (training), all-reduces the statistics (shards) or normalises with running statistics
-    const bool init_fused = !mid_init && c == 32 && fx <= 8 && !sh && !keep && !use_running_stats && (g_lean_head.load(std::memory_order_relaxed) & 2);
-    // (a layout that turns out not to take the fp16-pair path -- more than 16 edge types, an in-degree above 2 048 -- runs its head
-    //  again, the launch-per-op way; the init MLP's running statistics were updated by tgnn_forward_begin already)
-    BnPtrs ibn0 = P.bn(P.init(0) + 2), ibn1 = P.bn(P.init(1) + 2);
-    const bool init_stats_written = (head_done && !head_used) || (init_running_done && !use_running_stats);
-    if (init_stats_written) {
-        ibn0.rm = ibn0.rv = ibn1.rm = ibn1.rv = nullptr;
-        ibn0.nbt = ibn1.nbt = nullptr;
+    TGNN_TRY(F.init_mlp());
+    if (plan.fused_shard) TGNN_CHECK_ARG(sh->rank >= 0 && sh->rank < sh->world && sh->world <= 64, "shard rank / world (<= 64)");
+    TGNN_TRY(F.zero_fold_counter());
+    if (plan.path == ForwardPath::General) {
+        TGNN_TRY(F.release_side_chain());
+        for (int i = 0; i < f.D; ++i) TGNN_TRY(F.layer(i));
+    } else {
+        bool done = false;
+        TGNN_TRY(F.run_mid(&done));
+        if (done) return TGNN_OK;
     }
-    if (head_used) {
-    } else if (init_fused) {
-        prof.begin(1);
-        TGNN_TRY(forward_head_init(dims, P, x, w, n, init_stats_written ? 0 : update_running, slot_max, s));
-        prof.end();
-    } else if (!mid_init) {
-        prof.begin(1);
-        TGNN_TRY(tgnn_dense_act_fwd(x, fx, 32, nullptr, P.f(P.init(0)), P.f(P.init(0) + 1), n, fx, c, TGNN_ACT_LEAKY_RELU,
-                                    w.t0, c, w.partf, &np1, s));
-        prof.end();
-        TGNN_TRY(finalize1(w.partf, np1, c, ibn0, w.stat_i[0]));
-        prof.begin(1);
-        TGNN_TRY(tgnn_dense_act_fwd(w.t0, c, 32, w.stat_i[0], P.f(P.init(1)), P.f(P.init(1) + 1), n, c, c,
-                                    TGNN_ACT_LEAKY_RELU, w.a1, c, w.partf, &np1, s));
-        prof.end();
-        TGNN_TRY(finalize1(w.partf, np1, c, ibn1, w.stat_i[1]));
-        prof.begin(1);
-        launch_bn_apply(w.a1, c, w.stat_i[1], n, c, w.mid, c, slot_max, s);   // middle[0] = brch_1 = brch_2 (:55,58)
-        prof.end();
-    }
-    TGNN_TRY(exchange(0, nullptr, nullptr));
-    if (f16 && n_halo > 0) launch_absmax(w.mid + (size_t)n * c, n_halo * c, slot_max, s);   // (the halo rows of middle[0])
-
-    // ---- main loop (TilinGNN.py:59-71)
-    const bool run_stats = update_running || use_running_stats;
-    auto bn_job = [&](double *part, int nparts, const BnPtrs &bp, float *stat) {
-        return BnJob{part, nparts, nullptr, bp.gamma, bp.beta, run_stats ? bp.rm : nullptr, run_stats ? bp.rv : nullptr,
-                     (update_running && !use_running_stats) ? bp.nbt : nullptr, stat};
-    };
-    // CollConv (:63): input = BN_{i-1}(a2_{i-1}) folded into the gather; layer 0 reads middle[0]
-    // one all-to-all per layer instead of all-reduce + all-to-all (see tgnn_shard in tgnn.h)
-    if (fused_shard) TGNN_CHECK_ARG(sh->rank >= 0 && sh->rank < sh->world && sh->world <= 64, "shard rank / world (<= 64)");
-    const bool split = fused_shard && s2 != nullptr;       // one exchange per branch and layer, the collision branch's on the side stream
-    // The collision branch's BatchNorm record by the LAST block of the GIN MLP kernel (gin.hip: GinFin) instead of a 1-block
-    // finalize launch behind it -- 20 launches less on that chain (measured by leaving them out: 0.07 ms of 1.95).  Single
-    // device, width 32, batch statistics.
-#ifdef TGNN_ABL_NOFOLD
-    const bool fold_fin2 = false;
-#else
-    const bool fold_fin2 = c == 32 && !sh && !use_running_stats;
-#endif
-    if (fold_fin2 && !mid_k && !lean_head) TGNN_CHECK_HIP(hipMemsetAsync(fold_ctr, 0, 17 * sizeof(unsigned), s));   // (before ev[0]: the side chain sees it)
-    auto gin_layer = [&](int i, hipStream_t gs) -> int {
-        const int b = P.layer(i);
-        const float *gin_in = i == 0 ? w.mid : w.a2[(i - 1) & 1];
-        const float *gin_stat = i == 0 ? nullptr : w.stat2[(i - 1) & 1];
-        if (fold_fin2) {
-            GinFin fin{};
-            fin.counter = fold_ctr;
-            fin.job = bn_job(nullptr, 0, P.bn(b + 20), w.stat2[i & 1]);
-            fin.n_total = n;
-            fin.eps = eps;
-            fin.momentum = momentum;
-            prof.begin(3);
-            const int rc = gin32_fwd_folded(gin_in, c, gin_stat, graph->col_rowptr, graph->col_src, P.f(b + 13), P.f(b + 14), P.f(b + 15),
-                                            P.f(b + 16), P.f(b + 17), P.f(b + 18), P.f(b + 19), n, TGNN_ACT_LEAKY_RELU, w.a2[i & 1],
-                                            w.t0, w.part2, &np2, fin, gs, keep != nullptr);
-            prof.end();
-            if (rc != TGNN_ERR_UNSUPPORTED) return rc;
-            return TGNN_ERR_UNSUPPORTED;                       // (the workspace is aligned: cannot happen)
-        }
-        prof.begin(3);
-        if (keep && c != 32) {
-            // training at width 64: the generic kernel (the one inference runs at this width) also stores the aggregate, keep->u
-            TGNN_TRY(gin_generic_fwd_keep(gin_in, c, gin_stat, graph->col_rowptr, graph->col_src, P.f(b + 13), P.f(b + 14),
-                                          P.f(b + 15), P.f(b + 16), P.f(b + 17), P.f(b + 18), P.f(b + 19), n, c, TGNN_ACT_LEAKY_RELU,
-                                          w.a2[i & 1], w.t0, w.part2, &np2, gs));
-            prof.end();
-            return TGNN_OK;
-        }
-        TGNN_TRY(tgnn_gin_fwd(gin_in, c, gin_stat, graph->col_rowptr, graph->col_src, P.f(b + 13), P.f(b + 14),
-                              P.f(b + 15), P.f(b + 16), P.f(b + 17), P.f(b + 18), P.f(b + 19), n, c,
-                              TGNN_ACT_LEAKY_RELU, w.a2[i & 1], w.t0, w.part2, &np2, gs));
-        prof.end();
-        return TGNN_OK;
-    };
-    if (mid_k) {
-        double *const tail_zero[2] = {w.partf, w.small_part_wide};   // the tail kernel's tagged rows: cleared by the layer loop's blocks
-        if (sw != s && !weights_done) TGNN_CHECK_HIP(hipStreamWaitEvent(s, ev[kEvWeights], 0));   // (the images of the side stream)
-        TGNN_TRY(launch_forward_mid(dims, P, w.mid, w.a1, w.a2[0], w.a2[1], w.wimg, w.small_pack, graph, w.mid_part, w.small_runstat,
-                                    w.small_ctr, w.bounds, n, mid_k, mid_blocks, update_running, eps, momentum, s, weights_done,
-                                    weights_target, tail_k ? tail_zero : nullptr, mid_tail_part_doubles(), mid_init ? x : nullptr));
-        // (the final MLP reads the side stream's bounds and operand images: behind the layer loop, where the wait costs nothing)
-        if (sw != s && weights_done) TGNN_CHECK_HIP(hipStreamWaitEvent(s, ev[kEvWeights], 0));
-        if (tail_k) {
-            TGNN_TRY(launch_forward_tail(dims, P, w.mid, w.small_pack, probs, w.partf, w.small_part_wide, slot_max, dense_max, n, tail_k,
-                                         tail_blocks, update_running, eps, momentum, s, graph->nn_mid_verdict));
-            return TGNN_OK;
-        }
-    } else if (s2 && !weights_on_main) {
-        TGNN_CHECK_HIP(hipEventRecord(ev[0], s));            // middle[0] is complete
-        TGNN_CHECK_HIP(hipStreamWaitEvent(s2, ev[0], 0));
-        if (sw != s) TGNN_CHECK_HIP(hipStreamWaitEvent(s, ev[kEvWeights], 0));
-    }
-    for (int i = 0; i < (mid_k ? 0 : D); ++i) {
-        const int b = P.layer(i);
-        if (keep) {                                          // this layer's own buffers (kernels already queued keep theirs)
-            w.a1 = keep->a1 + (size_t)i * n * c;
-            w.a2[i & 1] = keep->a2 + (size_t)i * n * c;
-            w.t0 = keep->u + (size_t)i * n * c;
-            w.stat1 = keep->stat1 + (size_t)i * 4 * c;
-            w.stat2[i & 1] = keep->stat2 + (size_t)i * 4 * c;
-        }
-        const float *h1 = w.mid + (size_t)i * nr * c;
-        // [r6] tgnn_forward_resume, layer 0: the NNConv's launch goes out BEFORE the collision chain's -- the host is what the first
-        // layer waits for behind a just-prepared layout, and the adjacency chain is the longer one
-        const bool nn_first = weights_on_main && i == 0;
-        if (s2 && !nn_first) {
-            // ---- collision chain, layer i, on the side stream: a2[i & 1] / stat2[i & 1] were last read by merge_{i-2}
-            // (sharded: the halo rows and the statistics GIN_i reads arrive with the exchange of layer i-1, so the chain cannot run
-            //  ahead; only the HBM-bound neighbourhood sum goes beside the merge / NNConv -- the MLP, which finds no CU beside an
-            //  NNConv block, follows on the main stream: 52 us beside the NNConv against 19 us behind it, measured)
-            if (sh && split) {
-                // split exchange: the whole collision branch of layer i -- GIN, then ITS OWN all-to-all (halo rows of a2 + the
-                // BatchNorm sums, 32 floats per row) and the statistics -- on the side stream: it needs nothing of the adjacency
-                // branch, so the chain runs ahead of the NNConv / merge chain as it does on a single device, held back only by
-                // the two-deep buffers (a2[i & 1] / stat2[i & 1] were last read by merge_{i-2})
-                if (i >= 2) TGNN_CHECK_HIP(hipStreamWaitEvent(s2, ev[1 + kMaxDepth + i - 2], 0));
-                TGNN_TRY(gin_layer(i, s2));
-                if (i + 1 < D) {
-                    BnJob j2 = bn_job(w.part2, np2, P.bn(b + 20), w.stat2[i & 1]);
-                    j2.sums = sh->sum_buf + 64;
-                    const int64_t n_out = sh->n_send + 4 * (int64_t)sh->world, n_in = n_halo + 4 * (int64_t)sh->world;
-                    float *sb2 = sh->send_buf + (size_t)n_out * c, *rb2 = sh->recv_buf + (size_t)n_in * c;
-                    launch_shard_pack1(w.a2[i & 1], sh->send_idx_fused, n_out, j2, sb2, s2);
-                    TGNN_TRY(alltoall(sb2, rb2, c, 4, s2));
-                    launch_shard_unpack1(rb2, sh->recv_idx_fused, n_in, n, w.a2[i & 1], j2, sh->world, sh->rank, n_total, eps,
-                                         momentum, s2);
-                }
-            } else if (sh) {
-                if (i >= 1) TGNN_CHECK_HIP(hipStreamWaitEvent(s2, ev[1 + kMaxDepth + i - 1], 0));
-                const float *gin_in = i == 0 ? w.mid : w.a2[(i - 1) & 1];
-                TGNN_TRY(tgnn_gin_aggregate(gin_in, c, i == 0 ? nullptr : w.stat2[(i - 1) & 1], graph->col_rowptr, graph->col_src,
-                                            P.f(b + 13), n, c, w.t0, s2));
-            } else {
-                if (i >= 2) TGNN_CHECK_HIP(hipStreamWaitEvent(s2, ev[1 + kMaxDepth + i - 2], 0));
-                TGNN_TRY(gin_layer(i, s2));
-                if (!fold_fin2) {
-                    BnJobs j2{};
-                    j2.job[0] = bn_job(w.part2, np2, P.bn(b + 20), w.stat2[i & 1]);
-                    launch_bn_finalize(j2, 1, fin_mode, c, n, eps, momentum, s2);
-                }
-            }
-            TGNN_CHECK_HIP(hipEventRecord(ev[1 + i], s2));
-        }
-        // GraphConv (:62): NNConv mean + LeakyReLU; BN statistics emitted as partials
-        prof.begin(2);
-        // [r6] sharded, split exchange: the pack of the adjacency branch's message inside the NNConv (nnconv_eg.hip: SHARD)
-        const bool pack_in_nnconv = eg && split && i + 1 < D && sh->send_row_ptr && sh->send_row_slot && lean_head;
-        if (eg) {
-            EgShardPack pk{};
-            if (pack_in_nnconv)
-                pk = EgShardPack{sh->send_row_ptr, sh->send_row_slot, sh->send_buf, sh->send_idx_fused, sh->n_send + 4 * (int64_t)sh->world,
-                                 sh->sum_buf, w.bounds + 2 * D + 27, w.small_part_wide + (size_t)4 * 16 * 512};
-            TGNN_TRY(launch_nnconv_eg(h1, graph->nn_tile_grp_ptr, graph->nn_grp, w.wimg + (size_t)i * (T + 1) * kWtTypeF16, T,
-                                      P.f(b + 7), n, TGNN_ACT_LEAKY_RELU, w.a1, w.part1, &np1, s, slot_max + i, root_max + i,
-                                      prof.stamps ? prof.stamps + 2 * i : nullptr, pack_in_nnconv ? &pk : nullptr));
-        } else if (tiled) {
-            TGNN_TRY(launch_nnconv_cols(h1, c, graph->nn_tile_col_ptr, graph->nn_col_meta, graph->nn_col_src,
-                                        w.wimg + (size_t)i * (T + 1) * (f16 ? kWtTypeF16 : kWtType), T, P.f(b + 7), n,
-                                        TGNN_ACT_LEAKY_RELU, w.a1, w.part1, &np1, s, f16 ? slot_max + i : nullptr,
-                                        f16 ? root_max + i : nullptr, graph->nn_max_in_degree,
-                                        prof.stamps ? prof.stamps + 2 * i : nullptr));
-        } else {
-            TGNN_TRY(tgnn_nnconv_mean_fwd(h1, c, graph->adj_rowptr, graph->adj_src, graph->adj_type,
-                                      w.wtab + (size_t)i * T * c * c, T, P.f(b + 6), P.f(b + 7), n, c,
-                                      TGNN_ACT_LEAKY_RELU, w.a1, w.part1, &np1, s));
-        }
-        prof.end();
-        if (nn_first) {                                      // (single device, i == 0: see the branch above)
-            TGNN_TRY(gin_layer(i, s2));
-            if (!fold_fin2) {
-                BnJobs j2{};
-                j2.job[0] = bn_job(w.part2, np2, P.bn(b + 20), w.stat2[i & 1]);
-                launch_bn_finalize(j2, 1, fin_mode, c, n, eps, momentum, s2);
-            }
-            TGNN_CHECK_HIP(hipEventRecord(ev[1 + i], s2));
-        }
-        if (split && i + 1 < D) {
-            // ---- sharded, split exchange: this chain carries the adjacency branch only (rows of a1 + its BatchNorm sums); the
-            //      collision branch's half arrived (or is arriving) on the side stream
-            BnJob j1 = bn_job(w.part1, np1, P.bn(b + 8), w.stat1);
-            j1.sums = sh->sum_buf;
-            const int64_t n_out = sh->n_send + 4 * (int64_t)sh->world, n_in = n_halo + 4 * (int64_t)sh->world;
-            if (!pack_in_nnconv) launch_shard_pack1(w.a1, sh->send_idx_fused, n_out, j1, sh->send_buf, s);
-            TGNN_TRY(alltoall(sh->send_buf, sh->recv_buf, c, 4, s));
-            const float *resid_f = i >= 2 ? w.mid + (size_t)(i - 2) * nr * c : nullptr;
-            TGNN_CHECK_HIP(hipStreamWaitEvent(s, ev[1 + i], 0));
-            // [r6] unpack + merge as one launch: the record from the shards' sums in every block, the halo rows of a1 out of the message
-            launch_shard_unpack1_merge(sh->recv_buf, sh->recv_idx_fused, n_in, n, w.a1, j1, sh->world, sh->rank, n_total, eps, momentum,
-                                       w.a2[i & 1], w.stat2[i & 1], resid_f, nr, w.mid + (size_t)(i + 1) * nr * c,
-                                       f16 ? slot_max + i + 1 : nullptr, s);
-            TGNN_CHECK_HIP(hipEventRecord(ev[1 + kMaxDepth + i], s));       // (a2[i & 1] / stat2[i & 1] are free for GIN_{i+2})
-            continue;
-        }
-        if (fused_shard && i + 1 < D) {
-            // ---- sharded, fused: local sums -> ONE all-to-all (raw halo rows of both branches + the sums) -> the sums of
-            //      all shards added in rank order -> statistics -> merge of the own AND the halo rows
-            if (s2) {
-                TGNN_CHECK_HIP(hipStreamWaitEvent(s, ev[1 + i], 0));
-                TGNN_TRY(launch_gin32_mlp(w.t0, P.f(b + 14), P.f(b + 15), P.f(b + 16), P.f(b + 17), P.f(b + 18), P.f(b + 19), n,
-                                          TGNN_ACT_LEAKY_RELU, w.a2[i & 1], w.part2, &np2, s, nullptr, true));
-            } else {
-                TGNN_TRY(gin_layer(i, s));
-            }
-            BnJobs jobs{};
-            jobs.job[0] = bn_job(w.part1, np1, P.bn(b + 8), w.stat1);
-            jobs.job[1] = bn_job(w.part2, np2, P.bn(b + 20), w.stat2[i & 1]);
-            double *own = sh->sum_buf;
-            jobs.job[0].sums = own;
-            jobs.job[1].sums = own + 64;
-            const int64_t n_out = sh->n_send + 4 * (int64_t)sh->world, n_in = n_halo + 4 * (int64_t)sh->world;
-            launch_shard_pack_sums(w.a1, w.a2[i & 1], sh->send_idx_fused, n_out, jobs, sh->send_buf, s);
-            TGNN_TRY(alltoall(sh->send_buf, sh->recv_buf, 2 * c, 4, s));
-            launch_shard_unpack_finalize(sh->recv_buf, sh->recv_idx_fused, n_in, n, w.a1, w.a2[i & 1], jobs, sh->world,
-                                         sh->rank, n_total, eps, momentum, s);
-            // (what the next GIN reads -- the collision rows incl. halo and their statistics -- is complete here: it starts beside
-            //  the merge, not behind it)
-            if (s2) TGNN_CHECK_HIP(hipEventRecord(ev[1 + kMaxDepth + i], s));
-            const float *resid_f = i >= 2 ? w.mid + (size_t)(i - 2) * nr * c : nullptr;
-            if (f16)
-                launch_merge(w.a1, w.stat1, w.a2[i & 1], w.stat2[i & 1], resid_f, nr, c, w.mid + (size_t)(i + 1) * nr * c, nullptr,
-                             slot_max + i + 1, s);
-            else
-                TGNN_TRY(tgnn_merge_fwd(w.a1, w.stat1, w.a2[i & 1], w.stat2[i & 1], resid_f, nr, c,
-                                        w.mid + (size_t)(i + 1) * nr * c, nullptr, s));
-            continue;
-        }
-        // Few partial rows (small layouts): merge derives the first BatchNorm's record from them itself -- one launch
-        // less on the critical chain of a launch-latency-bound forward.  (With the 256 rows of a 100k-node layout the
-        // repeated reduction costs every merge block more than the separate 1-block finalize: measured.)
-        // (round 2: with 1024-thread blocks -- one batch of independent loads per thread -- the repeated reduction pays at every
-        //  size: the launch it replaces sits on the critical NNConv -> merge chain.  TGNN_BN_MAX_PARTIALS rows at most.)
-        constexpr int fuse_rows = TGNN_BN_MAX_PARTIALS;
-        const bool fused_bn1 = c == 32 && !use_running_stats && !sh && np1 <= fuse_rows;
-        if (s2 && sh) {
-            TGNN_CHECK_HIP(hipStreamWaitEvent(s, ev[1 + i], 0));
-            if (!split)
-                TGNN_TRY(launch_gin32_mlp(w.t0, P.f(b + 14), P.f(b + 15), P.f(b + 16), P.f(b + 17), P.f(b + 18), P.f(b + 19), n,
-                                          TGNN_ACT_LEAKY_RELU, w.a2[i & 1], w.part2, &np2, s, nullptr, true));
-            BnJobs jobs{};
-            jobs.job[0] = bn_job(w.part1, np1, P.bn(b + 8), w.stat1);
-            jobs.job[1] = bn_job(w.part2, np2, P.bn(b + 20), w.stat2[i & 1]);
-            TGNN_TRY(finalize_jobs(jobs, 2, c));
-        } else if (s2) {
-            if (!fused_bn1) {
-                BnJobs j1{};
-                j1.job[0] = bn_job(w.part1, np1, P.bn(b + 8), w.stat1);
-                launch_bn_finalize(j1, 1, fin_mode, c, n, eps, momentum, s);
-            }
-            TGNN_CHECK_HIP(hipStreamWaitEvent(s, ev[1 + i], 0));
-        } else {
-            TGNN_TRY(gin_layer(i, s));
-            BnJobs jobs{};
-            int nj = 0;
-            if (!fused_bn1) jobs.job[nj++] = bn_job(w.part1, np1, P.bn(b + 8), w.stat1);
-            if (!fold_fin2) jobs.job[nj++] = bn_job(w.part2, np2, P.bn(b + 20), w.stat2[i & 1]);
-            TGNN_TRY(finalize_jobs(jobs, nj, c));
-        }
-        // merge (:64-71): middle[i+1] = BN1(a1) * BN2(a2) (+ middle[i-2])
-        const float *resid = i >= 2 ? w.mid + (size_t)(i - 2) * nr * c : nullptr;
-        prof.begin(5);
-        if (fused_bn1) {
-            launch_merge_bn1(w.a1, bn_job(w.part1, np1, P.bn(b + 8), w.stat1), n, eps, momentum, w.a2[i & 1],
-                             w.stat2[i & 1], resid, n, w.mid + (size_t)(i + 1) * nr * c, s, f16 ? slot_max + i + 1 : nullptr);
-        } else if (f16) {
-            launch_merge(w.a1, w.stat1, w.a2[i & 1], w.stat2[i & 1], resid, n, c, w.mid + (size_t)(i + 1) * nr * c, nullptr,
-                         slot_max + i + 1, s);
-        } else {
-            TGNN_TRY(tgnn_merge_fwd(w.a1, w.stat1, w.a2[i & 1], w.stat2[i & 1], resid, n, c,
-                                    w.mid + (size_t)(i + 1) * nr * c, nullptr, s));
-        }
-        prof.end();
-        if (s2 && !sh) TGNN_CHECK_HIP(hipEventRecord(ev[1 + kMaxDepth + i], s));
-        if (i + 1 < D) TGNN_TRY(exchange(i + 1, w.a2[i & 1], w.a2[i & 1]));
-        if (s2 && sh) TGNN_CHECK_HIP(hipEventRecord(ev[1 + kMaxDepth + i], s));     // (the next GIN also reads the halo rows)
-    }
-
-    // ---- K11: final MLP over the concatenation (TilinGNN.py:74-76); K block kb = middle[kb]
-    const int cat_dim = c * (D + 1);
-    float *fbuf[4] = {w.f1, w.f2, w.f3, w.f4};
-    int fdim[5] = {cat_dim, kFinalDims[0], kFinalDims[1], kFinalDims[2], c};
-    // [r6] the final MLP's BatchNorm records by their producers (bn_fold_two_level in the rows / resident kernels: the same bits) instead
-    // of a 7 us bn_finalize launch behind each; 17 counter words per layer behind the collision branch's, cleared by the scales kernel
-    // (bit 2 of tgnn_set_lean_head, OFF by default: measured, every producer grew by the 6 - 8 us its finalize launch took -- all of
-    //  a dense kernel's blocks finish together, so both levels of the fold are serial latency behind the last one, unlike in the
-    //  collision MLP, whose row groups finish at different times: profiles/r06_tail_fold.txt)
-    const bool fold_final = lean_head && !sh && !use_running_stats && c == 32 && (g_lean_head.load(std::memory_order_relaxed) & 4);
-    for (int l = 0; l < 4; ++l) {
-        const int pi = P.fin(l);
-        GinFin ff{};
-        bool folded = false;
-        if (fold_final) {
-            ff.counter = w.bounds + 2 * D + 27 + 17 * l;
-            ff.job = bn_job(nullptr, 0, P.bn(pi + 2), w.stat_f[l]);
-            ff.n_total = n;
-            ff.eps = eps;
-            ff.momentum = momentum;
-        }
-        double *fold_rows = w.small_part_wide + (size_t)l * 16 * 512;
-        if (l == 0) {
-            TGNN_CHECK_ARG(c % 32 == 0, "final MLP over the slot-major buffer needs a network_width that is a multiple of 32");
-            prof.begin(6);
-            if (f16)
-                TGNN_TRY(dense_act_slots_bounded(w.mid, c, (int64_t)nr * c, P.f(pi), P.f(pi + 1), n, cat_dim, fdim[1],
-                                                 TGNN_ACT_LEAKY_RELU, fbuf[0], fdim[1], w.partf, &np1, slot_max, D + 1, dense_max, s,
-                                                 dimg_ok[0] ? w.dimg[0] : nullptr, fold_final ? &ff : nullptr, fold_rows, &folded));
-            else
-                TGNN_TRY(tgnn_dense_act_slots_fwd(w.mid, c, (int64_t)nr * c, nullptr, P.f(pi), P.f(pi + 1), n, cat_dim, fdim[1],
-                                                  TGNN_ACT_LEAKY_RELU, fbuf[0], fdim[1], w.partf, &np1, s));
-            prof.end();
-        } else {
-            prof.begin(6);
-            if (f16 && (l <= 2 || dimg_ok[l]))   // fp16 pairs: the input's bound follows from the producer's BatchNorm parameters (dense_bounds_kernel)
-                TGNN_TRY(dense_act_bounded(fbuf[l - 1], fdim[l], 32, w.stat_f[l - 1], P.f(pi), P.f(pi + 1), n, fdim[l], fdim[l + 1],
-                                           TGNN_ACT_LEAKY_RELU, fbuf[l], fdim[l + 1], w.partf, &np1, final_bound_word(w, D, l) + 1, 1,
-                                           final_bound_word(w, D, l), s, dimg_ok[l] ? w.dimg[l] : nullptr, fold_final ? &ff : nullptr, fold_rows,
-                                           &folded));
-            else
-                TGNN_TRY(tgnn_dense_act_fwd(fbuf[l - 1], fdim[l], 32, w.stat_f[l - 1], P.f(pi), P.f(pi + 1), n, fdim[l],
-                                            fdim[l + 1], TGNN_ACT_LEAKY_RELU, fbuf[l], fdim[l + 1], w.partf, &np1, s));
-            prof.end();
-        }
-        if (!folded) TGNN_TRY(finalize1(w.partf, np1, fdim[l + 1], P.bn(pi + 2), w.stat_f[l]));
-    }
-    prof.begin(6);
-    TGNN_TRY(tgnn_dense_act_fwd(fbuf[3], c, 32, w.stat_f[3], P.f(P.last()), P.f(P.last() + 1), n, c, dims->output_dim,
-                                TGNN_ACT_SIGMOID, probs, dims->output_dim, nullptr, nullptr, s));
-    prof.end();
+    TGNN_CHECK_ARG(f.c % 32 == 0, "final MLP over the slot-major buffer needs a network_width that is a multiple of 32");
+    TGNN_TRY(F.final_mlp());
     TGNN_CHECK_LAUNCH();
     return TGNN_OK;
 }
@@ -1013,23 +1146,15 @@ extern "C" int tgnn_forward_begin(const tgnn_model_dims *dims, const void *const
     DeviceGuard guard__(stream ? stream : stream2);
     TGNN_CHECK_ARG(dims_ok(dims) && params_host && x && n_nodes >= 2, "arguments");
     hipStream_t s = static_cast<hipStream_t>(stream), s2 = static_cast<hipStream_t>(stream2);
-    const int c = dims->network_width, D = dims->network_depth, fx = dims->node_features_dim;
-    // what forward_impl's lean head + fused init MLP need, as far as it can be known without the graph; the rest (fp16-pair
+    const int D = dims->network_depth;
+    // what the plan's lean head + fused init MLP need, as far as it can be known without the graph; the rest (fp16-pair
     // operands: edge groups / columns, largest in-degree) is checked by tgnn_forward_resume
-    if (!s2 || s2 == s || c != 32 || fx > 8 || D > kMaxDepth || ((int64_t)c * (D + 1) * kFinalDims[0]) % 4 != 0 || !g_split_f16 ||
-        (g_lean_head.load(std::memory_order_relaxed) & 3) != 3 || n_nodes <= tgnn_get_mid_layout_limit() || n_nodes <= tgnn_get_small_layout_limit())
+    if (!head_early_ok(dims->network_width, D, dims->node_features_dim, s2 && s2 != s, g_split_f16.load(),
+                       g_lean_head.load(std::memory_order_relaxed), n_nodes, tgnn_get_small_layout_limit(), tgnn_get_mid_layout_limit()))
         return TGNN_ERR_UNSUPPORTED;
-    const int np = tgnn_param_count(dims);
-    for (int i = 0; i < np; ++i)
-        if (!params_host[i]) {
-            set_error("tgnn_forward_begin: params_host[%d] is null", i);
-            return TGNN_ERR_INVALID_ARG;
-        }
-    Workspace w = carve(*dims, n_nodes, n_nodes, 0, ws, ws_bytes);
-    if (!ws || w.bytes > ws_bytes) {
-        set_error("tgnn_forward_begin: workspace too small (%zu < %zu)", ws_bytes, w.bytes);
-        return TGNN_ERR_WORKSPACE;
-    }
+    TGNN_TRY(check_params(dims, params_host, "tgnn_forward_begin"));
+    Workspace w;
+    TGNN_TRY(carve_checked(*dims, n_nodes, n_nodes, 0, ws, ws_bytes, "tgnn_forward_begin", &w));
     int dev = 0;
     TGNN_CHECK_HIP(hipGetDevice(&dev));
     TGNN_CHECK_ARG(dev >= 0 && dev < 64, "device index");
@@ -1074,21 +1199,13 @@ extern "C" int tgnn_forward_small_prepass(const tgnn_model_dims *dims, const voi
     TGNN_CHECK_HIP(hipGetDevice(&dev));
     TGNN_CHECK_ARG(dev >= 0 && dev < 64, "device index");
     const int c = dims->network_width, D = dims->network_depth, fe = dims->adj_edge_features_dim;
-    if (c != 32 || n_nodes < 2 || n_nodes > tgnn_get_small_layout_limit() || !edge_weight_table_device_count_ok(fe, c) ||
-        (g_lean_head.load(std::memory_order_relaxed) & 8))
-        return TGNN_ERR_UNSUPPORTED;
-    Workspace w = carve(*dims, n_nodes, n_nodes, 0, ws, ws_bytes);
-    if (!ws || w.bytes > ws_bytes) return TGNN_ERR_WORKSPACE;
+    if (!small_prepass_ok(c, n_nodes, tgnn_get_small_layout_limit(), edge_weight_table_device_count_ok(fe, c))) return TGNN_ERR_UNSUPPORTED;
+    Workspace w;
+    TGNN_TRY(carve_checked(*dims, n_nodes, n_nodes, 0, ws, ws_bytes, nullptr, &w));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Params P{params_host, D};
-    EdgeMlpLayers layers{};
-    const float *roots[kMaxDepth];
-    for (int i = 0; i < D; ++i) {
-        const int b = P.layer(i);
-        layers.l[i] = EdgeMlpLayer{P.f(b), P.f(b + 1), P.f(b + 2), P.f(b + 3), P.f(b + 4), P.f(b + 5)};
-        roots[i] = P.f(b + 6);
-    }
-    launch_edge_weight_table_batched(adj_edge_attr, type_rep_edge, 0, fe, layers, D, c, w.wtab, roots, w.wimg, s, nullptr, nullptr, 1.0f,
+    const EdgeMlpTable em(P, D);
+    launch_edge_weight_table_batched(adj_edge_attr, type_rep_edge, 0, fe, em.layers, D, c, w.wtab, em.roots, w.wimg, s, nullptr, nullptr, 1.0f,
                                      n_types_dev, kCarveTypes);
     launch_small_pack(P, D, w.small_pack, w.small_ctr, s);
     g_small_pre[dev].ws = ws;
@@ -1108,22 +1225,16 @@ extern "C" int tgnn_forward_begin_weights(const tgnn_model_dims *dims, const voi
     TGNN_CHECK_ARG(dev >= 0 && dev < 64, "device index");
     HeadEvent &he = g_head[dev];
     const int c = dims->network_width, D = dims->network_depth, fe = dims->adj_edge_features_dim;
-    if (!he.ev || he.ws != ws || he.n != n_nodes || c != 32 || !edge_weight_table_device_count_ok(fe, c) || !g_nnconv_eg.load() ||
-        !g_split_f16.load() || (g_lean_head.load(std::memory_order_relaxed) & 24))
+    const bool head_match = he.ev && he.ws == ws && he.n == n_nodes;
+    if (!weights_early_ok(head_match, c, edge_weight_table_device_count_ok(fe, c), g_nnconv_eg.load(), g_split_f16.load()))
         return TGNN_ERR_UNSUPPORTED;                           // (no matching tgnn_forward_begin, or a forward that will not take this launch)
-    Workspace w = carve(*dims, n_nodes, n_nodes, 0, ws, ws_bytes);
-    if (!ws || w.bytes > ws_bytes) return TGNN_ERR_WORKSPACE;
+    Workspace w;
+    TGNN_TRY(carve_checked(*dims, n_nodes, n_nodes, 0, ws, ws_bytes, nullptr, &w));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Params P{params_host, D};
-    EdgeMlpLayers layers{};
-    const float *roots[kMaxDepth];
-    for (int i = 0; i < D; ++i) {
-        const int b = P.layer(i);
-        layers.l[i] = EdgeMlpLayer{P.f(b), P.f(b + 1), P.f(b + 2), P.f(b + 3), P.f(b + 4), P.f(b + 5)};
-        roots[i] = P.f(b + 6);
-    }
+    const EdgeMlpTable em(P, D);
     // (no wait for tgnn_forward_begin's stream: the kernel takes the roots' bounds itself when it reads the type count itself)
-    launch_edge_weight_table_batched(adj_edge_attr, type_rep_edge, 0, fe, layers, D, c, w.wtab, roots, w.wimg, s, nullptr, w.bounds + D + 1,
+    launch_edge_weight_table_batched(adj_edge_attr, type_rep_edge, 0, fe, em.layers, D, c, w.wtab, em.roots, w.wimg, s, nullptr, w.bounds + D + 1,
                                      kEgImageScale, n_types_dev, kCarveTypes);
     he.weights = true;
     TGNN_CHECK_LAUNCH();

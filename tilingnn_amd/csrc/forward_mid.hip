@@ -877,7 +877,6 @@ constexpr size_t kMidMaxLds = 160 * 1024 - 256;
 // runs (tiles in rounds, tgnn_set_mid_layout_limit up to 65 536) but the general schedule is faster (measured: 40 000 nodes 1.13 vs
 // 1.05 ms, 50 000: 1.28 vs 1.20; 32 000: 0.82 vs 0.97, 10 000: 0.61 vs 0.77)
 static std::atomic<int64_t> g_mid_limit{32768};
-static std::atomic<int> g_mid_blocks_cap{0};                      // experiments: upper bound of the grid (0 = one block per CU)
 
 // > 0: tiles per block of the persistent layer loop for this layout; 0: not eligible (the general schedule runs)
 int mid_layout_tiles_per_block(const tgnn_model_dims *d, const tgnn_graph *g, int64_t n_nodes, int *blocks_out) {
@@ -902,7 +901,6 @@ int mid_layout_tiles_per_block(const tgnn_model_dims *d, const tgnn_graph *g, in
     }
     if (cap <= 0) return 0;
     int max_blocks = cap < 256 ? cap : 256;                       // (mid_part / gpart are sized for 256 blocks: launch_forward_mid)
-    if (const int dbg = g_mid_blocks_cap.load(std::memory_order_relaxed); dbg > 0 && dbg < max_blocks) max_blocks = dbg;
     const int64_t n_tiles = (n_nodes + 15) / 16;
     int64_t k = (n_tiles + max_blocks - 1) / max_blocks;
     // a power of two up to 8 tiles per block: the waves of a block then share its tiles evenly (8 / k waves per tile), and fewer
@@ -1135,4 +1133,3 @@ extern "C" int tgnn_debug_mid_timing(unsigned long long *out, int n_blocks) {
 extern "C" void tgnn_set_mid_layout_limit(int64_t n_nodes) { g_mid_limit.store(n_nodes < 0 ? 0 : n_nodes); }
 extern "C" int64_t tgnn_get_mid_layout_limit(void) { return g_mid_limit.load(); }
 extern "C" int64_t tgnn_mid_layout_max_nodes(void) { return 65536; }
-extern "C" void tgnn_debug_set_mid_blocks(int32_t blocks) { g_mid_blocks_cap.store(blocks < 0 ? 0 : blocks); }
