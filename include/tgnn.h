@@ -1026,6 +1026,11 @@ int tgnn_forward_bf16(const tgnn_model_dims *dims, const void *const *params_hos
  * with the same ws and node count waits for it and skips its own init MLP (the running-statistics update was applied here). */
 int tgnn_forward_bf16_begin(const tgnn_model_dims *dims, const void *const *params_host, const float *x, int64_t n_nodes,
                             int32_t update_running, void *ws, size_t ws_bytes, tgnn_stream_t stream2);
+/* Drops what tgnn_forward_bf16_begin left pending for this thread on `device` (-1: the current one), for a caller whose forward is
+ * refused between the two calls: without it, a later tgnn_forward_bf16 whose workspace happens to lie at the freed address and has
+ * the same node count would take the old init MLP for its own.  Host-side only: no launch, no synchronisation.  The caller orders
+ * its stream behind stream2 before it frees the workspace. */
+int tgnn_forward_bf16_drop(int32_t device);
 
 /* ---- tile-in-region predicate (csrc/region.hip): the reference's `contain` (util/algo_util.py:143-144) for K regions x all tiles
  * of a complete graph, in fp64, one launch (a fixed few for K > 65535); no host synchronisation, same bits from run to run.

@@ -243,15 +243,21 @@ def test_config3_new_layout_takes_the_early_init_mlp(dev, big):
             assert torch.equal(net.state_dict()[k], v), k
 
 
-def compose_forward(net, x, adj, attr, col):
+def compose_forward(net, x, adj, attr, col, graph=None, kernel=None):
     """TilinGNN.forward (TilinGNN.py:51-78) spelled out op by op with the per-op entry points validated above -- the checker
-    of the fused library call `tgnn_forward_bf16` (same kernels, same order: bit-identical probabilities)."""
+    of the fused library call `tgnn_forward_bf16` (same kernels, same order: bit-identical probabilities).
+    graph: the prepared layout (default: prepared here); kernel: the NNConv structure (`ops_bf16.nnconv64`).
+    -> (probs, intermediates, the deep copy of `net` whose running statistics this run has updated); intermediates: "mid" the
+    bf16 skip buffer [D + 1] x [N, 64], "h2" the collision branch's outputs, "a1" the pre-BatchNorm NNConv outputs, "f1" the
+    first final Linear's output (fp32 [N, 256], pre-BatchNorm) and "f1_stat" its BatchNorm record."""
     from tilingnn_amd import ops, ops_bf16
     import copy
     net = copy.deepcopy(net)                                   # running statistics are updated by both runs
     dev, n, D = x.device, int(x.shape[0]), net.network_depth
-    graph = ops.prepare_graph(n, adj, attr, col)
+    if graph is None:
+        graph = ops.prepare_graph(n, adj, attr, col)
     P = lambda c: ops.new_partials(c, dev)
+    inter = {"h2": [], "a1": []}
 
     def lin_bn(layer, a, in_stat):
         parts = P(layer.linear.out_features)
@@ -267,18 +273,21 @@ def compose_forward(net, x, adj, attr, col):
         h2 = ops_bf16.collconv64(h2, graph, g2.ginConv.eps, *g2.ginConv._mlp_params(), g2.batch_norm)
         wtab = ops.edge_weight_table(attr, graph, *g1.nnConv._edge_mlp_params(), W)
         p1 = P(W)
-        a1, np1 = ops_bf16.nnconv64(mid[i], graph, wtab, g1.nnConv.root, g1.nnConv.bias, ops.ACT_LEAKY_RELU, p1)
+        a1, np1 = ops_bf16.nnconv64(mid[i], graph, wtab, g1.nnConv.root, g1.nnConv.bias, ops.ACT_LEAKY_RELU, p1, kernel=kernel)
         st1 = ops.bn_finalize(p1, np1, n, g1.batch_norm, update_running=True)
         mid.append(ops_bf16.merge(a1, st1, h2, None, mid[i - 2] if i >= 2 else None))
+        inter["h2"].append(h2)
+        inter["a1"].append(a1)
     f = net.final_mlp[0].mlp
     pf = P(256)
     h, npf = ops_bf16.dense_slots(torch.stack(mid).contiguous(), f[0].linear.weight, f[0].linear.bias, ops.ACT_LEAKY_RELU, pf)
     st = ops.bn_finalize(pf, npf, n, f[0].batch_norm, update_running=True)
+    inter.update(mid=mid, f1=h, f1_stat=st)
     for layer in f[1:]:
         h, st = lin_bn(layer, h, st)
     last = net.final_mlp[1].linear
     probs, _ = ops.dense_act(h, last.weight, last.bias, ops.ACT_SIGMOID, in_stat=st)
-    return probs
+    return probs, inter, net
 
 
 @pytest.mark.parametrize("depth", [1, 3])
@@ -287,7 +296,8 @@ def test_library_forward_is_the_composition_of_its_ops(dev, depth):
     x3, adj, attr, col, _ = g
     x = torch.cat([x3, torch.zeros(x3.shape[0], 2, device=dev)], dim=1)[:, [0, 1, 3, 4, 2]].contiguous()
     net, _ = make_net(dev, depth=depth)
-    want = compose_forward(net, x, adj, attr, col)
+    want, inter, _ = compose_forward(net, x, adj, attr, col)
+    assert len(inter["mid"]) == depth + 1 and inter["f1"].shape == (1254, 256)
     net.activation_dtype = torch.bfloat16
     got = net(x=x, adj_e_index=adj, adj_e_features=attr, col_e_idx=col)[0]
     d = float((got - want).abs().max())

@@ -1475,6 +1475,17 @@ extern "C" int tgnn_forward_bf16_begin(const tgnn_model_dims *dims, const void *
     return TGNN_OK;
 }
 
+// a forward refused between tgnn_forward_bf16_begin and tgnn_forward_bf16: forget the pending init MLP (its workspace is freed by
+// the caller; the address comes back from the allocator for the next forward of the same size)
+extern "C" int tgnn_forward_bf16_drop(int32_t device) {
+    int dev = device;
+    if (dev < 0) TGNN_CHECK_HIP(hipGetDevice(&dev));
+    TGNN_CHECK_ARG(dev >= 0 && dev < 64, "device index");
+    g_head64[dev].ws = nullptr;
+    g_head64[dev].n = 0;
+    return TGNN_OK;
+}
+
 /* TilinGNN.forward (TilinGNN.py:51-78) at network_width 64 with bf16 activation storage; same parameter table, graph
  * structure and BatchNorm semantics as tgnn_forward.  Train mode only (the mode the reference runs inference in). */
 extern "C" int tgnn_forward_bf16(const tgnn_model_dims *dims, const void *const *params_host, const float *x,

@@ -131,6 +131,12 @@ def dense_slots(mid: Tensor, weight: Tensor, bias: Tensor, act: int, partials: O
     return out, npart.value
 
 
+def _drop_begun(dev) -> None:
+    """A forward refused behind tgnn_forward_bf16_begin: the library forgets the pending init MLP, so that the next forward whose
+    workspace the allocator puts at the freed address (same node count) runs its own.  Host-side only."""
+    check(lib.tgnn_forward_bf16_drop(dev.index if dev.index is not None else -1))
+
+
 def forward(net, x: Tensor, adj_e_index: Tensor, adj_e_features: Tensor, col_e_idx: Tensor, graph=None) -> Tensor:
     """`tgnn_forward_bf16`: the whole network with bf16 activation storage -> probs fp32 [N, output_dim]."""
     if net.network_width != WIDTH:
@@ -158,10 +164,12 @@ def forward(net, x: Tensor, adj_e_index: Tensor, adj_e_features: Tensor, col_e_i
         except Exception:
             if side is not None:                                   # (begin's launches write the workspace freed below)
                 torch.cuda.current_stream(dev).wait_stream(side)
+                _drop_begun(dev)
             raise
     if (graph.cols is None and graph.groups is None) or graph.n_types > max_types():
         if ws is not None:
             torch.cuda.current_stream(dev).wait_stream(_lib.side_stream_torch(dev))
+            _drop_begun(dev)
         raise ValueError(f"the bf16 path needs the NNConv type columns or edge groups and at most {max_types()} edge types")
     if ws is None:
         ws_bytes = lib.tgnn_forward_bf16_workspace_bytes(C.byref(dims), n, graph.n_types)
