@@ -185,6 +185,23 @@ int tgnn_nnconv_mean_eg_fwd(const float *h, int64_t ldh, int64_t n_src_rows, con
                             float *wimg_scratch, uint32_t *bounds_scratch, double *bn_partial, int32_t *n_partials_host,
                             tgnn_stream_t stream);
 
+/* The same op at network_width 64, fp32 in and out (csrc/nnconv64_eg.hip: nnconv64_eg_kernel), over the SAME edge-group structure:
+ * rows and weights as fp16 pairs (three matrix terms), the messages kept as an fp16 pair for the fold, the mean taken in fp32
+ * before the root product -- fp32 accuracy (2e-6 of the output's max-norm) on the matrix cores, where the generic kernel of
+ * tgnn_nnconv_mean_fwd runs one thread per output.  A block holds the weight images of one half of the output columns in LDS
+ * and walks its tiles twice: up to tgnn_nnconv64_eg_max_types() edge types (18; beyond: TGNN_ERR_UNSUPPORTED, tgnn_last_error
+ * names the limit).  No in-degree limit in the kernel; the edge-group structure is stated for in-degrees up to 2 048.
+ * tgnn_nnconv64_mean_eg_fwd is the op for tests, arguments as tgnn_nnconv_mean_eg_fwd (ldh == 64, n_src_rows * 256 < 2^31):
+ * wimg_scratch tgnn_nnconv64_eg_image_floats(n_types) floats, bounds_scratch 2 words; the bound of |h| and the weight image
+ * are computed inside.  BatchNorm partial rows: double [blocks][2][64] of the stored output. */
+int32_t tgnn_nnconv64_eg_max_types(void);
+size_t tgnn_nnconv64_eg_image_floats(int32_t n_types);
+int tgnn_nnconv64_mean_eg_fwd(const float *h, int64_t ldh, int64_t n_src_rows, const int32_t *tile_grp_ptr,
+                              const int32_t *grp, const float *wtab, int32_t n_types,
+                              const float *root, const float *bias, int64_t n_nodes, int32_t act, float *out,
+                              float *wimg_scratch, uint32_t *bounds_scratch, double *bn_partial, int32_t *n_partials_host,
+                              tgnn_stream_t stream);
+
 /* Measurement helper of bench.py (roofline.gather_bound; csrc/ubench.hip): rows of 128 bytes gathered per second by one launch
  * over every CU from an L2 / Infinity-Cache resident table of n_rows x 128 bytes (>= 8192 rows), band-local random rows, best of
  * `reps` launches of `iters` x 8 gather steps per wave.  shape 0 = the column NNConv's lane map (16 rows x 64 bytes per
@@ -320,7 +337,8 @@ typedef struct tgnn_graph {
     const int32_t *nn_mid_tile_nb;
     const uint32_t *nn_mid_ent;
     /* NNConv edge-group structure (tgnn_nnconv_eg_build; both NULL => the type columns, or the CSR kernel, are used).  The
-     * general schedule of the fp32 width-32 forward prefers it (tgnn_set_nnconv_eg; in-degrees up to 2048). */
+     * general schedule of the fp32 width-32 forward prefers it (tgnn_set_nnconv_eg; in-degrees up to 2048); the fp32 width-64
+     * forward runs its NNConv on it when tgnn_set_nnconv64_eg is on. */
     const int32_t *nn_tile_grp_ptr;
     const int32_t *nn_grp;
     /* [r6] NULL, or: a device word that is non-zero when nn_mid_tile_nb / nn_mid_ent turned out not to be usable (tgnn_graph_prep's
@@ -551,6 +569,12 @@ int32_t tgnn_set_mid_tail(int32_t on);
  * carries them, instead of over its type columns.  Default 1; returns the previous setting (an argument outside 0 .. 1 only
  * queries). */
 int32_t tgnn_set_nnconv_eg(int32_t on);
+/* General schedule, width 64, fp32 (tgnn_forward and tgnn_forward_train, single device, train-mode BatchNorm): the NNConv over the
+ * layout's edge groups on the matrix cores (csrc/nnconv64_eg.hip) instead of the generic kernel, when the graph carries groups,
+ * has 1 .. tgnn_nnconv64_eg_max_types() edge types, a known largest in-degree of 1 .. 2 048 and rows within 2 GB.  A forward on
+ * running statistics (eval mode) and the sharded forward stay on the generic kernel.  Default 0; returns the previous setting (an
+ * argument outside 0 .. 1 only queries). */
+int32_t tgnn_set_nnconv64_eg(int32_t on);
 /* The final MLP's fp16-pair Linears for many rows (csrc/dense.hip; reference: graph_networks/networks/TilinGNN.py:74-76).  Bit 1
  * (default on): the BatchNorm-on-load layers 256 -> 128 -> 64 on dense_f16_resident_kernel (W's operand image resident in LDS, no
  * barrier in the k loop, 16 KB requests per wave).  Bit 0 (default off; an experiment that measured slower): dense_f16_rows2_kernel

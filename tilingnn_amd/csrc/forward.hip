@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "forward_plan.h"
+#include "nnconv64_eg.h"
 #include "tgnn_common.h"
 
 namespace tgnn {
@@ -81,6 +82,8 @@ static bool dims_ok(const tgnn_model_dims *d) {
 
 struct Workspace {
     float *mid, *a1, *a2[2], *t0, *f1, *f2, *f3, *f4, *wtab, *wimg;
+    float *wimg64;                // width 64: fp16-pair images of the edge-group NNConv, all layers (nnconv64_eg.hip)
+    unsigned *bounds64;           // width 64: [0, D) max |middle[i]| as float bits (zeroed per forward), [D, 2 D) max |root_i|
     double *part1, *part2, *partf;
     float *small_pack;            // small-layout kernel: per-layer parameter packs, its partial rows, its barrier counter
     double *small_part, *small_part_wide, *small_runstat;
@@ -135,6 +138,7 @@ static const int kFinalDims[4] = {256, 128, 64, 0};  // TilinGNN.py:46 hidden_la
 static_assert(kPlanMaxDepth == kMaxDepth, "forward_plan.h plans for the depth the kernels take");
 static std::atomic<int> g_split_f16{1};              // tgnn_set_split_precision
 static std::atomic<int> g_nnconv_eg{1};              // tgnn_set_nnconv_eg
+static std::atomic<int> g_nnconv64_eg{0};            // tgnn_set_nnconv64_eg
 static std::atomic<int> g_lean_head{3};              // tgnn_set_lean_head: bit 0 the head without memsets / early edge-weight event, bit 1 the fused init MLP, bit 2 the final MLP's folded BatchNorm records
 static std::atomic<int64_t> g_path_count[3];          // forwards queued on the general schedule / small-layout kernel / mid-size kernel
 static std::atomic<int64_t> g_union_count[2];         // tgnn_forward_union: persistent launches / layouts scored inside them
@@ -180,6 +184,11 @@ static Workspace carve(const tgnn_model_dims &d, int64_t n, int64_t nr, int32_t 
     w.stat_i[0] = cv.take<float>(4 * c);
     w.stat_i[1] = cv.take<float>(4 * c);
     for (int l = 0; l < 4; ++l) w.stat_f[l] = cv.take<float>(4 * 256);
+    if (c == 64) {                // (behind everything else: no other piece moves)
+        const int t64 = tc < nnconv64_eg_max_types() ? tc : nnconv64_eg_max_types();
+        w.wimg64 = cv.take<float>((size_t)D * (t64 + 1) * kEg64TypeFloats);
+        w.bounds64 = cv.take<unsigned>(2 * kMaxDepth);
+    }
     w.bytes = cv.off + 256;
     return w;
 }
@@ -197,6 +206,10 @@ extern "C" int32_t tgnn_set_split_precision(int32_t mode) {
 extern "C" int32_t tgnn_set_nnconv_eg(int32_t on) {
     if (on != 0 && on != 1) return g_nnconv_eg.load();
     return g_nnconv_eg.exchange(on);
+}
+extern "C" int32_t tgnn_set_nnconv64_eg(int32_t on) {
+    if (on != 0 && on != 1) return g_nnconv64_eg.load();
+    return g_nnconv64_eg.exchange(on);
 }
 extern "C" int32_t tgnn_set_lean_head(int32_t bits) {
     if (bits < 0 || bits > 7) return g_lean_head.load();
@@ -550,6 +563,7 @@ struct Forward {
     // taken on the side stream with the other two (nobody needs it before the final MLP)
     int queue_head() {
         if (plan.weights_done == WeightsDoneWord::SmallCtr) TGNN_CHECK_HIP(hipMemsetAsync(weights_done, 0, 4, s));
+        if (plan.eg64) TGNN_CHECK_HIP(hipMemsetAsync(w.bounds64, 0, (size_t)D * sizeof(unsigned), s));   // (the layers' max |h| words)
         if (plan.scales == ScalesKernel::Lean || plan.scales == ScalesKernel::Full) {
             const float *roots[kMaxDepth];
             for (int i = 0; i < D; ++i) roots[i] = P.f(P.layer(i) + 6);
@@ -590,6 +604,12 @@ struct Forward {
             launch_edge_weight_table_batched(adj_edge_attr, graph->type_rep_edge, T, fe, em.layers, D, c, w.wtab, plan.tiled ? em.roots : nullptr,
                                              plan.tiled ? w.wimg : nullptr, sw, weights_done, root_max, plan.eg ? kEgImageScale : 1.0f);
             prof.end();
+            // width 64 on edge groups: the fp16-pair images of all layers from the table just queued, behind it on the same stream
+            if (plan.eg64) {
+                prof.begin(0);
+                launch_nnconv64_eg_images(w.wtab, em.roots, T, D, w.wimg64, w.bounds64 + D, sw);
+                prof.end();
+            }
         }
         // [r6] the layer loop waits for the edge weights alone: the event sits in front of the final MLP's bounds and images (they
         // are joined with the collision chain, which the last merge waits for) -- 12 us of idle main stream in front of the first NNConv
@@ -818,7 +838,12 @@ struct Forward {
         const int b = P.layer(i);
         const float *h1 = slot(i);
         prof.begin(2);
-        if (plan.eg) {
+        if (plan.eg64) {
+            // the bound of |h| the row split scales by: one read of the slot in front of the kernel it enables
+            launch_absmax(h1, nr * c, w.bounds64 + i, s);
+            TGNN_TRY(launch_nnconv64_eg(h1, nr, graph->nn_tile_grp_ptr, graph->nn_grp, w.wimg64 + (size_t)i * (T + 1) * kEg64TypeFloats, T,
+                                        P.f(b + 7), n, TGNN_ACT_LEAKY_RELU, w.a1, w.part1, &np1, s, w.bounds64 + i, w.bounds64 + D + i));
+        } else if (plan.eg) {
             EgShardPack pk{};
             if (pack_in_nnconv(i))
                 pk = EgShardPack{sh->send_row_ptr, sh->send_row_slot, sh->send_buf, sh->send_idx_fused, shard_rows_out(),
@@ -1085,7 +1110,7 @@ static int forward_impl(const tgnn_model_dims *dims, const void *const *params_h
     f.weights_early = ho.weights_early;
     f.edge_table_device_count_ok = edge_weight_table_device_count_ok(f.fe, f.c);
     f.device_cus = device_cus();
-    f.split_f16 = g_split_f16.load(); f.nnconv_eg = g_nnconv_eg.load(); f.lean_head = g_lean_head.load(std::memory_order_relaxed);
+    f.split_f16 = g_split_f16.load(); f.nnconv_eg = g_nnconv_eg.load(); f.nnconv64_eg = g_nnconv64_eg.load(); f.lean_head = g_lean_head.load(std::memory_order_relaxed);
     f.mid_init_in_kernel = mid_init_in_kernel();
 
     hipStream_t s2 = side_stream_used(f) ? side : nullptr;

@@ -388,7 +388,7 @@ class TilinGNN(Tracked, nn.Module):
         # without waiting, with the DEVICE address of that verdict in the graph struct -- the persistent kernels read it first and
         # leave without output or update when the batches do not fit (tgnn_graph.nn_mid_verdict); the host looks at the word behind
         # its launches and then runs the general schedule, whose update is this forward's one
-        g = graph.c_struct(defer_late_check=True)
+        g = ops.c_struct_for_width(graph, self.network_width, defer_late_check=True)   # (width 64: + edge groups, if switched on)
         if begun:
             check(lib.tgnn_forward_resume(C.byref(dims), table, ptr(xf), ptr(ea), C.byref(g), int(update_running), ptr(probs), ptr(ws),
                                           ws_bytes, _lib.current_stream(dev), _lib.side_stream(dev)))

@@ -591,6 +591,32 @@ def graph_columns(graph: PreparedGraph) -> Optional[NNConvColumns]:
     return hit
 
 
+NNCONV64_EG_MAX_IN_DEGREE = 2048      # csrc/nnconv64_eg_plan.h: what the edge-group structure is stated for
+
+
+def set_nnconv64_eg(on: int) -> int:
+    """Width-64 fp32 forwards (inference and training) run their NNConv on edge groups on the matrix cores (tgnn_set_nnconv64_eg;
+    default off).  Returns the previous setting; anything but 0 / 1 only queries."""
+    return int(lib.tgnn_set_nnconv64_eg(int(on)))
+
+
+def c_struct_for_width(graph: PreparedGraph, c: int, defer_late_check: bool = False) -> _lib.Graph:
+    """The graph's C struct as a forward of width `c` takes it: with tgnn_set_nnconv64_eg on, a width-64 forward gets the
+    layout's edge groups (built on first use: small layouts are prepared with columns only) in a COPY of the struct -- the
+    graph itself, which width-32 forwards may share through the cache, stays as it was prepared."""
+    g = graph.c_struct(defer_late_check)
+    if c != 64 or lib.tgnn_set_nnconv64_eg(-1) != 1 or graph.groups is not None:
+        return g
+    if not (1 <= graph.n_types <= int(lib.tgnn_nnconv64_eg_max_types()) and 1 <= graph.max_in_degree <= NNCONV64_EG_MAX_IN_DEGREE):
+        return g
+    grp = graph_groups(graph)
+    if grp is None:
+        return g
+    g = _lib.Graph.from_buffer_copy(g)
+    g.nn_tile_grp_ptr, g.nn_grp = grp.tile_grp_ptr.data_ptr(), grp.grp.data_ptr()
+    return g
+
+
 def graph_groups(graph: PreparedGraph) -> Optional[NNConvGroups]:
     """The graph's edge groups, built on first use when the preparation left them out."""
     if graph.groups is not None:
@@ -629,7 +655,8 @@ def nnconv_mean(h: Tensor, graph: PreparedGraph, wtab: Tensor, root: Tensor, bia
     """NNConv mean: the matrix-core column kernel when the graph carries the column structure, else the CSR /
     LDS-weight-table kernel (any type count that fits LDS) or the generic one.  kernel: None = that order; "cols_f16" = the
     column kernel with the fp16 x 2 split as tgnn_forward runs it (max_in_degree: the bound to scale by, default the
-    layout's)."""
+    layout's); "eg" = the edge-group kernel of the width (32, or 64: the groups are built on first use; ValueError beyond
+    its limits)."""
     h = _f32c(h, "x")
     c = int(h.shape[1])
     n = graph.n_nodes                      # destination rows; x may carry extra (halo) rows behind them
@@ -643,10 +670,23 @@ def nnconv_mean(h: Tensor, graph: PreparedGraph, wtab: Tensor, root: Tensor, bia
     if kernel is None and graph.groups is not None and c == 32 and not force_csr_kernel and 1 <= graph.max_in_degree <= 2048 \
             and int(h.shape[0]) * c * 4 < 2 ** 31:
         kernel = "eg"                          # a layout that carries edge groups: the kernel tgnn_forward runs on it
+    if kernel == "eg" and c == 64:             # fp32 at width 64: nnconv64_eg_kernel (csrc/nnconv64_eg.hip)
+        t_max, d_max = int(lib.tgnn_nnconv64_eg_max_types()), NNCONV64_EG_MAX_IN_DEGREE
+        grp = graph_groups(graph) if graph.n_types <= t_max and graph.max_in_degree <= d_max else None
+        if grp is None or int(h.shape[0]) * 256 >= 2 ** 31:
+            raise ValueError(f"the width-64 edge-group kernel takes at most {t_max} edge types, in-degrees up to {d_max} and "
+                             f"rows within 2 GB: this layout has {graph.n_types} types, in-degree {graph.max_in_degree}, "
+                             f"{int(h.shape[0])} rows")
+        wimg = torch.empty(lib.tgnn_nnconv64_eg_image_floats(graph.n_types), dtype=torch.float32, device=h.device)
+        bounds = torch.empty(2, dtype=torch.int32, device=h.device)
+        check(lib.tgnn_nnconv64_mean_eg_fwd(ptr(h), c, int(h.shape[0]), ptr(grp.tile_grp_ptr), ptr(grp.grp), ptr(wt), graph.n_types,
+                                            ptr(_f32c(root, "root")), ptr(_f32c(bias, "bias")), n, act, ptr(out), ptr(wimg), ptr(bounds),
+                                            ptr(partials), C.byref(npart), _stream(h)))
+        return out, npart.value
     if kernel == "eg":
         grp = graph_groups(graph)
         if grp is None or c != 32:
-            raise ValueError("the edge-group kernel needs <= 40 edge types and width 32")
+            raise ValueError("the edge-group kernel needs <= 40 edge types and width 32 (or 64: nnconv64_eg_kernel)")
         wimg = torch.empty(lib.tgnn_nnconv_weight_image_floats(graph.n_types), dtype=torch.float32, device=h.device)
         bounds = torch.empty(2, dtype=torch.int32, device=h.device)
         check(lib.tgnn_nnconv_mean_eg_fwd(ptr(h), c, int(h.shape[0]), ptr(grp.tile_grp_ptr), ptr(grp.grp), ptr(wt), graph.n_types, ptr(_f32c(root, "root")), ptr(_f32c(bias, "bias")), n, act,

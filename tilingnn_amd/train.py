@@ -243,7 +243,7 @@ def forward_train(net, x: Tensor, adj_e_index: Tensor, adj_e_features: Tensor, c
     dims = net._dims()
     ws_bytes = lib.tgnn_forward_workspace_bytes(C.byref(dims), n, T)
     ws = _Scratch.get("fwd", ws_bytes, dev)
-    gs = g.c_struct()
+    gs = ops.c_struct_for_width(g, c)                  # (width 64: + the layout's edge groups, if tgnn_set_nnconv64_eg is on)
     check(lib.tgnn_forward_train(C.byref(dims), table, ptr(xf), ptr(ea), C.byref(gs), C.byref(keep), ptr(probs), ptr(ws),
                                  ws_bytes, _lib.current_stream(dev), _lib.side_stream(dev)))
     sv.keep, sv._keep_alive = keep, (a1, a2, u, st1, st2, wtab)
