@@ -246,6 +246,18 @@ int tgnn_gin_fwd(const float *a, int64_t lda, const float *in_stat, const int32_
                  const float *w2, const float *b2, const float *w3, const float *b3, int64_t n_nodes,
                  int32_t c, int32_t act, float *out, float *z_scratch, double *bn_partial,
                  int32_t *n_partials_host, tgnn_stream_t stream);
+/* The same op at C = 64 on the matrix cores (csrc/gin64_mlp.hip: gin64_mlp_kernel), fp32 in and out: the neighbourhood sum by the
+ * gather kernel of tgnn_gin_aggregate into z_scratch [N][64] (16-byte aligned; left there: z_scratch IS the aggregate the MLP read),
+ * then the MLP 64 -> 32 -> 64 -> 64 with every fp32 operand as three bf16 pieces (six matrix terms), the output sigmoid at full
+ * accuracy -- 1e-6 of the output's max-norm against fp64, where tgnn_gin_fwd at this width runs one wave per row on the vector
+ * units.  lda >= 64; lda % 4 != 0 or a / out / z_scratch not 16-byte aligned: TGNN_ERR_UNSUPPORTED (tgnn_last_error says which).
+ * act: TGNN_ACT_NONE or TGNN_ACT_LEAKY_RELU.  n_nodes == 0: TGNN_OK, 0 partial rows.  BatchNorm partial rows (bn_partial may be
+ * NULL): double [blocks][sum 64 | sum of squares 64] of the stored output, blocks <= 512, summed in a fixed order (the same bits
+ * on every call). */
+int tgnn_gin64_fwd(const float *a, int64_t lda, const float *in_stat, const int32_t *rowptr, const int32_t *col_src,
+                   const float *eps, const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
+                   const float *b3, int64_t n_nodes, int32_t act, float *out, float *z_scratch, double *bn_partial,
+                   int32_t *n_partials_host, tgnn_stream_t stream);
 
 /* Linear_trans (layers/util.py:31-37) without its BatchNorm:  out = act(f(A) . W^T + b).
  * A is given as ceil(in_dim/32) column blocks of 32: element (r, k) lives at
@@ -575,6 +587,11 @@ int32_t tgnn_set_nnconv_eg(int32_t on);
  * running statistics (eval mode) and the sharded forward stay on the generic kernel.  Default 0; returns the previous setting (an
  * argument outside 0 .. 1 only queries). */
 int32_t tgnn_set_nnconv64_eg(int32_t on);
+/* General schedule, width 64, fp32 (tgnn_forward and tgnn_forward_train, single device, either BatchNorm mode): the collision
+ * branch's GINConv as the gather kernel plus gin64_mlp_kernel (tgnn_gin64_fwd's two launches) instead of the generic kernel.  The
+ * training forward keeps the aggregate where the backward reads it, as before.  The sharded forward and the bf16-storage path
+ * are not routed.  Default 0; returns the previous setting (an argument outside 0 .. 1 only queries). */
+int32_t tgnn_set_gin64_mfma(int32_t on);
 /* The final MLP's fp16-pair Linears for many rows (csrc/dense.hip; reference: graph_networks/networks/TilinGNN.py:74-76).  Bit 1
  * (default on): the BatchNorm-on-load layers 256 -> 128 -> 64 on dense_f16_resident_kernel (W's operand image resident in LDS, no
  * barrier in the k loop, 16 KB requests per wave).  Bit 0 (default off; an experiment that measured slower): dense_f16_rows2_kernel

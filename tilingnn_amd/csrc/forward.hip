@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "forward_plan.h"
+#include "gin64_mlp.h"
 #include "nnconv64_eg.h"
 #include "tgnn_common.h"
 
@@ -139,6 +140,7 @@ static_assert(kPlanMaxDepth == kMaxDepth, "forward_plan.h plans for the depth th
 static std::atomic<int> g_split_f16{1};              // tgnn_set_split_precision
 static std::atomic<int> g_nnconv_eg{1};              // tgnn_set_nnconv_eg
 static std::atomic<int> g_nnconv64_eg{0};            // tgnn_set_nnconv64_eg
+static std::atomic<int> g_gin64_mfma{0};             // tgnn_set_gin64_mfma
 static std::atomic<int> g_lean_head{3};              // tgnn_set_lean_head: bit 0 the head without memsets / early edge-weight event, bit 1 the fused init MLP, bit 2 the final MLP's folded BatchNorm records
 static std::atomic<int64_t> g_path_count[3];          // forwards queued on the general schedule / small-layout kernel / mid-size kernel
 static std::atomic<int64_t> g_union_count[2];         // tgnn_forward_union: persistent launches / layouts scored inside them
@@ -210,6 +212,10 @@ extern "C" int32_t tgnn_set_nnconv_eg(int32_t on) {
 extern "C" int32_t tgnn_set_nnconv64_eg(int32_t on) {
     if (on != 0 && on != 1) return g_nnconv64_eg.load();
     return g_nnconv64_eg.exchange(on);
+}
+extern "C" int32_t tgnn_set_gin64_mfma(int32_t on) {
+    if (on != 0 && on != 1) return g_gin64_mfma.load();
+    return g_gin64_mfma.exchange(on);
 }
 extern "C" int32_t tgnn_set_lean_head(int32_t bits) {
     if (bits < 0 || bits > 7) return g_lean_head.load();
@@ -770,6 +776,14 @@ struct Forward {
             return rc;                                         // (TGNN_ERR_UNSUPPORTED: the workspace is aligned, cannot happen)
         }
         prof.begin(3);
+        if (plan.gin64) {
+            // width 64 on the matrix cores: the aggregate into t0 (the training forward's keep->u: where the backward looks for
+            // it), the MLP kernel on it -- inference and training alike
+            TGNN_TRY(gin64_fwd(gin_in, c, gin_stat, graph->col_rowptr, graph->col_src, P.f(b + 13), P.f(b + 14), P.f(b + 15), P.f(b + 16),
+                               P.f(b + 17), P.f(b + 18), P.f(b + 19), n, TGNN_ACT_LEAKY_RELU, w.a2[i & 1], w.t0, w.part2, &np2, gs));
+            prof.end();
+            return TGNN_OK;
+        }
         if (keep && c != 32) {
             // training at width 64: the generic kernel (the one inference runs at this width) also stores the aggregate, keep->u
             TGNN_TRY(gin_generic_fwd_keep(gin_in, c, gin_stat, graph->col_rowptr, graph->col_src, P.f(b + 13), P.f(b + 14),
@@ -1110,7 +1124,7 @@ static int forward_impl(const tgnn_model_dims *dims, const void *const *params_h
     f.weights_early = ho.weights_early;
     f.edge_table_device_count_ok = edge_weight_table_device_count_ok(f.fe, f.c);
     f.device_cus = device_cus();
-    f.split_f16 = g_split_f16.load(); f.nnconv_eg = g_nnconv_eg.load(); f.nnconv64_eg = g_nnconv64_eg.load(); f.lean_head = g_lean_head.load(std::memory_order_relaxed);
+    f.split_f16 = g_split_f16.load(); f.nnconv_eg = g_nnconv_eg.load(); f.nnconv64_eg = g_nnconv64_eg.load(); f.gin64_mfma = g_gin64_mfma.load(); f.lean_head = g_lean_head.load(std::memory_order_relaxed);
     f.mid_init_in_kernel = mid_init_in_kernel();
 
     hipStream_t s2 = side_stream_used(f) ? side : nullptr;

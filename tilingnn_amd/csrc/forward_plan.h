@@ -8,6 +8,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "gin64_plan.h"
 #include "nnconv64_eg_plan.h"
 
 namespace tgnn {
@@ -47,6 +48,7 @@ struct ForwardFacts {
     // switches
     int split_f16 = 1, nnconv_eg = 1, lean_head = 3;
     int nnconv64_eg = 0;               // tgnn_set_nnconv64_eg
+    int gin64_mfma = 0;                // tgnn_set_gin64_mfma
     bool mid_init_in_kernel = false;
 };
 
@@ -64,6 +66,7 @@ struct ForwardPlan {
     bool verdict_refused = false;      // nn_mid_verdict given, but the forward is not the two persistent kernels alone
     bool f16 = false, eg = false, tiled = false, lean_head = false;
     bool eg64 = false;                 // width 64, fp32: the NNConv on edge groups (nnconv64_eg.hip) instead of the generic kernel
+    bool gin64 = false;                // width 64, fp32: the GIN MLP on the matrix cores (gin64_mlp.hip) instead of the generic kernel
     bool init_fused_early = false, init_fused = false, head_used = false;
     bool weights_on_main = false, weights_queued = false, small_pre_used = false;
     WeightsDoneWord weights_done = WeightsDoneWord::None;
@@ -117,6 +120,7 @@ ForwardPlan plan_forward(const ForwardFacts &f, Probe &probe) {
     p.tiled = p.cols_ok || p.eg;
     // width 64 (general schedule, nothing above applies): the NNConv alone changes kernels, everything else stays as it is
     p.eg64 = nnconv64_eg_ok(f.c, sh, f.has_groups, f.nr, f.T, f.max_in_degree, urs, f.nnconv64_eg);
+    p.gin64 = gin64_mfma_ok(f.c, sh, f.gin64_mfma);           // (either BatchNorm mode: the kernel needs no bound of its operand)
     // the persistent kernels, with CUs to spare for the edge-weight kernel's blocks, wait for the edge weights on a counter of that
     // kernel's finished blocks instead of the host's event
     p.mid_counter = p.mid_k && p.mid_blocks + 16 <= f.device_cus && p.side;

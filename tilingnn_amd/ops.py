@@ -714,8 +714,18 @@ def nnconv_mean(h: Tensor, graph: PreparedGraph, wtab: Tensor, root: Tensor, bia
     return out, npart.value
 
 
+def set_gin64_mfma(on: int) -> int:
+    """Width-64 fp32 forwards (inference and training) run the collision branch's GIN MLP on the matrix cores
+    (tgnn_set_gin64_mfma; default off).  Returns the previous setting; anything but 0 / 1 only queries."""
+    return int(lib.tgnn_set_gin64_mfma(int(on)))
+
+
 def gin(a: Tensor, graph: PreparedGraph, eps: Tensor, w1, b1, w2, b2, w3, b3, act: int = ACT_NONE,
-        in_stat: Optional[Tensor] = None, partials: Optional[Tensor] = None) -> Tuple[Tensor, int]:
+        in_stat: Optional[Tensor] = None, partials: Optional[Tensor] = None, kernel: Optional[str] = None) -> Tuple[Tensor, int]:
+    """GINConv + activation.  kernel: None = tgnn_gin_fwd (the matrix-core kernels at width 32, the generic one elsewhere);
+    "mfma" = the width-64 matrix-core kernel (tgnn_gin64_fwd; ValueError at any other width)."""
+    if kernel not in (None, "mfma"):
+        raise ValueError(f"unknown GIN kernel {kernel!r}")
     a = _f32c(a, "x")
     c = int(a.shape[1])
     n = graph.n_nodes                      # destination rows; x may carry extra (halo) rows behind them
@@ -727,6 +737,12 @@ def gin(a: Tensor, graph: PreparedGraph, eps: Tensor, w1, b1, w2, b2, w3, b3, ac
     z_scratch = torch.empty(n, c, dtype=torch.float32, device=a.device)
     npart = C.c_int32(0)
     ps = [_f32c(p, "gin parameter") for p in (eps, w1, b1, w2, b2, w3, b3)]
+    if kernel == "mfma":
+        if c != 64:
+            raise ValueError(f"the matrix-core GIN kernel selected by kernel=\"mfma\" is the width-64 one: x has width {c}")
+        check(lib.tgnn_gin64_fwd(ptr(a), c, ptr(in_stat), ptr(graph.col_rowptr), ptr(graph.col_src), *[ptr(p) for p in ps],
+                                 n, act, ptr(out), ptr(z_scratch), ptr(partials), C.byref(npart), _stream(a)))
+        return out, npart.value
     check(lib.tgnn_gin_fwd(ptr(a), c, ptr(in_stat), ptr(graph.col_rowptr), ptr(graph.col_src), *[ptr(p) for p in ps],
                            n, c, act, ptr(out), ptr(z_scratch), ptr(partials), C.byref(npart), _stream(a)))
     return out, npart.value
