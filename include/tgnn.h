@@ -246,6 +246,21 @@ int tgnn_gin_fwd(const float *a, int64_t lda, const float *in_stat, const int32_
                  const float *w2, const float *b2, const float *w3, const float *b3, int64_t n_nodes,
                  int32_t c, int32_t act, float *out, float *z_scratch, double *bn_partial,
                  int32_t *n_partials_host, tgnn_stream_t stream);
+/* The same op at C = 32 with the form chosen by the caller instead of by the process-wide switches (csrc/gin32_plan.h) -- the launch
+ * code tgnn_forward runs, without a folded BatchNorm finalize:
+ *   variant 0: the gather kernel into z_scratch, then gin32_mlp_kernel (every operand as three bf16 pieces): tgnn_gin_fwd's two launches;
+ *   variant 1: the gather kernel, then gin32_mlp16_kernel (layers 2 / 3 on fp16 pairs scaled by powers of two from max |W2|, max |W3|):
+ *              what tgnn_set_gin_mlp_f16(1) selects inside the forward;
+ *   variant 2: gin32_fused_kernel, one launch, z_scratch untouched (may be NULL): what tgnn_set_gin_fused selects.  Its rows are
+ *              bit-identical to variant 0's.
+ * TGNN_ERR_UNSUPPORTED (tgnn_last_error says which; nothing is launched): c != 32; lda % 4 != 0 or a / out / z_scratch not 16-byte
+ * aligned; n_nodes * 128 >= 2^31; for variants 1 and 2 also act != TGNN_ACT_LEAKY_RELU or lda != 32.  There is no fall-back to the
+ * generic kernel.  n_nodes == 0: TGNN_OK, 0 partial rows.  BatchNorm partial rows (bn_partial may be NULL): double [blocks][sum 32 |
+ * sum of squares 32] of the stored output, summed in a fixed order (the same bits on every call). */
+int tgnn_gin32_fwd(const float *a, int64_t lda, const float *in_stat, const int32_t *rowptr, const int32_t *col_src,
+                   const float *eps, const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
+                   const float *b3, int64_t n_nodes, int32_t c, int32_t act, int32_t variant, float *out, float *z_scratch,
+                   double *bn_partial, int32_t *n_partials_host, tgnn_stream_t stream);
 /* The same op at C = 64 on the matrix cores (csrc/gin64_mlp.hip: gin64_mlp_kernel), fp32 in and out: the neighbourhood sum by the
  * gather kernel of tgnn_gin_aggregate into z_scratch [N][64] (16-byte aligned; left there: z_scratch IS the aggregate the MLP read),
  * then the MLP 64 -> 32 -> 64 -> 64 with every fp32 operand as three bf16 pieces (six matrix terms), the output sigmoid at full

@@ -126,6 +126,7 @@ def _load() -> C.CDLL:
         "tgnn_persist_fallback": (None, [i64]),
         "tgnn_spin_error_peek": (C.c_uint32, []),
         "tgnn_gin_fwd": (C.c_int, [p, i64, p, p, p, p, p, p, p, p, p, p, i64, i32, i32, p, p, p, pi32, p]),
+        "tgnn_gin32_fwd": (C.c_int, [p, i64, p, p, p, p, p, p, p, p, p, p, i64, i32, i32, i32, p, p, p, pi32, p]),
         "tgnn_gin64_fwd": (C.c_int, [p, i64, p, p, p, p, p, p, p, p, p, p, i64, i32, p, p, p, pi32, p]),
         "tgnn_dense_act_fwd": (C.c_int, [p, i64, i64, p, p, p, i64, i32, i32, i32, p, i64, p, pi32, p]),
         "tgnn_dense_act_slots_fwd": (C.c_int, [p, i32, i64, p, p, p, i64, i32, i32, i32, p, i64, p, pi32, p]),
@@ -279,7 +280,7 @@ EXPORTED_SYMBOLS = (
     "tgnn_nnconv_mean_fwd", "tgnn_nnconv_cols_max_columns", "tgnn_nnconv_cols_workspace_bytes",
     "tgnn_nnconv_cols_build", "tgnn_nnconv_cols_max_types", "tgnn_nnconv_weight_image_floats", "tgnn_nnconv_mean_cols_fwd", "tgnn_nnconv_mean_cols_f16_fwd", "tgnn_nnconv_eg_max_groups", "tgnn_nnconv_eg_build", "tgnn_nnconv_mean_eg_fwd",
     "tgnn_nnconv64_eg_max_types", "tgnn_nnconv64_eg_image_floats", "tgnn_nnconv64_mean_eg_fwd", "tgnn_set_nnconv64_eg",
-    "tgnn_gin64_fwd", "tgnn_set_gin64_mfma",
+    "tgnn_gin64_fwd", "tgnn_set_gin64_mfma", "tgnn_gin32_fwd",
     "tgnn_ubench_row_gather", "tgnn_mid_entries_words", "tgnn_mid_entries_build", "tgnn_forward_path_counts", "tgnn_set_mid_layout_limit", "tgnn_get_mid_layout_limit", "tgnn_mid_layout_max_nodes",
     "tgnn_spin_error_poll", "tgnn_set_spin_budget_us", "tgnn_persist_fallback", "tgnn_spin_error_peek", "tgnn_gin_fwd", "tgnn_dense_act_fwd", "tgnn_dense_act_slots_fwd", "tgnn_dense_act_slots_f16_fwd", "tgnn_bn_finalize", "tgnn_bn_apply",
     "tgnn_merge_fwd", "tgnn_param_count", "tgnn_param_name", "tgnn_forward_workspace_bytes", "tgnn_forward", "tgnn_forward_begin", "tgnn_forward_resume",

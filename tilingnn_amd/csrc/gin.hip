@@ -24,6 +24,7 @@
 #include <stdlib.h>
 
 #include "forward_persist.h"
+#include "gin32_plan.h"
 
 namespace tgnn {
 
@@ -106,6 +107,8 @@ __global__ __launch_bounds__(256) void gin_aggregate_kernel(
 // tiles-per-SIMD quantisation of 32-row tiles were the cost); this one: see profiles/.
 // ------------------------------------------------------------------------------------------
 constexpr int kMlpWaves = 8, kMlpThreads = kMlpWaves * 64;
+static_assert(kGin32BlockRows == kGin32TileRows * kMlpWaves && kGin32MaxPartials == TGNN_BN_MAX_PARTIALS &&
+              kGin32ActLeakyRelu == TGNN_ACT_LEAKY_RELU, "gin32_plan.h restates these");
 constexpr int kGinGroupRow0 = TGNN_BN_MAX_PARTIALS - 16;      // [r6] the 16 group rows of gin32_mlp_kernel's two-level BatchNorm fold
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
@@ -147,15 +150,8 @@ __global__ __launch_bounds__(kMlpThreads, 2) void gin32_mlp_kernel(
 #endif
 
     // ---- tile share of this wave (16-row tiles): balanced per SIMD (waves w, w + 4 of a block run on SIMD w & 3)
-    const int64_t n_tiles = (n + 15) / 16;
-    const int nblk = gridDim.x;
-    int64_t blk = blockIdx.x;
-    if (nblk >= 8 && (nblk & 7) == 0) blk = (int64_t)(blockIdx.x & 7) * (nblk >> 3) + (blockIdx.x >> 3);
-    const int64_t slot = blk * 4 + (wave & 3), n_slots = (int64_t)nblk * 4;
-    const int64_t q0 = n_tiles * slot / n_slots, q1 = n_tiles * (slot + 1) / n_slots;
-    constexpr int kSubs = kMlpWaves / 4;
-    const int sub = wave >> 2;
-    const int64_t t0 = q0 + (q1 - q0) * sub / kSubs, t1 = q0 + (q1 - q0) * (sub + 1) / kSubs;
+    const Gin32Tiles share = gin32_wave_share(n, (int)gridDim.x, (int)blockIdx.x, wave);   // gin32_plan.h
+    const int64_t t0 = share.t0, t1 = share.t1;
 
     // Z rows of a tile: lane (n, q) reads floats 8 q .. 8 q + 7 of row n; one tile ahead
     auto load_z = [&](int64_t tile, float4 (&zin)[2]) {
@@ -393,15 +389,8 @@ __global__ __launch_bounds__(kMlp16Threads) void gin32_mlp16_kernel(
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fn = lane & 15, fq = lane >> 4;
 
-    const int64_t n_tiles = (n + 15) / 16;
-    const int nblk = gridDim.x;
-    int64_t blk = blockIdx.x;
-    if (nblk >= 8 && (nblk & 7) == 0) blk = (int64_t)(blockIdx.x & 7) * (nblk >> 3) + (blockIdx.x >> 3);
-    const int64_t slot = blk * 4 + (wave & 3), n_slots = (int64_t)nblk * 4;
-    const int64_t q0 = n_tiles * slot / n_slots, q1 = n_tiles * (slot + 1) / n_slots;
-    constexpr int kSubs = kMlp16Waves / 4;
-    const int sub = wave >> 2;
-    const int64_t t0 = q0 + (q1 - q0) * sub / kSubs, t1 = q0 + (q1 - q0) * (sub + 1) / kSubs;
+    const Gin32Tiles share = gin32_wave_share(n, (int)gridDim.x, (int)blockIdx.x, wave);   // gin32_plan.h
+    const int64_t t0 = share.t0, t1 = share.t1;
 
     auto load_z = [&](int64_t tile, float4 (&zin)[2]) {
         int64_t zr = tile * 16 + fn;                        // clamped, unconditional: rows >= n are masked at the store
@@ -657,12 +646,9 @@ __global__ __launch_bounds__(kFusedThreads) void gin32_fused_kernel(
     __syncthreads();
 
     // the tile share of a team (= of a SIMD): as gin32_mlp_kernel shares the tiles out over the SIMD slots of the grid
-    const int64_t n_tiles = (n + 15) / 16;
-    const int nblk = gridDim.x, team = wave & 3, role = wave >> 2;   // role 0: the MLP wave, 1 .. 3: gather waves
-    int64_t blk = blockIdx.x;
-    if (nblk >= 8 && (nblk & 7) == 0) blk = (int64_t)(blockIdx.x & 7) * (nblk >> 3) + (blockIdx.x >> 3);
-    const int64_t slot = blk * 4 + team, n_slots = (int64_t)nblk * 4;
-    const int64_t t0 = n_tiles * slot / n_slots, t1 = n_tiles * (slot + 1) / n_slots;
+    const int team = wave & 3, role = wave >> 2;             // role 0: the MLP wave, 1 .. 3: gather waves
+    const Gin32Tiles share = gin32_slot_share(n, (int)gridDim.x, (int)blockIdx.x, team);   // gin32_plan.h
+    const int64_t t0 = share.t0, t1 = share.t1;
     const GinGraph G{rowptr, col_src, n};
     float *ring = rings + team * kFusedRing * kMidTileFloats;
     // ring slot s: ready[s] = 1 + the number of the last tile handed over there, taken[s] = 1 + the number of the last tile read
@@ -811,6 +797,69 @@ extern "C" void tgnn_debug_set_block_caps(int32_t nnconv_blocks, int32_t gin_mlp
 #endif
 
 namespace tgnn {
+// blocks of the MLP / fused kernels inside the forward: one per CU (the weight prologue is paid once per block), minus a few CUs left
+// to the other chain's small kernels (see launch_cols_t in nnconv_cols.hip), or what tgnn_debug_set_block_caps asks for
+static int gin32_grid(int64_t n_nodes) {
+    constexpr int reserve = 32;
+    int cap = cus_minus(reserve);
+    if (const int dbg = g_debug_block_cap[1].load(); dbg > 0) cap = dbg < device_cus() ? dbg : device_cus();
+    return gin32_blocks(n_nodes, cap);                       // gin32_plan.h
+}
+
+static void launch_gin32_aggregate(const float *a, int64_t lda, const float *in_stat, const int32_t *rowptr, const int32_t *col_src,
+                                   const float *eps, int64_t n_nodes, float *z, hipStream_t s) {
+    const int64_t rows_per_xcd = (n_nodes + 7) / 8;
+    const unsigned agg_blocks = (unsigned)(8 * ((rows_per_xcd + 31) / 32));
+    gin_aggregate_kernel<32><<<agg_blocks, 256, 0, s>>>(a, lda, in_stat, rowptr, col_src, eps, n_nodes, z);
+}
+
+// the MLP on an aggregate z [N][32]: kGin32Bf16x3 (gin32_mlp_kernel) or kGin32F16 (gin32_mlp16_kernel, LeakyReLU only)
+static int launch_gin32_mlp_variant(Gin32Variant variant, const float *z, const float *w1, const float *b1, const float *w2, const float *b2,
+                                    const float *w3, const float *b3, int64_t n_nodes, int32_t act, float *out, double *bn_partial,
+                                    int32_t *n_partials_host, hipStream_t s, const GinFin *fin) {
+    const int blocks = gin32_grid(n_nodes);
+    GinFin f{};
+    if (variant == kGin32F16) {
+        // the inference forward's opt-in kernel: fp16 pairs in layers 2 / 3 (the kernel fills in the record's job itself)
+        if (fin && bn_partial) f = *fin;
+        gin32_mlp16_kernel<<<blocks, kMlp16Threads, 0, s>>>(z, w1, b1, w2, b2, w3, b3, n_nodes, out, bn_partial, f);
+    } else {
+        if (fin && bn_partial) {
+            f = *fin;
+            f.job.partials = bn_partial;
+            f.job.n_partials = blocks;
+        }
+        gin32_mlp_kernel<<<blocks, kMlpThreads, 0, s>>>(z, w1, b1, w2, b2, w3, b3, n_nodes, act, out, bn_partial, f);
+    }
+    if (n_partials_host) *n_partials_host = blocks;
+    TGNN_CHECK_LAUNCH();
+    return TGNN_OK;
+}
+
+// One form of GINConv at width 32, chosen by the caller: what gin32_fwd_folded (the forward) and tgnn_gin32_fwd (the op) both run.
+// fin == NULL: no folded BatchNorm finalize.
+static int launch_gin32_variant(Gin32Variant variant, const float *a, int64_t lda, const float *in_stat, const int32_t *rowptr,
+                                const int32_t *col_src, const float *eps, const float *w1, const float *b1, const float *w2, const float *b2,
+                                const float *w3, const float *b3, int64_t n_nodes, int32_t act, float *out, float *z_scratch,
+                                double *bn_partial, int32_t *n_partials_host, const GinFin *fin, hipStream_t s) {
+    if (variant == kGin32Fused) {
+        // one launch, no z round trip (gin32_fused_kernel)
+        const int blocks = gin32_grid(n_nodes);
+        GinFin f{};
+        if (fin && bn_partial) f = *fin;
+        f.job.partials = bn_partial;
+        f.job.n_partials = blocks;
+        static LdsOptIn site;
+        TGNN_CHECK_HIP(opt_in_dynamic_lds(gin32_fused_kernel, (int)kFusedLdsBytes, site));
+        gin32_fused_kernel<<<blocks, kFusedThreads, kFusedLdsBytes, s>>>(a, in_stat, rowptr, col_src, eps, w1, b1, w2, b2, w3, b3, n_nodes, out, bn_partial, f);
+        if (n_partials_host) *n_partials_host = blocks;
+        TGNN_CHECK_LAUNCH();
+        return TGNN_OK;
+    }
+    launch_gin32_aggregate(a, lda, in_stat, rowptr, col_src, eps, n_nodes, z_scratch, s);
+    return launch_gin32_mlp_variant(variant, z_scratch, w1, b1, w2, b2, w3, b3, n_nodes, act, out, bn_partial, n_partials_host, s, fin);
+}
+
 int gin32_fwd_folded(const float *a, int64_t lda, const float *in_stat, const int32_t *rowptr, const int32_t *col_src, const float *eps,
                      const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, const float *b3,
                      int64_t n_nodes, int32_t act, float *out, float *z_scratch, double *bn_partial, int32_t *n_partials_host,
@@ -821,34 +870,51 @@ int gin32_fwd_folded(const float *a, int64_t lda, const float *in_stat, const in
     // Measured, cached-layout forward, two kernels / fused: 20 000 nodes 0.880 / 0.916 ms, 100 000: 1.78 / 1.85, 300 000: 4.53 / 4.39;
     // the op alone (events, single stream) 43.6 / 38.1 us at 100 000 nodes, 94.0 / 83.3 at 300 000.  Inside the two-chain forward both
     // forms cost ~62 us of wall clock per layer at 100 000 nodes (the chains take the CUs in turns); the fused form wins where the
-    // layer is long enough for its z traffic (25.6 MB per 100 000 nodes) to matter: from kGinFusedMinNodes on
-    constexpr int64_t kGinFusedMinNodes = 200000;
-    const int fused_mode = g_gin_fused.load(std::memory_order_relaxed);   // 0 never, 1 by size, 2 always
-    if (!need_z && lda == 32 && act == TGNN_ACT_LEAKY_RELU && (fused_mode == 2 || (fused_mode == 1 && n_nodes >= kGinFusedMinNodes)) &&
-        n_nodes * 128 < (int64_t(1) << 31)) {
-        // one launch, no z round trip (gin32_fused_kernel)
-        int blocks = producer_blocks(n_nodes, 16 * kMlpWaves);
-        constexpr int reserve = 32;
-        int cap = cus_minus(reserve);
-        if (const int dbg = g_debug_block_cap[1].load(); dbg > 0) cap = dbg < device_cus() ? dbg : device_cus();
-        if (blocks > cap) blocks = cap;
-        if (blocks >= 8) blocks &= ~7;
-        GinFin f = fin;
-        f.job.partials = bn_partial;
-        f.job.n_partials = blocks;
-        static LdsOptIn site;
-        TGNN_CHECK_HIP(opt_in_dynamic_lds(gin32_fused_kernel, (int)kFusedLdsBytes, site));
-        gin32_fused_kernel<<<blocks, kFusedThreads, kFusedLdsBytes, s>>>(a, in_stat, rowptr, col_src, eps, w1, b1, w2, b2, w3, b3, n_nodes, out, bn_partial, f);
-        if (n_partials_host) *n_partials_host = blocks;
-        TGNN_CHECK_LAUNCH();
-        return TGNN_OK;
-    }
-    const int64_t rows_per_xcd = (n_nodes + 7) / 8;
-    const unsigned agg_blocks = (unsigned)(8 * ((rows_per_xcd + 31) / 32));
-    gin_aggregate_kernel<32><<<agg_blocks, 256, 0, s>>>(a, lda, in_stat, rowptr, col_src, eps, n_nodes, z_scratch);
-    return launch_gin32_mlp(z_scratch, w1, b1, w2, b2, w3, b3, n_nodes, act, out, bn_partial, n_partials_host, s, &fin, !need_z);
+    // layer is long enough for its z traffic (25.6 MB per 100 000 nodes) to matter: from kGinFusedMinNodes on (gin32_plan.h)
+    const Gin32Variant variant = gin32_variant(need_z, lda, act, n_nodes, g_gin_fused.load(std::memory_order_relaxed),
+                                               g_gin_mlp16.load(std::memory_order_relaxed));
+    return launch_gin32_variant(variant, a, lda, in_stat, rowptr, col_src, eps, w1, b1, w2, b2, w3, b3, n_nodes, act, out, z_scratch, bn_partial,
+                                n_partials_host, &fin, s);
 }
 }  // namespace tgnn
+
+extern "C" int tgnn_gin32_fwd(const float *a, int64_t lda, const float *in_stat, const int32_t *rowptr, const int32_t *col_src,
+                              const float *eps, const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
+                              const float *b3, int64_t n_nodes, int32_t c, int32_t act, int32_t variant, float *out, float *z_scratch,
+                              double *bn_partial, int32_t *n_partials_host, tgnn_stream_t stream) {
+    DeviceGuard guard__(stream);
+    TGNN_CHECK_ARG(n_nodes >= 0 && c >= 1, "shape");
+    TGNN_CHECK_ARG(act == TGNN_ACT_NONE || act == TGNN_ACT_LEAKY_RELU, "activation");
+    TGNN_CHECK_ARG(variant == kGin32Bf16x3 || variant == kGin32F16 || variant == kGin32Fused, "variant");
+    if (c != 32) {
+        set_error("tgnn_gin32_fwd: width 32 only (c = %d)", (int)c);
+        return TGNN_ERR_UNSUPPORTED;
+    }
+    if (n_nodes == 0) {
+        if (n_partials_host) *n_partials_host = 0;
+        return TGNN_OK;
+    }
+    TGNN_CHECK_ARG(a && rowptr && eps && w1 && b1 && w2 && b2 && w3 && b3 && out && (z_scratch || variant == kGin32Fused), "null pointer");
+    TGNN_CHECK_ARG(lda >= 32, "lda");
+    if (lda % 4 != 0 || ((uintptr_t)a % 16) != 0 || ((uintptr_t)out % 16) != 0 || (variant != kGin32Fused && ((uintptr_t)z_scratch % 16) != 0)) {
+        set_error("tgnn_gin32_fwd: lda a multiple of 4, a / out / z_scratch 16-byte aligned (lda %lld)", (long long)lda);
+        return TGNN_ERR_UNSUPPORTED;
+    }
+    if (!gin32_rows_addressable(n_nodes)) {
+        set_error("tgnn_gin32_fwd: %lld rows of 128 bytes are past 2 GB", (long long)n_nodes);
+        return TGNN_ERR_UNSUPPORTED;
+    }
+    if (variant != kGin32Bf16x3 && act != TGNN_ACT_LEAKY_RELU) {
+        set_error("tgnn_gin32_fwd: variant %d runs with LeakyReLU only", (int)variant);
+        return TGNN_ERR_UNSUPPORTED;
+    }
+    if (variant != kGin32Bf16x3 && lda != 32) {
+        set_error("tgnn_gin32_fwd: variant %d reads packed rows only (lda %lld, not 32)", (int)variant, (long long)lda);
+        return TGNN_ERR_UNSUPPORTED;
+    }
+    return launch_gin32_variant(static_cast<Gin32Variant>(variant), a, lda, in_stat, rowptr, col_src, eps, w1, b1, w2, b2, w3, b3, n_nodes, act,
+                                out, z_scratch, bn_partial, n_partials_host, nullptr, static_cast<hipStream_t>(stream));
+}
 
 extern "C" int tgnn_gin_fwd(const float *a, int64_t lda, const float *in_stat, const int32_t *rowptr,
                             const int32_t *col_src, const float *eps, const float *w1, const float *b1,
@@ -868,16 +934,11 @@ extern "C" int tgnn_gin_fwd(const float *a, int64_t lda, const float *in_stat, c
     int blocks;
     if (c == 32 && lda % 4 == 0 && ((uintptr_t)a % 16) == 0 && ((uintptr_t)out % 16) == 0 && z_scratch &&
         ((uintptr_t)z_scratch % 16) == 0) {
-        const int64_t rows_per_xcd = (n_nodes + 7) / 8;
-        const unsigned agg_blocks = (unsigned)(8 * ((rows_per_xcd + 31) / 32));
-        gin_aggregate_kernel<32><<<agg_blocks, 256, 0, s>>>(a, lda, in_stat, rowptr, col_src, eps, n_nodes, z_scratch);
-        // persistent 8-wave blocks; the waves of one SIMD split a contiguous share of 32-row tiles
-        blocks = producer_blocks(n_nodes, 16 * kMlpWaves);
-        // one block per CU (the weight prologue is paid once per block), minus a few CUs left to the other chain's small
-        // kernels (see launch_cols_t in nnconv_cols.hip)
-        constexpr int reserve = 32;
-        if (blocks > cus_minus(reserve)) blocks = cus_minus(reserve);
-        if (blocks >= 8) blocks &= ~7;
+        launch_gin32_aggregate(a, lda, in_stat, rowptr, col_src, eps, n_nodes, z_scratch, s);
+        // persistent 8-wave blocks; the waves of one SIMD split a contiguous share of 16-row tiles.  One block per CU (the weight
+        // prologue is paid once per block), minus a few CUs left to the other chain's small kernels (see launch_cols_t in
+        // nnconv_cols.hip); the debug cap does not apply to this entry
+        blocks = gin32_blocks(n_nodes, cus_minus(32));
         gin32_mlp_kernel<<<blocks, kMlpThreads, 0, s>>>(z_scratch, w1, b1, w2, b2, w3, b3, n_nodes, act, out,
                                                         bn_partial, GinFin{});
     } else {
@@ -892,41 +953,12 @@ extern "C" int tgnn_gin_fwd(const float *a, int64_t lda, const float *in_stat, c
 
 namespace tgnn {
 // the MLP half of tgnn_gin_fwd (width 32) on an aggregate tgnn_gin_aggregate wrote; forward.hip's sharded schedule runs the two
-// halves on different streams
+// halves on different streams.  inference: nobody reads z afterwards -- the fp16-pair kernel when its switch is on (gin32_plan.h)
 int launch_gin32_mlp(const float *z, const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
                      const float *b3, int64_t n_nodes, int32_t act, float *out, double *bn_partial, int32_t *n_partials_host,
                      hipStream_t s, const GinFin *fin, bool inference) {
-    if (inference && act == TGNN_ACT_LEAKY_RELU && g_gin_mlp16.load(std::memory_order_relaxed)) {
-        // the inference forward's kernel (gin32_mlp16_kernel): fp16 pairs in layers 2 / 3, 16 waves per block
-        int blocks = producer_blocks(n_nodes, 16 * kMlp16Waves);
-        constexpr int reserve = 32;
-        int cap = cus_minus(reserve);
-        if (const int dbg = g_debug_block_cap[1].load(); dbg > 0) cap = dbg < device_cus() ? dbg : device_cus();
-        if (blocks > cap) blocks = cap;
-        if (blocks >= 8) blocks &= ~7;
-        GinFin f{};
-        if (fin && bn_partial) f = *fin;
-        gin32_mlp16_kernel<<<blocks, kMlp16Threads, 0, s>>>(z, w1, b1, w2, b2, w3, b3, n_nodes, out, bn_partial, f);
-        if (n_partials_host) *n_partials_host = blocks;
-        TGNN_CHECK_LAUNCH();
-        return TGNN_OK;
-    }
-    int blocks = producer_blocks(n_nodes, 16 * kMlpWaves);
-    constexpr int reserve = 32;
-    int cap = cus_minus(reserve);
-    if (const int dbg = g_debug_block_cap[1].load(); dbg > 0) cap = dbg < device_cus() ? dbg : device_cus();
-    if (blocks > cap) blocks = cap;
-    if (blocks >= 8) blocks &= ~7;
-    GinFin f{};
-    if (fin && bn_partial) {
-        f = *fin;
-        f.job.partials = bn_partial;
-        f.job.n_partials = blocks;
-    }
-    gin32_mlp_kernel<<<blocks, kMlpThreads, 0, s>>>(z, w1, b1, w2, b2, w3, b3, n_nodes, act, out, bn_partial, f);
-    if (n_partials_host) *n_partials_host = blocks;
-    TGNN_CHECK_LAUNCH();
-    return TGNN_OK;
+    const Gin32Variant variant = gin32_variant(!inference, 32, act, n_nodes, 0, g_gin_mlp16.load(std::memory_order_relaxed));
+    return launch_gin32_mlp_variant(variant, z, w1, b1, w2, b2, w3, b3, n_nodes, act, out, bn_partial, n_partials_host, s, fin);
 }
 }  // namespace tgnn
 

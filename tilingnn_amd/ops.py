@@ -720,11 +720,16 @@ def set_gin64_mfma(on: int) -> int:
     return int(lib.tgnn_set_gin64_mfma(int(on)))
 
 
+GIN32_VARIANTS = {"bf16x3": 0, "f16": 1, "fused": 2}      # tgnn_gin32_fwd's variant (csrc/gin32_plan.h: Gin32Variant)
+
+
 def gin(a: Tensor, graph: PreparedGraph, eps: Tensor, w1, b1, w2, b2, w3, b3, act: int = ACT_NONE,
         in_stat: Optional[Tensor] = None, partials: Optional[Tensor] = None, kernel: Optional[str] = None) -> Tuple[Tensor, int]:
     """GINConv + activation.  kernel: None = tgnn_gin_fwd (the matrix-core kernels at width 32, the generic one elsewhere);
-    "mfma" = the width-64 matrix-core kernel (tgnn_gin64_fwd; ValueError at any other width)."""
-    if kernel not in (None, "mfma"):
+    "mfma" = the width-64 matrix-core kernel (tgnn_gin64_fwd; ValueError at any other width); "bf16x3" / "f16" / "fused" = one of
+    the three width-32 forms whatever the process-wide switches say (tgnn_gin32_fwd variants 0 / 1 / 2; ValueError at any other
+    width, RuntimeError where the form refuses the call: see include/tgnn.h)."""
+    if kernel not in (None, "mfma", *GIN32_VARIANTS):
         raise ValueError(f"unknown GIN kernel {kernel!r}")
     a = _f32c(a, "x")
     c = int(a.shape[1])
@@ -742,6 +747,12 @@ def gin(a: Tensor, graph: PreparedGraph, eps: Tensor, w1, b1, w2, b2, w3, b3, ac
             raise ValueError(f"the matrix-core GIN kernel selected by kernel=\"mfma\" is the width-64 one: x has width {c}")
         check(lib.tgnn_gin64_fwd(ptr(a), c, ptr(in_stat), ptr(graph.col_rowptr), ptr(graph.col_src), *[ptr(p) for p in ps],
                                  n, act, ptr(out), ptr(z_scratch), ptr(partials), C.byref(npart), _stream(a)))
+        return out, npart.value
+    if kernel in GIN32_VARIANTS:
+        if c != 32:
+            raise ValueError(f"kernel={kernel!r} is a width-32 form of GINConv: x has width {c}")
+        check(lib.tgnn_gin32_fwd(ptr(a), c, ptr(in_stat), ptr(graph.col_rowptr), ptr(graph.col_src), *[ptr(p) for p in ps],
+                                 n, c, act, GIN32_VARIANTS[kernel], ptr(out), ptr(z_scratch), ptr(partials), C.byref(npart), _stream(a)))
         return out, npart.value
     check(lib.tgnn_gin_fwd(ptr(a), c, ptr(in_stat), ptr(graph.col_rowptr), ptr(graph.col_src), *[ptr(p) for p in ps],
                            n, c, act, ptr(out), ptr(z_scratch), ptr(partials), C.byref(npart), _stream(a)))
