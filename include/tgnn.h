@@ -1008,6 +1008,23 @@ int tgnn_sigmoid_mlp_bwd(const float *x, int64_t n_rows, int32_t d0, int32_t d1,
                          const float *b1, const float *w2, const float *b2, const float *w3, const float *t3,
                          const float *d_out, int64_t ld_dout, float *dw1, float *db1, float *dw2, float *db2, float *dw3,
                          float *db3, float *dx, void *ws, size_t ws_bytes, tgnn_stream_t stream);
+/* The same adjoint as kernels of its own (csrc/mlp_bwd.hip) for the two shapes every layer of tgnn_backward has:
+ *   tall (1): (d0, d1, d2, d3) = (32, 32, 64, 32), any n_rows (GINConv's MLP at width 32) -- one persistent kernel that keeps a
+ *             16-row tile's whole chain in registers + one fold kernel over the blocks' partial rows;
+ *   wide (2): (fe <= 64, 32, 64, a multiple of 64) on n_rows <= 63 rows, dx NULL (GraphConv's edge MLP) -- two launches.
+ * _form: 0 = not taken, 1 = tall, 2 = wide; host only, no device call.  _workspace_bytes: 0 where the form is 0.
+ * tgnn_sigmoid_mlp_bwd_fused takes the argument list of tgnn_sigmoid_mlp_bwd; where the form is 0 it returns
+ * TGNN_ERR_UNSUPPORTED (tgnn_last_error set), launches nothing, writes nothing and does NOT fall back to the chain.  The tall
+ * form wants x, t3, d_out, dx aligned to 16 bytes and ld_dout a multiple of 4.  No atomics: the same bits on every call.
+ * tgnn_set_mlp_bwd_fused: 0 / 1 (default 0) -- 1 sends tgnn_backward's GIN adjoint (width 32) and edge-MLP adjoint (widths 32 and
+ * 64, 1 <= T <= 63, fe <= 64) to these kernels; returns the previous value; anything else only queries. */
+int32_t tgnn_sigmoid_mlp_bwd_fused_form(int64_t n_rows, int32_t d0, int32_t d1, int32_t d2, int32_t d3, int32_t want_dx);
+size_t tgnn_sigmoid_mlp_bwd_fused_workspace_bytes(int64_t n_rows, int32_t d0, int32_t d1, int32_t d2, int32_t d3);
+int tgnn_sigmoid_mlp_bwd_fused(const float *x, int64_t n_rows, int32_t d0, int32_t d1, int32_t d2, int32_t d3, const float *w1,
+                               const float *b1, const float *w2, const float *b2, const float *w3, const float *t3,
+                               const float *d_out, int64_t ld_dout, float *dw1, float *db1, float *dw2, float *db2, float *dw3,
+                               float *db3, float *dx, void *ws, size_t ws_bytes, tgnn_stream_t stream);
+int32_t tgnn_set_mlp_bwd_fused(int32_t on);
 /* NNConv backward building block (edge_conv.py:25; PyG NNConv: message = x_j . W_e, mean, + x . root):
  * out [n_nodes][(n_types + 1) * c], c = 32 or 64 (the network width; n_types <= 63): slot t < n_types = sum over the
  * row's CSR slots of type t of rows[src];

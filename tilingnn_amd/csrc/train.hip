@@ -14,6 +14,7 @@
 //   init MLP (2 x Linear/LeakyReLU/BatchNorm)
 // Gradients go to grads_host[k], indexed like params_host (entries of buffers -- running statistics, GIN's eps -- are
 // not touched).
+#include "mlp_bwd_plan.h"
 #include "tgnn_common.h"
 
 namespace tgnn {
@@ -82,6 +83,11 @@ static BwdBuffers carve_bwd(const tgnn_model_dims &d, int64_t n, int32_t T, void
     size_t mlp = tgnn_sigmoid_mlp_bwd_workspace_bytes(nn, c, 32, 64, c);
     const size_t mlp_e = tgnn_sigmoid_mlp_bwd_workspace_bytes(T > 0 ? T : 1, fe, 32, 64, c * c);
     if (mlp_e > mlp) mlp = mlp_e;
+    // the fused adjoints (mlp_bwd.hip) share the area: sized for the larger of the two paths whatever tgnn_set_mlp_bwd_fused says,
+    // so that a switch flipped between the query and the call cannot overrun it
+    const size_t fused[] = {mlp_bwd_fused_workspace_bytes(nn, c, 32, 64, c), mlp_bwd_fused_workspace_bytes(T > 0 ? T : 1, fe, 32, 64, c * c)};
+    for (size_t v : fused)
+        if (v > mlp) mlp = v;
     b.mlp_bytes = mlp;
     b.mlp = a.bytes(mlp);
     b.total = a.off + 256;
@@ -175,6 +181,13 @@ extern "C" int tgnn_backward(const tgnn_model_dims *dims, const void *const *par
     }
 
     // ---- the message-passing layers, last to first
+    // tgnn_set_mlp_bwd_fused, read once per call: the two sigmoid-MLP adjoints of a layer on mlp_bwd.hip's kernels where
+    // mlp_bwd_plan.h has a form for their shape (GIN: width 32; edge MLP: 1 <= T <= 63, fe <= 64), else the chain as before
+    const bool fused_on = tgnn_set_mlp_bwd_fused(-1) == 1;
+    const bool fused_edge = fused_on && T >= 1 && mlp_bwd_form(T, fe, 32, 64, c * c, 0) == 2;
+    const bool fused_gin = fused_on && mlp_bwd_form(n, c, 32, 64, c, 1) == 1;
+    const auto mlp_bwd_edge = fused_edge ? tgnn_sigmoid_mlp_bwd_fused : tgnn_sigmoid_mlp_bwd;
+    const auto mlp_bwd_gin = fused_gin ? tgnn_sigmoid_mlp_bwd_fused : tgnn_sigmoid_mlp_bwd;
     auto slot = [&](int k) { return b.dcat + (size_t)k * c; };           // row stride cat
     const float *carry = nullptr;
     for (int i = D - 1; i >= 0; --i) {
@@ -206,18 +219,18 @@ extern "C" int tgnn_backward(const tgnn_model_dims *dims, const void *const *par
         TGNN_TRYB(tgnn_add_into(b.dh1, c, n, c, slot(i), cat, stream));
         if (T > 0) {
             TGNN_TRYB(tgnn_rows_gather(adj_edge_attr, fe, graph->type_rep_edge, T, fe, b.rows, fe, stream));
-            TGNN_TRYB(tgnn_sigmoid_mlp_bwd(b.rows, T, fe, 32, 64, c * c, P.f(pb), P.f(pb + 1), P.f(pb + 2), P.f(pb + 3),
-                                           P.f(pb + 4), wtab, b.dwcat, (int64_t)c * c, G(pb), G(pb + 1), G(pb + 2), G(pb + 3),
-                                           G(pb + 4), G(pb + 5), nullptr, b.mlp, b.mlp_bytes, stream));
+            TGNN_TRYB(mlp_bwd_edge(b.rows, T, fe, 32, 64, c * c, P.f(pb), P.f(pb + 1), P.f(pb + 2), P.f(pb + 3), P.f(pb + 4), wtab,
+                                   b.dwcat, (int64_t)c * c, G(pb), G(pb + 1), G(pb + 2), G(pb + 3), G(pb + 4), G(pb + 5), nullptr,
+                                   b.mlp, b.mlp_bytes, stream));
         } else {
             const int sz[6] = {32 * fe, 32, 64 * 32, 64, c * c * 64, c * c};
             for (int k = 0; k < 6; ++k) TGNN_CHECK_HIP(hipMemsetAsync(G(pb + k), 0, sizeof(float) * sz[k], s));
         }
         // GIN adjoint: u = the aggregate the MLP read, a2 = its output (LeakyReLU is the identity on a sigmoid)
         float *du = b.dy1;                                   // dy1 is dead by now
-        TGNN_TRYB(tgnn_sigmoid_mlp_bwd(keep->u + (size_t)i * n * c, n, c, 32, 64, c, P.f(pb + 14), P.f(pb + 15), P.f(pb + 16),
-                                       P.f(pb + 17), P.f(pb + 18), a2, b.dz2, c, G(pb + 14), G(pb + 15), G(pb + 16), G(pb + 17),
-                                       G(pb + 18), G(pb + 19), du, b.mlp, b.mlp_bytes, stream));
+        TGNN_TRYB(mlp_bwd_gin(keep->u + (size_t)i * n * c, n, c, 32, 64, c, P.f(pb + 14), P.f(pb + 15), P.f(pb + 16), P.f(pb + 17),
+                              P.f(pb + 18), a2, b.dz2, c, G(pb + 14), G(pb + 15), G(pb + 16), G(pb + 17), G(pb + 18), G(pb + 19), du,
+                              b.mlp, b.mlp_bytes, stream));
         float *next_carry = b.carry[i & 1];
         TGNN_TRYB(tgnn_gin_aggregate(du, c, nullptr, tgraph->colT_rowptr, tgraph->colT_src, P.f(pb + 13), n, c, next_carry, stream));
         carry = next_carry;

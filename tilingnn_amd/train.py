@@ -21,6 +21,7 @@ Adjoints, per forward kernel (C = network width, T edge types, D layers):
                    The edge MLP (T rows) is back-propagated with the generic dense pieces.
   GIN              t1, t2 re-derived from the kept aggregate; three sigmoid/Linear adjoints; the aggregation's adjoint is
                    the aggregation on the transposed collision graph (tgnn_gin_aggregate).
+  (set_mlp_bwd_fused(1): the sigmoid-MLP adjoints of both branches as kernels of their own, csrc/mlp_bwd.hip -- opt-in.)
 Widths 32 (the reference's network_width, inputs/config.py:38) and 64 (BASELINE config 3); other widths raise.  Width 64
 runs the same schedule: the width-64 forms of the adjoint kernels (type sums one wave per row, merge backward, GIN
 aggregation, the slot-major weight gradient over 64-wide slots) and the forward's generic GIN kernel keeping the aggregate.
@@ -272,22 +273,41 @@ def _mlp_backward(layers, acts, stats, first_input, first_slot_major, dy, grads,
     return dy
 
 
-def sigmoid_mlp_backward(weights, x: Tensor, t3: Tensor, d_out: Tensor, grads: Dict[str, Tensor], names, need_dx: bool):
-    """Three Linear + Sigmoid layers without BatchNorm (GraphConv's edge MLP, GINConv's MLP) in one library call
-    (tgnn_sigmoid_mlp_bwd).  weights = [w1, b1, w2, b2, w3, b3]; t3 = the MLP's output; names = the `...mlp.k` prefixes."""
+def set_mlp_bwd_fused(on: int) -> int:
+    """1: tgnn_backward and `sigmoid_mlp_backward(kernel=None)` run the two sigmoid-MLP adjoints of a layer on the kernels of
+    csrc/mlp_bwd.hip where they have a form for the shape (tgnn_set_mlp_bwd_fused; default off).  Returns the previous setting;
+    anything but 0 / 1 only queries."""
+    return int(lib.tgnn_set_mlp_bwd_fused(int(on)))
+
+
+def sigmoid_mlp_backward(weights, x: Tensor, t3: Tensor, d_out: Tensor, grads: Dict[str, Tensor], names, need_dx: bool,
+                         kernel: Optional[str] = None):
+    """Three Linear + Sigmoid layers without BatchNorm (GraphConv's edge MLP, GINConv's MLP) in one library call.
+    weights = [w1, b1, w2, b2, w3, b3]; t3 = the MLP's output; names = the `...mlp.k` prefixes.
+    kernel: "chain" = tgnn_sigmoid_mlp_bwd (the generic kernels in sequence), "fused" = tgnn_sigmoid_mlp_bwd_fused (raises where
+    it has no form for the shape), None = what tgnn_backward takes: fused iff the switch is on and the form predicate says so
+    (an edge MLP on no rows never goes there)."""
     n, d0 = int(x.shape[0]), int(x.shape[1])
     d1, d2, d3 = int(weights[0].shape[0]), int(weights[2].shape[0]), int(weights[4].shape[0])
     dev = x.device
     gw = [torch.empty_like(weights[2 * k]) for k in range(3)]
     gb = [torch.empty_like(weights[2 * k + 1]) for k in range(3)]
     dx = torch.empty(n, d0, dtype=torch.float32, device=dev) if need_dx else None
-    nb = lib.tgnn_sigmoid_mlp_bwd_workspace_bytes(n, d0, d1, d2, d3)
+    if kernel not in (None, "chain", "fused"):
+        raise ValueError("sigmoid_mlp_backward: kernel is None, 'chain' or 'fused'")
+    if kernel is None:
+        form = int(lib.tgnn_sigmoid_mlp_bwd_fused_form(n, d0, d1, d2, d3, 1 if need_dx else 0))
+        kernel = "fused" if set_mlp_bwd_fused(-1) == 1 and form != 0 and (form == 1 or n >= 1) else "chain"
+    if kernel == "fused":
+        nb, entry = lib.tgnn_sigmoid_mlp_bwd_fused_workspace_bytes(n, d0, d1, d2, d3), lib.tgnn_sigmoid_mlp_bwd_fused
+    else:
+        nb, entry = lib.tgnn_sigmoid_mlp_bwd_workspace_bytes(n, d0, d1, d2, d3), lib.tgnn_sigmoid_mlp_bwd
     ws = _Scratch.get("mlp_bwd", nb, dev)
     if not (x.is_contiguous() and t3.is_contiguous()):
         raise ValueError("sigmoid_mlp_backward: x and t3 must be contiguous")
-    check(lib.tgnn_sigmoid_mlp_bwd(ptr(x), n, d0, d1, d2, d3, ptr(weights[0]), ptr(weights[1]), ptr(weights[2]),
-                                   ptr(weights[3]), ptr(weights[4]), ptr(t3), ptr(d_out), d_out.stride(0), ptr(gw[0]),
-                                   ptr(gb[0]), ptr(gw[1]), ptr(gb[1]), ptr(gw[2]), ptr(gb[2]), ptr(dx), ptr(ws), nb, _s(x)))
+    check(entry(ptr(x), n, d0, d1, d2, d3, ptr(weights[0]), ptr(weights[1]), ptr(weights[2]),
+                ptr(weights[3]), ptr(weights[4]), ptr(t3), ptr(d_out), d_out.stride(0), ptr(gw[0]),
+                ptr(gb[0]), ptr(gw[1]), ptr(gb[1]), ptr(gw[2]), ptr(gb[2]), ptr(dx), ptr(ws), nb, _s(x)))
     for k in range(3):
         grads[names[k] + ".linear.weight"], grads[names[k] + ".linear.bias"] = gw[k], gb[k]
     return dx
