@@ -1025,6 +1025,25 @@ int tgnn_sigmoid_mlp_bwd_fused(const float *x, int64_t n_rows, int32_t d0, int32
                                const float *d_out, int64_t ld_dout, float *dw1, float *db1, float *dw2, float *db2, float *dw3,
                                float *db3, float *dx, void *ws, size_t ws_bytes, tgnn_stream_t stream);
 int32_t tgnn_set_mlp_bwd_fused(int32_t on);
+/* The tall form at width 64, a form of its own (csrc/mlp_bwd.hip: mlp_bwd_tall64_kernel; the queries above keep answering 0 for
+ * its shape): (d0, d1, d2, d3) = (64, 32, 64, 64), any n_rows (GINConv's MLP at width 64) -- one persistent kernel of 4-wave blocks,
+ * one wave per SIMD, that keeps a 16-row tile's whole chain in registers + one fold kernel over the blocks' partial rows.
+ * fp32 products and sums on the matrix cores, but for layer 1's forward product, which is summed in fp64.
+ * _ok: 1 iff n_rows >= 0 and the dims are exactly those; host only, no device call.  _workspace_bytes: 0 where _ok is 0.
+ * tgnn_sigmoid_mlp_bwd_tall64 takes the argument list of tgnn_sigmoid_mlp_bwd; where _ok is 0 it returns TGNN_ERR_UNSUPPORTED
+ * (tgnn_last_error set), launches nothing, writes nothing and does NOT fall back to the chain.  n_rows == 0 zeroes the six
+ * gradients.  x, t3, d_out, dx aligned to 16 bytes and ld_dout a multiple of 4, else TGNN_ERR_INVALID_ARG and nothing written;
+ * dx may be NULL.  No atomics: the same bits on every call.
+ * tgnn_set_mlp_bwd_tall64: 0 / 1 (default 0) -- 1 sends tgnn_backward's GIN adjoint at width 64 to this kernel, whatever
+ * tgnn_set_mlp_bwd_fused says (that switch keeps deciding the edge MLP at both widths and the GIN adjoint at width 32); returns the
+ * previous value; anything else only queries. */
+int32_t tgnn_sigmoid_mlp_bwd_tall64_ok(int64_t n_rows, int32_t d0, int32_t d1, int32_t d2, int32_t d3);
+size_t tgnn_sigmoid_mlp_bwd_tall64_workspace_bytes(int64_t n_rows, int32_t d0, int32_t d1, int32_t d2, int32_t d3);
+int tgnn_sigmoid_mlp_bwd_tall64(const float *x, int64_t n_rows, int32_t d0, int32_t d1, int32_t d2, int32_t d3, const float *w1,
+                                const float *b1, const float *w2, const float *b2, const float *w3, const float *t3,
+                                const float *d_out, int64_t ld_dout, float *dw1, float *db1, float *dw2, float *db2, float *dw3,
+                                float *db3, float *dx, void *ws, size_t ws_bytes, tgnn_stream_t stream);
+int32_t tgnn_set_mlp_bwd_tall64(int32_t on);
 /* NNConv backward building block (edge_conv.py:25; PyG NNConv: message = x_j . W_e, mean, + x . root):
  * out [n_nodes][(n_types + 1) * c], c = 32 or 64 (the network width; n_types <= 63): slot t < n_types = sum over the
  * row's CSR slots of type t of rows[src];

@@ -237,6 +237,11 @@ def _load() -> C.CDLL:
         "tgnn_sigmoid_mlp_bwd_fused": (C.c_int, [p, i64, i32, i32, i32, i32, p, p, p, p, p, p, p, i64, p, p, p, p, p, p, p, p,
                                                  sz, p]),
         "tgnn_set_mlp_bwd_fused": (i32, [i32]),
+        "tgnn_sigmoid_mlp_bwd_tall64_ok": (i32, [i64, i32, i32, i32, i32]),
+        "tgnn_sigmoid_mlp_bwd_tall64_workspace_bytes": (sz, [i64, i32, i32, i32, i32]),
+        "tgnn_sigmoid_mlp_bwd_tall64": (C.c_int, [p, i64, i32, i32, i32, i32, p, p, p, p, p, p, p, i64, p, p, p, p, p, p, p, p,
+                                                  sz, p]),
+        "tgnn_set_mlp_bwd_tall64": (i32, [i32]),
         "tgnn_nnconv_type_sum": (C.c_int, [p, i64, p, i64, p, p, p, p, i64, i32, i32, p, p]),
         "tgnn_csr_degree": (C.c_int, [p, i64, p, p, p]),
         "tgnn_unsupervised_loss_bwd": (C.c_int, [p, i64, p, i64, i64, p, i64, p, i64, p, i64, f32, f32, f32, p, p, p, i64,
@@ -301,6 +306,7 @@ EXPORTED_SYMBOLS = (
     "tgnn_bn_bwd_reduce", "tgnn_bn_bwd_apply", "tgnn_merge_bwd_reduce", "tgnn_wgrad_workspace_bytes", "tgnn_wgrad", "tgnn_wgrad_slots",
     "tgnn_sigmoid_mlp_bwd_workspace_bytes", "tgnn_sigmoid_mlp_bwd",
     "tgnn_sigmoid_mlp_bwd_fused_form", "tgnn_sigmoid_mlp_bwd_fused_workspace_bytes", "tgnn_sigmoid_mlp_bwd_fused", "tgnn_set_mlp_bwd_fused",
+    "tgnn_sigmoid_mlp_bwd_tall64_ok", "tgnn_sigmoid_mlp_bwd_tall64_workspace_bytes", "tgnn_sigmoid_mlp_bwd_tall64", "tgnn_set_mlp_bwd_tall64",
     "tgnn_nnconv_type_sum", "tgnn_csr_degree", "tgnn_unsupervised_loss_bwd",
     "tgnn_f32_to_bf16", "tgnn_nnconv64_image_elems", "tgnn_nnconv64_bf16_fwd", "tgnn_nnconv64_bf16_eg_fwd", "tgnn_gin64_bf16_fwd", "tgnn_collconv64_bf16_fwd", "tgnn_merge_bf16_fwd",
     "tgnn_dense_bf16_slots_fwd", "tgnn_forward_bf16_workspace_bytes", "tgnn_forward_bf16")

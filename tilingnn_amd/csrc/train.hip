@@ -14,6 +14,7 @@
 //   init MLP (2 x Linear/LeakyReLU/BatchNorm)
 // Gradients go to grads_host[k], indexed like params_host (entries of buffers -- running statistics, GIN's eps -- are
 // not touched).
+#include "mlp_bwd64_plan.h"
 #include "mlp_bwd_plan.h"
 #include "tgnn_common.h"
 
@@ -83,9 +84,10 @@ static BwdBuffers carve_bwd(const tgnn_model_dims &d, int64_t n, int32_t T, void
     size_t mlp = tgnn_sigmoid_mlp_bwd_workspace_bytes(nn, c, 32, 64, c);
     const size_t mlp_e = tgnn_sigmoid_mlp_bwd_workspace_bytes(T > 0 ? T : 1, fe, 32, 64, c * c);
     if (mlp_e > mlp) mlp = mlp_e;
-    // the fused adjoints (mlp_bwd.hip) share the area: sized for the larger of the two paths whatever tgnn_set_mlp_bwd_fused says,
-    // so that a switch flipped between the query and the call cannot overrun it
-    const size_t fused[] = {mlp_bwd_fused_workspace_bytes(nn, c, 32, 64, c), mlp_bwd_fused_workspace_bytes(T > 0 ? T : 1, fe, 32, 64, c * c)};
+    // the fused adjoints (mlp_bwd.hip) share the area: sized for the largest of all paths whatever tgnn_set_mlp_bwd_fused and
+    // tgnn_set_mlp_bwd_tall64 say, so that a switch flipped between the query and the call cannot overrun it
+    const size_t fused[] = {mlp_bwd_fused_workspace_bytes(nn, c, 32, 64, c), mlp_bwd_fused_workspace_bytes(T > 0 ? T : 1, fe, 32, 64, c * c),
+                            mlp_bwd_tall64_workspace_bytes(nn, c, 32, 64, c)};
     for (size_t v : fused)
         if (v > mlp) mlp = v;
     b.mlp_bytes = mlp;
@@ -187,7 +189,9 @@ extern "C" int tgnn_backward(const tgnn_model_dims *dims, const void *const *par
     const bool fused_edge = fused_on && T >= 1 && mlp_bwd_form(T, fe, 32, 64, c * c, 0) == 2;
     const bool fused_gin = fused_on && mlp_bwd_form(n, c, 32, 64, c, 1) == 1;
     const auto mlp_bwd_edge = fused_edge ? tgnn_sigmoid_mlp_bwd_fused : tgnn_sigmoid_mlp_bwd;
-    const auto mlp_bwd_gin = fused_gin ? tgnn_sigmoid_mlp_bwd_fused : tgnn_sigmoid_mlp_bwd;
+    // tgnn_set_mlp_bwd_tall64, read once per call and on its own: the GIN adjoint at width 64 on mlp_bwd_tall64_kernel
+    const bool tall64_gin = tgnn_set_mlp_bwd_tall64(-1) == 1 && mlp_bwd_tall64_ok(n, c, 32, 64, c);
+    const auto mlp_bwd_gin = tall64_gin ? tgnn_sigmoid_mlp_bwd_tall64 : fused_gin ? tgnn_sigmoid_mlp_bwd_fused : tgnn_sigmoid_mlp_bwd;
     auto slot = [&](int k) { return b.dcat + (size_t)k * c; };           // row stride cat
     const float *carry = nullptr;
     for (int i = D - 1; i >= 0; --i) {

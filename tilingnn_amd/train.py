@@ -21,7 +21,8 @@ Adjoints, per forward kernel (C = network width, T edge types, D layers):
                    The edge MLP (T rows) is back-propagated with the generic dense pieces.
   GIN              t1, t2 re-derived from the kept aggregate; three sigmoid/Linear adjoints; the aggregation's adjoint is
                    the aggregation on the transposed collision graph (tgnn_gin_aggregate).
-  (set_mlp_bwd_fused(1): the sigmoid-MLP adjoints of both branches as kernels of their own, csrc/mlp_bwd.hip -- opt-in.)
+  (set_mlp_bwd_fused(1): the sigmoid-MLP adjoints of both branches as kernels of their own, csrc/mlp_bwd.hip -- opt-in;
+   set_mlp_bwd_tall64(1): the GIN adjoint at width 64 as a kernel of its own, same file -- opt-in, a switch of its own.)
 Widths 32 (the reference's network_width, inputs/config.py:38) and 64 (BASELINE config 3); other widths raise.  Width 64
 runs the same schedule: the width-64 forms of the adjoint kernels (type sums one wave per row, merge backward, GIN
 aggregation, the slot-major weight gradient over 64-wide slots) and the forward's generic GIN kernel keeping the aggregate.
@@ -280,25 +281,38 @@ def set_mlp_bwd_fused(on: int) -> int:
     return int(lib.tgnn_set_mlp_bwd_fused(int(on)))
 
 
+def set_mlp_bwd_tall64(on: int) -> int:
+    """1: tgnn_backward and `sigmoid_mlp_backward(kernel=None)` run GINConv's MLP adjoint at width 64 (64 -> 32 -> 64 -> 64) on
+    mlp_bwd_tall64_kernel (tgnn_set_mlp_bwd_tall64; default off), whatever set_mlp_bwd_fused says.  Returns the previous setting;
+    anything but 0 / 1 only queries."""
+    return int(lib.tgnn_set_mlp_bwd_tall64(int(on)))
+
+
 def sigmoid_mlp_backward(weights, x: Tensor, t3: Tensor, d_out: Tensor, grads: Dict[str, Tensor], names, need_dx: bool,
                          kernel: Optional[str] = None):
     """Three Linear + Sigmoid layers without BatchNorm (GraphConv's edge MLP, GINConv's MLP) in one library call.
     weights = [w1, b1, w2, b2, w3, b3]; t3 = the MLP's output; names = the `...mlp.k` prefixes.
     kernel: "chain" = tgnn_sigmoid_mlp_bwd (the generic kernels in sequence), "fused" = tgnn_sigmoid_mlp_bwd_fused (raises where
-    it has no form for the shape), None = what tgnn_backward takes: fused iff the switch is on and the form predicate says so
-    (an edge MLP on no rows never goes there)."""
+    it has no form for the shape), "tall64" = tgnn_sigmoid_mlp_bwd_tall64 (raises for anything but 64 -> 32 -> 64 -> 64),
+    None = what tgnn_backward takes: tall64 iff its switch is on and its predicate holds, else fused iff that switch is on and the
+    form predicate says so (an edge MLP on no rows never goes there), else the chain."""
     n, d0 = int(x.shape[0]), int(x.shape[1])
     d1, d2, d3 = int(weights[0].shape[0]), int(weights[2].shape[0]), int(weights[4].shape[0])
     dev = x.device
     gw = [torch.empty_like(weights[2 * k]) for k in range(3)]
     gb = [torch.empty_like(weights[2 * k + 1]) for k in range(3)]
     dx = torch.empty(n, d0, dtype=torch.float32, device=dev) if need_dx else None
-    if kernel not in (None, "chain", "fused"):
-        raise ValueError("sigmoid_mlp_backward: kernel is None, 'chain' or 'fused'")
+    if kernel not in (None, "chain", "fused", "tall64"):
+        raise ValueError("sigmoid_mlp_backward: kernel is None, 'chain', 'fused' or 'tall64'")
     if kernel is None:
         form = int(lib.tgnn_sigmoid_mlp_bwd_fused_form(n, d0, d1, d2, d3, 1 if need_dx else 0))
-        kernel = "fused" if set_mlp_bwd_fused(-1) == 1 and form != 0 and (form == 1 or n >= 1) else "chain"
-    if kernel == "fused":
+        if set_mlp_bwd_tall64(-1) == 1 and lib.tgnn_sigmoid_mlp_bwd_tall64_ok(n, d0, d1, d2, d3) == 1:
+            kernel = "tall64"
+        else:
+            kernel = "fused" if set_mlp_bwd_fused(-1) == 1 and form != 0 and (form == 1 or n >= 1) else "chain"
+    if kernel == "tall64":
+        nb, entry = lib.tgnn_sigmoid_mlp_bwd_tall64_workspace_bytes(n, d0, d1, d2, d3), lib.tgnn_sigmoid_mlp_bwd_tall64
+    elif kernel == "fused":
         nb, entry = lib.tgnn_sigmoid_mlp_bwd_fused_workspace_bytes(n, d0, d1, d2, d3), lib.tgnn_sigmoid_mlp_bwd_fused
     else:
         nb, entry = lib.tgnn_sigmoid_mlp_bwd_workspace_bytes(n, d0, d1, d2, d3), lib.tgnn_sigmoid_mlp_bwd
