@@ -810,7 +810,8 @@ def test_sharded_forward_with_the_collision_branch_on_a_side_stream(dev, one_col
 def test_split_precision_kernels_hold_fp32_accuracy_across_magnitudes(dev, scale_a, scale_w):
     """The bf16x3 kernels (wide Linear blocks, GIN MLP, column NNConv) split every fp32 operand exactly into three
     bf16 pieces; the claim "fp32-class accuracy" must not depend on the magnitude of the data.  Dense 256 -> 128 and
-    672-wide slot-major 672 -> 256 against fp64, inputs and weights scaled over 9 orders of magnitude."""
+    672-wide slot-major 672 -> 256 against fp64, inputs and weights scaled over 9 orders of magnitude.
+    (This test runs the dense layers only; the column NNConv across magnitudes: tests/test_nnconv32_ops.py.)"""
     from tilingnn_amd import ops
     gen = torch.Generator().manual_seed(11)
     n = 4099

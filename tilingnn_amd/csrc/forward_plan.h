@@ -14,7 +14,8 @@
 namespace tgnn {
 
 constexpr int kPlanMaxDepth = 64;      // == kMaxDepth (tgnn_common.h; forward.hip asserts it)
-constexpr int kCarveTypes = 16;        // (= tgnn_nnconv_cols_max_types(): what the matrix-core NNConv kernels take)
+constexpr int kCarveTypes = 16;        // types the workspace's type-dependent pieces are carved for at least (forward.hip: carve); NOT
+                                       // the matrix-core NNConv kernels' limit: tgnn_nnconv_cols_max_types() is 22
 constexpr int kFinalWidth0 = 256;      // out width of the final MLP's first Linear (TilinGNN.py:46)
 
 // bits of tgnn_set_lean_head

@@ -713,7 +713,11 @@ extern "C" int tgnn_nnconv_mean_fwd(const float *h, int64_t ldh, const int32_t *
     TGNN_CHECK_ARG(n_types == 0 || (col_src && col_type && wtab), "null graph pointer");
     TGNN_CHECK_ARG(ldh >= c, "ldh");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t lds_bytes = (size_t)(n_types + 1) * kTypeStride * sizeof(float);
+    // the weight table; the BatchNorm fold reuses the front of it as [16 waves][16][4] doubles = 8 KB, more than the table of a
+    // layout without edge types (the root alone: 5 KB) -- without the floor the sums of waves 10 .. 15 fell beyond the allocation
+    const size_t table_bytes = (size_t)(n_types + 1) * kTypeStride * sizeof(float);
+    const size_t fold_bytes = (size_t)kNNWaves * 16 * 4 * sizeof(double);
+    const size_t lds_bytes = table_bytes > fold_bytes ? table_bytes : fold_bytes;
     if (c == 32 && lds_bytes <= kMaxDynLds) {
         static LdsOptIn site;
         TGNN_CHECK_HIP(opt_in_dynamic_lds(nnconv32_lds_kernel, (int)kMaxDynLds, site));

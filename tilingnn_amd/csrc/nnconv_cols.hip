@@ -444,7 +444,8 @@ int launch_nnconv_cols(const float *h, int64_t ldh, const int32_t *tile_col_ptr,
         return launch_cols_t<4, 16, 4, true>(h, ldh, tile_col_ptr, col_meta, col_src, wimg, n_types, bias, n_nodes, act, out,
                                              bn_partial, n_partials_host, 1, s, h_max, root_max, deg_log2, stamp);
     }
-    // 16 waves per CU either way: two 8-wave blocks when two 6 KB-per-type weight images fit the LDS (T <= 11), else
+    // 16 waves per CU either way: two 8-wave blocks when two 6 KB-per-type weight images fit the LDS (T <= 10: a block takes
+    // (T + 1) 6 144 + 8 x 1 280 bytes, twice that is 155 648 at T = 10 and 167 936 at T = 11, against 163 840), else
     // one 16-wave block.  Measured with the fp32 kernel at N = 100k, T = 13 (us): <depth 4, 16 waves/CU> 55.7 |
     // <16, 8> 66.0 | <8, 8> 64.9 | <16, 4> 85.2 | <32, 4> 90.2
     if (cols_lds_bytes(n_types, 8) * 2 <= 160 * 1024)

@@ -592,6 +592,8 @@ def graph_columns(graph: PreparedGraph) -> Optional[NNConvColumns]:
 
 
 NNCONV64_EG_MAX_IN_DEGREE = 2048      # csrc/nnconv64_eg_plan.h: what the edge-group structure is stated for
+NNCONV_EG_MAX_IN_DEGREE = 2048        # csrc/nnconv_eg.hip: the root term's factor max(deg, 1) is exact in fp16 up to here
+NNCONV_KERNELS = (None, "eg", "cols", "cols_f16", "csr")     # nnconv_mean's kernel=
 
 
 def set_nnconv64_eg(on: int) -> int:
@@ -652,11 +654,19 @@ def edge_weight_table(edge_attr: Tensor, graph: PreparedGraph, w1, b1, w2, b2, w
 def nnconv_mean(h: Tensor, graph: PreparedGraph, wtab: Tensor, root: Tensor, bias: Tensor, act: int = ACT_NONE,
                 partials: Optional[Tensor] = None, force_csr_kernel: bool = False,
                 kernel: Optional[str] = None, max_in_degree: int = 0) -> Tuple[Tensor, int]:
-    """NNConv mean: the matrix-core column kernel when the graph carries the column structure, else the CSR /
-    LDS-weight-table kernel (any type count that fits LDS) or the generic one.  kernel: None = that order; "cols_f16" = the
-    column kernel with the fp16 x 2 split as tgnn_forward runs it (max_in_degree: the bound to scale by, default the
-    layout's); "eg" = the edge-group kernel of the width (32, or 64: the groups are built on first use; ValueError beyond
-    its limits)."""
+    """NNConv mean.  kernel: None = the edge-group kernel when the layout carries groups (width 32, in-degrees 1 ... 2 048), else
+    the matrix-core column kernel when it carries (or, beside groups, can build) the column structure, else the CSR kernels;
+    a name runs exactly that form or raises ValueError naming the limit it is beyond -- none falls back:
+      "eg"        the edge-group kernel of the width (32, or 64: the groups are built on first use)
+      "cols"      the bf16 x 3 column kernel (tgnn_nnconv_mean_cols_fwd; the columns are built on first use)
+      "cols_f16"  the column kernel with the fp16 x 2 split as tgnn_forward runs it (max_in_degree: the bound to scale by,
+                  default the layout's)
+      "csr"       tgnn_nnconv_mean_fwd: the LDS-weight-table kernel at width 32 while the table fits, else the generic one
+                  (the same as force_csr_kernel=True)."""
+    if kernel not in NNCONV_KERNELS:
+        raise ValueError(f"unknown NNConv kernel {kernel!r}: one of {', '.join(repr(k) for k in NNCONV_KERNELS)}")
+    if kernel == "csr":
+        kernel, force_csr_kernel = None, True
     h = _f32c(h, "x")
     c = int(h.shape[1])
     n = graph.n_nodes                      # destination rows; x may carry extra (halo) rows behind them
@@ -683,26 +693,43 @@ def nnconv_mean(h: Tensor, graph: PreparedGraph, wtab: Tensor, root: Tensor, bia
                                             ptr(_f32c(root, "root")), ptr(_f32c(bias, "bias")), n, act, ptr(out), ptr(wimg), ptr(bounds),
                                             ptr(partials), C.byref(npart), _stream(h)))
         return out, npart.value
+    t_max = int(lib.tgnn_nnconv_cols_max_types())
+    if kernel in ("eg", "cols", "cols_f16"):   # the tiled width-32 forms: their limits, stated before anything is built
+        what = {"eg": "edge-group", "cols": "column", "cols_f16": "fp16-pair column"}[kernel] + " NNConv kernel"
+        if c != 32:
+            raise ValueError(f"the {what} is built for width 32" + (" (or 64: nnconv64_eg_kernel)" if kernel == "eg" else "")
+                             + f", not {c}")
+        if graph.n_types > t_max:
+            raise ValueError(f"the {what} takes at most {t_max} edge types (its LDS weight image): this layout has {graph.n_types}")
+        if int(h.shape[0]) * 128 >= 2 ** 31:
+            raise ValueError(f"the {what} addresses rows within 2 GB: x has {int(h.shape[0])} rows")
     if kernel == "eg":
+        # the root term is folded with max(deg, 1) as an fp16 factor: exact up to 2 048 (csrc/nnconv_eg.hip)
+        if not 1 <= graph.max_in_degree <= NNCONV_EG_MAX_IN_DEGREE:
+            raise ValueError(f"the edge-group NNConv kernel takes in-degrees 1 ... {NNCONV_EG_MAX_IN_DEGREE}: this layout's "
+                             f"largest is {graph.max_in_degree}")
         grp = graph_groups(graph)
-        if grp is None or c != 32:
-            raise ValueError("the edge-group kernel needs <= 40 edge types and width 32 (or 64: nnconv64_eg_kernel)")
+        if grp is None:
+            raise ValueError("the edge-group NNConv kernel needs <= 40 edge types")
         wimg = torch.empty(lib.tgnn_nnconv_weight_image_floats(graph.n_types), dtype=torch.float32, device=h.device)
         bounds = torch.empty(2, dtype=torch.int32, device=h.device)
         check(lib.tgnn_nnconv_mean_eg_fwd(ptr(h), c, int(h.shape[0]), ptr(grp.tile_grp_ptr), ptr(grp.grp), ptr(wt), graph.n_types, ptr(_f32c(root, "root")), ptr(_f32c(bias, "bias")), n, act,
                                           ptr(out), ptr(wimg), ptr(bounds), ptr(partials), C.byref(npart), _stream(h)))
         return out, npart.value
-    tl = graph_columns(graph) if (kernel == "cols_f16" or (graph.groups is not None and not force_csr_kernel)) else graph.cols
+    tl = graph_columns(graph) if (kernel in ("cols", "cols_f16") or (graph.groups is not None and not force_csr_kernel)) else graph.cols
+    if kernel in ("cols", "cols_f16") and tl is None:
+        raise ValueError(f"the column NNConv kernels need the column structure: at most {t_max} edge types")
     if kernel == "cols_f16":
-        if tl is None or c != 32:
-            raise ValueError("the fp16-pair column kernel needs the column structure and width 32")
+        if (max_in_degree if max_in_degree else graph.max_in_degree) < 1:
+            raise ValueError("the fp16-pair column NNConv kernel scales by an in-degree bound >= 1: this layout's largest "
+                             f"in-degree is {graph.max_in_degree}")
         wimg = torch.empty(lib.tgnn_nnconv_weight_image_floats(graph.n_types), dtype=torch.float32, device=h.device)
         bounds = torch.empty(2, dtype=torch.int32, device=h.device)
         check(lib.tgnn_nnconv_mean_cols_f16_fwd(ptr(h), c, int(h.shape[0]), ptr(tl.tile_col_ptr), ptr(tl.col_meta), ptr(tl.col_src),
                                                 ptr(wt), graph.n_types, ptr(_f32c(root, "root")), ptr(_f32c(bias, "bias")), n,
                                                 max_in_degree if max_in_degree else graph.max_in_degree, act, ptr(out), ptr(wimg),
                                                 ptr(bounds), ptr(partials), C.byref(npart), _stream(h)))
-    elif tl is not None and c == 32 and not force_csr_kernel and int(h.shape[0]) * c * 4 < 2 ** 31:
+    elif kernel == "cols" or (tl is not None and c == 32 and not force_csr_kernel and int(h.shape[0]) * c * 4 < 2 ** 31):
         wimg = torch.empty(lib.tgnn_nnconv_weight_image_floats(graph.n_types), dtype=torch.float32, device=h.device)
         check(lib.tgnn_nnconv_mean_cols_fwd(ptr(h), c, ptr(tl.tile_col_ptr), ptr(tl.col_meta), ptr(tl.col_src), ptr(wt),
                                             graph.n_types, ptr(_f32c(root, "root")), ptr(_f32c(bias, "bias")), n, c, act,
