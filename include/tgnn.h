@@ -463,6 +463,21 @@ int tgnn_backward(const tgnn_model_dims *dims, const void *const *params_host, v
                   const float *adj_edge_attr, const tgnn_graph *graph, const tgnn_train_graph *tgraph,
                   const tgnn_train_save *keep, const float *probs, const float *dprobs, void *ws, size_t ws_bytes,
                   tgnn_stream_t stream);
+/* tgnn_backward with the edge groups of both directions (groups == NULL: tgnn_backward itself, which calls this).  With
+ * tgnn_set_nnconv_bwd_eg(1), groups given and tgnn_nnconv_bwd_eg_ok, every layer's NNConv adjoint runs on tgnn_nnconv_bwd_eg;
+ * otherwise the chain as before.  The switch is read once per call.  tgnn_backward_workspace_bytes covers both routes whatever the
+ * switch says. */
+typedef struct tgnn_train_groups {
+    const int32_t *fwd_tile_grp_ptr, *fwd_grp; /* tgnn_nnconv_eg_build over the adjacency CSR (the forward's structure) */
+    const int32_t *bwd_tile_grp_ptr, *bwd_grp; /* the same over adjT_rowptr / adjT_src / adjT_type */
+    const int32_t *type_major;                 /* tgnn_nnconv_bwd_eg_build over the forward structure */
+    int64_t n_list;                            /* its group count */
+    int32_t max_in_degree, max_out_degree;     /* of the adjacency graph */
+} tgnn_train_groups;
+int tgnn_backward_groups(const tgnn_model_dims *dims, const void *const *params_host, void *const *grads_host, const float *x,
+                         const float *adj_edge_attr, const tgnn_graph *graph, const tgnn_train_graph *tgraph,
+                         const tgnn_train_groups *groups, const tgnn_train_save *keep, const float *probs, const float *dprobs,
+                         void *ws, size_t ws_bytes, tgnn_stream_t stream);
 
 /* ---- the same forward for ONE SHARD of a node-range partition (one process per GPU) -------------------------
  * This device owns rows [0, n_own) of a layout whose buffers carry n_rows - n_own halo rows of other shards behind
@@ -1044,6 +1059,40 @@ int tgnn_sigmoid_mlp_bwd_tall64(const float *x, int64_t n_rows, int32_t d0, int3
                                 const float *d_out, int64_t ld_dout, float *dw1, float *db1, float *dw2, float *db2, float *dw3,
                                 float *db3, float *dx, void *ws, size_t ws_bytes, tgnn_stream_t stream);
 int32_t tgnn_set_mlp_bwd_tall64(int32_t on);
+/* The NNConv adjoint on edge groups (csrc/nnconv_bwd_eg.hip), widths 32 and 64, without the type sums
+ * S' [N][(T+1) C] of tgnn_nnconv_type_sum's route.  With g = dz / max(in-degree, 1):
+ *   dh [N][C]        = sum over the out-edges (v -> u) of g[u] . W_type^T + dz[v] . root^T: the forward's edge-group kernel in its sum
+ *                      form over the groups of the TRANSPOSED adjacency CSR (tgnn_nnconv_eg_build over adjT_rowptr / adjT_src /
+ *                      adjT_type), fp16-pair split as in the forward (1e-5 of the largest entry);
+ *   dwcat [T+1][C][C] = per type the sum of h[src]^T (x) g[dst] over its edges, entry T = d root = h^T . dz, as [in][out]: per group
+ *                      of the FORWARD structure a 16-edge outer product on the exact-fp32 matrix instruction, partial tiles per
+ *                      (block, type) folded in block order.  No atomics: the same bits on every call.
+ * tgnn_nnconv_bwd_eg_ok: 1 iff c is 32 or 64, 1 <= n_types <= 18 (width 64: tgnn_nnconv64_eg_max_types) or 22 (width 32:
+ * tgnn_nnconv_cols_max_types), both degrees lie in 1 .. 2048, n_nodes c 4 < 2^31 and both group structures are there; host only.
+ * tgnn_nnconv_bwd_eg_workspace_bytes: what the op wants (256-byte aligned), 0 where no layout of that shape holds the predicate.
+ * tgnn_nnconv_bwd_eg_list_ints / _build: the type-major list of the forward structure -- kBwdEgListHeader = 64 ints (entries
+ * 0 .. T + 1: where each type starts, the root groups being type T; entry T + 1 = the number of groups), then (group, tile) pairs
+ * sorted by type, the groups of a type in ascending order; two launches, deterministic; built once per layout.
+ * tgnn_nnconv_bwd_eg_dw_blocks: the dW kernel's grid for a list of n_list groups (one block per 16 groups, at most 512).
+ * tgnn_nnconv_bwd_eg: h, dz, g, dh are [n_nodes][c] with row stride ld == c, 16-byte aligned; n_list = the list's group count (entry
+ * T + 1, read back at build); max_in_degree / max_out_degree: of the adjacency graph.  Where the predicate fails:
+ * TGNN_ERR_UNSUPPORTED, tgnn_last_error names the limit, nothing is launched or written, and there is no fall-back.  Argument errors
+ * (null pointer, alignment, row stride): TGNN_ERR_INVALID_ARG, nothing written.
+ * tgnn_set_nnconv_bwd_eg: 0 / 1 (default 0) -- 1 sends the NNConv adjoint of tgnn_backward_groups to this op where the predicate
+ * holds and the groups were given; returns the previous value; anything else only queries. */
+int32_t tgnn_nnconv_bwd_eg_ok(int32_t c, int64_t n_nodes, int32_t n_types, int32_t max_in_degree, int32_t max_out_degree,
+                              int32_t has_fwd_groups, int32_t has_bwd_groups);
+size_t tgnn_nnconv_bwd_eg_workspace_bytes(int64_t n_nodes, int64_t n_groups_cap, int32_t n_types, int32_t c);
+size_t tgnn_nnconv_bwd_eg_list_ints(int64_t n_groups_cap);
+int32_t tgnn_nnconv_bwd_eg_dw_blocks(int64_t n_list);
+int tgnn_nnconv_bwd_eg_build(const int32_t *tile_grp_ptr, const int32_t *grp, int64_t n_nodes, int32_t n_types, int32_t *type_major,
+                             tgnn_stream_t stream);
+int tgnn_nnconv_bwd_eg(const float *h, int64_t ld, const float *dz, const float *g, const int32_t *fwd_tile_grp_ptr,
+                       const int32_t *fwd_grp, const int32_t *bwd_tile_grp_ptr, const int32_t *bwd_grp, const int32_t *type_major,
+                       int64_t n_list, const float *wtab, const float *root, int64_t n_nodes, int32_t n_types, int32_t c,
+                       int32_t max_in_degree, int32_t max_out_degree, float *dh, float *dwcat, void *ws, size_t ws_bytes,
+                       tgnn_stream_t stream);
+int32_t tgnn_set_nnconv_bwd_eg(int32_t on);
 /* NNConv backward building block (edge_conv.py:25; PyG NNConv: message = x_j . W_e, mean, + x . root):
  * out [n_nodes][(n_types + 1) * c], c = 32 or 64 (the network width; n_types <= 63): slot t < n_types = sum over the
  * row's CSR slots of type t of rows[src];

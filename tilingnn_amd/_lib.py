@@ -62,6 +62,12 @@ class TrainGraphDesc(C.Structure):
                 ("colT_rowptr", C.c_void_p), ("colT_src", C.c_void_p), ("deg", C.c_void_p), ("inv_deg", C.c_void_p)]
 
 
+class TrainGroupsDesc(C.Structure):
+    """tgnn_train_groups"""
+    _fields_ = [("fwd_tile_grp_ptr", C.c_void_p), ("fwd_grp", C.c_void_p), ("bwd_tile_grp_ptr", C.c_void_p), ("bwd_grp", C.c_void_p),
+                ("type_major", C.c_void_p), ("n_list", C.c_int64), ("max_in_degree", C.c_int32), ("max_out_degree", C.c_int32)]
+
+
 ALLREDUCE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)
 ALLTOALL_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p)
 
@@ -215,6 +221,16 @@ def _load() -> C.CDLL:
         "tgnn_backward_workspace_bytes": (sz, [C.POINTER(ModelDims), i64, i32]),
         "tgnn_backward": (C.c_int, [C.POINTER(ModelDims), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), p, p,
                                     C.POINTER(Graph), C.POINTER(TrainGraphDesc), C.POINTER(TrainSave), p, p, p, sz, p]),
+        "tgnn_backward_groups": (C.c_int, [C.POINTER(ModelDims), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), p, p,
+                                           C.POINTER(Graph), C.POINTER(TrainGraphDesc), C.POINTER(TrainGroupsDesc),
+                                           C.POINTER(TrainSave), p, p, p, sz, p]),
+        "tgnn_nnconv_bwd_eg_ok": (i32, [i32, i64, i32, i32, i32, i32, i32]),
+        "tgnn_nnconv_bwd_eg_workspace_bytes": (sz, [i64, i64, i32, i32]),
+        "tgnn_nnconv_bwd_eg_list_ints": (sz, [i64]),
+        "tgnn_nnconv_bwd_eg_dw_blocks": (i32, [i64]),
+        "tgnn_nnconv_bwd_eg_build": (C.c_int, [p, p, i64, i32, p, p]),
+        "tgnn_nnconv_bwd_eg": (C.c_int, [p, i64, p, p, p, p, p, p, p, i64, p, p, i64, i32, i32, i32, i32, p, p, p, sz, p]),
+        "tgnn_set_nnconv_bwd_eg": (i32, [i32]),
         "tgnn_forward_train": (C.c_int, [C.POINTER(ModelDims), C.POINTER(C.c_void_p), p, p, C.POINTER(Graph),
                                          C.POINTER(TrainSave), p, p, sz, p, p]),
         "tgnn_gin_aggregate": (C.c_int, [p, i64, p, p, p, p, i64, i32, p, p]),
@@ -307,6 +323,8 @@ EXPORTED_SYMBOLS = (
     "tgnn_sigmoid_mlp_bwd_workspace_bytes", "tgnn_sigmoid_mlp_bwd",
     "tgnn_sigmoid_mlp_bwd_fused_form", "tgnn_sigmoid_mlp_bwd_fused_workspace_bytes", "tgnn_sigmoid_mlp_bwd_fused", "tgnn_set_mlp_bwd_fused",
     "tgnn_sigmoid_mlp_bwd_tall64_ok", "tgnn_sigmoid_mlp_bwd_tall64_workspace_bytes", "tgnn_sigmoid_mlp_bwd_tall64", "tgnn_set_mlp_bwd_tall64",
+    "tgnn_backward_groups", "tgnn_nnconv_bwd_eg_ok", "tgnn_nnconv_bwd_eg_workspace_bytes", "tgnn_nnconv_bwd_eg_list_ints",
+    "tgnn_nnconv_bwd_eg_dw_blocks", "tgnn_nnconv_bwd_eg_build", "tgnn_nnconv_bwd_eg", "tgnn_set_nnconv_bwd_eg",
     "tgnn_nnconv_type_sum", "tgnn_csr_degree", "tgnn_unsupervised_loss_bwd",
     "tgnn_f32_to_bf16", "tgnn_nnconv64_image_elems", "tgnn_nnconv64_bf16_fwd", "tgnn_nnconv64_bf16_eg_fwd", "tgnn_gin64_bf16_fwd", "tgnn_collconv64_bf16_fwd", "tgnn_merge_bf16_fwd",
     "tgnn_dense_bf16_slots_fwd", "tgnn_forward_bf16_workspace_bytes", "tgnn_forward_bf16")

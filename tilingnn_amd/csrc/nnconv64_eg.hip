@@ -79,7 +79,10 @@ __global__ __launch_bounds__(256) void nnconv64_eg_image_kernel(const float *__r
     }
 }
 
-template <int WAVES, int ACT>
+// SUM (the adjoint's input gradient, nnconv_bwd_eg.hip: this op over the TRANSPOSED graph with the transposed table): the edge SUM
+// instead of the mean, no bias, no activation, no BatchNorm partials; the root group's rows come from a second array, passed in
+// `bias`'s place ([n rows][64] packed like h: dz where h is g = dz / deg).  The other instantiations keep their code.
+template <int WAVES, int ACT, bool SUM = false>
 __global__ __launch_bounds__(WAVES * 64) void nnconv64_eg_kernel(
     const float *__restrict__ h, uint32_t h_bytes, const int *__restrict__ tile_grp_ptr, const int2 *__restrict__ grp,
     const float *__restrict__ wimg, int n_types, const float *__restrict__ bias, int64_t n, float *__restrict__ out,
@@ -105,6 +108,8 @@ __global__ __launch_bounds__(WAVES * 64) void nnconv64_eg_kernel(
 
     const __amdgpu_buffer_rsrc_t h_rsrc =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(h), 0, (int)h_bytes, 0x00020000);   // beyond the rows: zeros
+    const __amdgpu_buffer_rsrc_t own_rsrc =
+        SUM ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(bias), 0, (int)h_bytes, 0x00020000) : h_rsrc;
     const uint32_t fq_bytes = (uint32_t)fq * 32u;
     auto load_four = [&](int p, int &s4, int &m4) {         // groups p .. p+3: lane (fj, fq) <- group p + fq, word fj
         const int pc = p < cend ? p : cbeg;                  // (never past the wave's share)
@@ -140,10 +145,18 @@ __global__ __launch_bounds__(WAVES * 64) void nnconv64_eg_kernel(
         auto issue_gather = [&](int s, int meta, float4 (&x)[4]) {
             const bool root = (meta & kEg64RootBit) != 0;    // wave-uniform
             const uint32_t off = root ? own_off : ((uint32_t)s << 8) + fq_bytes;   // s = -1: beyond the rows, loads zeros
+            if (SUM && root) {                               // (wave-uniform) the root rows of the sum form: the second array
 #pragma unroll
-            for (int kc = 0; kc < 2; ++kc) {
-                x[2 * kc] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(h_rsrc, off + 128u * kc, 0, 0));
-                x[2 * kc + 1] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(h_rsrc, off + 128u * kc + 16u, 0, 0));
+                for (int kc = 0; kc < 2; ++kc) {
+                    x[2 * kc] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(own_rsrc, off + 128u * kc, 0, 0));
+                    x[2 * kc + 1] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(own_rsrc, off + 128u * kc + 16u, 0, 0));
+                }
+            } else {
+#pragma unroll
+                for (int kc = 0; kc < 2; ++kc) {
+                    x[2 * kc] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(h_rsrc, off + 128u * kc, 0, 0));
+                    x[2 * kc + 1] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(h_rsrc, off + 128u * kc + 16u, 0, 0));
+                }
             }
             if (root) {
                 ++gtile;
@@ -151,7 +164,7 @@ __global__ __launch_bounds__(WAVES * 64) void nnconv64_eg_kernel(
             }
         };
         f32x4 d[2] = {zero4, zero4};                         // out tile: rows 4 fq + r, channel 32 half + 16 nb + fj
-        const float bias_r[2] = {bias[32 * half + fj], bias[32 * half + 16 + fj]};
+        const float bias_r[2] = {SUM ? 0.f : bias[32 * half + fj], SUM ? 0.f : bias[32 * half + 16 + fj]};
 
         // a group: its messages M = G . W_t[:, half] as fp16 pairs, folded into the tile by the selection operand
         auto consume = [&](int s, int m, int meta, const float4 (&x)[4]) {
@@ -178,7 +191,7 @@ __global__ __launch_bounds__(WAVES * 64) void nnconv64_eg_kernel(
                 gh[kc] = __builtin_bit_cast(f16x8, u32x4{h0, h1, h2, h3});
                 gl[kc] = __builtin_bit_cast(f16x8, u32x4{l0, l1, l2, l3});
             }
-            if (root) {                                      // the edge sum of rows 4 fq + r -> their mean; then S = I
+            if (!SUM && root) {                              // the edge sum of rows 4 fq + r -> their mean; then S = I
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int dg = __shfl(s, 4 * fq + r, 64);    // float bits of max(deg, 1) of row 4 fq + r, -1 = row >= n
@@ -211,7 +224,7 @@ __global__ __launch_bounds__(WAVES * 64) void nnconv64_eg_kernel(
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int dg = __shfl(s, 4 * fq + r, 64);
-                        float o = fmaf(d[nb][r], unscale, bias_r[nb]);
+                        float o = SUM ? d[nb][r] * unscale : fmaf(d[nb][r], unscale, bias_r[nb]);
                         if constexpr (ACT == TGNN_ACT_LEAKY_RELU) o = leakyf_(o);
                         if (dg >= 0) {                       // row < n
                             const int64_t v = ctile * 16 + 4 * fq + r;
@@ -318,12 +331,19 @@ void launch_nnconv64_eg_images(const float *wtab_all, const float *const *roots,
 
 int launch_nnconv64_eg(const float *h, int64_t n_src_rows, const int32_t *tile_grp_ptr, const int32_t *grp, const float *wimg,
                        int32_t n_types, const float *bias, int64_t n_nodes, int32_t act, float *out, double *bn_partial,
-                       int32_t *n_partials_host, hipStream_t s, const unsigned *h_max, const unsigned *root_max) {
+                       int32_t *n_partials_host, hipStream_t s, const unsigned *h_max, const unsigned *root_max,
+                       const float *sum_root_rows) {
     constexpr int WAVES = kEg64Waves;
     const bool leaky = act == TGNN_ACT_LEAKY_RELU;
-    auto kern = leaky ? nnconv64_eg_kernel<WAVES, TGNN_ACT_LEAKY_RELU> : nnconv64_eg_kernel<WAVES, TGNN_ACT_NONE>;
-    static LdsOptIn site[2];
-    TGNN_CHECK_HIP(opt_in_dynamic_lds(kern, (int)kEg64MaxLds, site[leaky]));
+    const bool sum = sum_root_rows != nullptr;               // (the adjoint's form: act, bias and bn_partial are not read)
+    auto kern = sum ? nnconv64_eg_kernel<WAVES, TGNN_ACT_NONE, true>
+                    : leaky ? nnconv64_eg_kernel<WAVES, TGNN_ACT_LEAKY_RELU> : nnconv64_eg_kernel<WAVES, TGNN_ACT_NONE>;
+    static LdsOptIn site[3];
+    TGNN_CHECK_HIP(opt_in_dynamic_lds(kern, (int)kEg64MaxLds, site[sum ? 2 : leaky]));
+    if (sum) {
+        bias = sum_root_rows;
+        bn_partial = nullptr;
+    }
     const int64_t n_tiles = (n_nodes + 15) / 16;
     int64_t blocks = (n_tiles + WAVES - 1) / WAVES;          // at least one tile per wave
     const int64_t cap = cus_minus(32);                       // (CUs left to the collision chain, as in the width-32 path)
@@ -367,5 +387,5 @@ extern "C" int tgnn_nnconv64_mean_eg_fwd(const float *h, int64_t ldh, int64_t n_
     launch_absmax(h, n_src_rows * 64, bounds_scratch, s);
     launch_nnconv64_eg_images(wtab, &root, n_types, 1, wimg_scratch, bounds_scratch + 1, s);
     return launch_nnconv64_eg(h, n_src_rows, tile_grp_ptr, grp, wimg_scratch, n_types, bias, n_nodes, act, out, bn_partial,
-                              n_partials_host, s, bounds_scratch, bounds_scratch + 1);
+                              n_partials_host, s, bounds_scratch, bounds_scratch + 1, nullptr);
 }

@@ -48,7 +48,10 @@ struct EgShard {
     double *group_rows;                        // 16 x 64 doubles
 };
 
-template <int WAVES, int OCC, int ACT, bool SHARD = false>
+// SUM (the adjoint's input gradient, nnconv_bwd_eg.hip: this op over the TRANSPOSED graph with the transposed table): the edge SUM
+// instead of the mean, no bias, no activation, no BatchNorm partials; the root group's rows come from a second array, passed in
+// `bias`'s place ([N][32] packed like h: dz where h is g = dz / deg), with S = I.  The other instantiations keep their code.
+template <int WAVES, int OCC, int ACT, bool SHARD = false, bool SUM = false>
 __global__ __launch_bounds__(WAVES * 64, OCC) void nnconv32_eg_kernel(
     const float *__restrict__ h, const int *__restrict__ tile_grp_ptr, const int2 *__restrict__ grp,
     const float *__restrict__ wimg, int n_types, const float *__restrict__ bias, int64_t n,
@@ -88,12 +91,14 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void nnconv32_eg_kernel(
     const int cbeg = __builtin_amdgcn_readfirstlane(tile_grp_ptr[t0]);
     const int cend = __builtin_amdgcn_readfirstlane(tile_grp_ptr[t1]);
 
-    const float bias0 = bias[fj], bias1 = bias[16 + fj];
+    const float bias0 = SUM ? 0.f : bias[fj], bias1 = SUM ? 0.f : bias[16 + fj];
     // BN partial sums of this lane: channel 16 m + fj over the rows 4 fq .. 4 fq + 3 of every tile
     double bs[2] = {0, 0}, bq[2] = {0, 0};
 
     const __amdgpu_buffer_rsrc_t h_rsrc =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(h), 0, (int)0x80000000u, 0x00020000);   // 2 GB window
+    const __amdgpu_buffer_rsrc_t own_rsrc =
+        SUM ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(bias), 0, (int)0x80000000u, 0x00020000) : h_rsrc;
     const uint32_t fq_bytes = (uint32_t)fq * 32u;
     auto load_four = [&](int p, int &s4, int &m4) {         // groups p .. p+3: lane (fj, fq) <- group p + fq, word fj
         const int pc = p < cend ? p : cbeg;                  // (reads past cend stay inside the slack)
@@ -126,8 +131,13 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void nnconv32_eg_kernel(
 #else
         const uint32_t off = root ? own_off : ((uint32_t)s << 7) + fq_bytes;   // s = -1: beyond the window, loads zeros
 #endif
-        x[0] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(h_rsrc, off, 0, 0));
-        x[1] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(h_rsrc, off + 16u, 0, 0));
+        if (SUM && root) {                                   // (wave-uniform) the root rows of the sum form: the second array
+            x[0] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(own_rsrc, off, 0, 0));
+            x[1] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(own_rsrc, off + 16u, 0, 0));
+        } else {
+            x[0] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(h_rsrc, off, 0, 0));
+            x[1] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(h_rsrc, off + 16u, 0, 0));
+        }
         if (root) {
             ++gtile;
             own_off = own_off_of(gtile);
@@ -193,7 +203,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void nnconv32_eg_kernel(
         Msg r;
         r.a0 = u32x2{a00, a01}; r.b0 = u32x2{b00, b01}; r.a1 = u32x2{a10, a11}; r.b1 = u32x2{b10, b11};
         r.sel = sel0;
-        if (meta & kEgRootBit) {                             // S = diag(max(deg, 1)): s = its float bits for row fj
+        if (!SUM && (meta & kEgRootBit)) {                   // S = diag(max(deg, 1)): s = its float bits for row fj
             asm volatile("" ::: "memory");                   // (a real branch: one group in ~16 takes it)
             const _Float16 dg = (_Float16)__int_as_float(s);
             r.sel = r.sel * dg;
@@ -222,9 +232,9 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void nnconv32_eg_kernel(
         for (int r = 0; r < 4; ++r) {
             const int dg = __shfl(s, 4 * fq + r, 64);        // row 4 fq + r's word
             const bool valid = dg >= 0;
-            const float inv = unscale * __builtin_amdgcn_rcpf(__int_as_float(dg));
-            float o0 = fmaf(d0[r], inv, bias0);
-            float o1 = fmaf(d1[r], inv, bias1);
+            const float inv = SUM ? unscale : unscale * __builtin_amdgcn_rcpf(__int_as_float(dg));
+            float o0 = SUM ? d0[r] * inv : fmaf(d0[r], inv, bias0);
+            float o1 = SUM ? d1[r] * inv : fmaf(d1[r], inv, bias1);
             if constexpr (ACT == TGNN_ACT_LEAKY_RELU) {
                 o0 = leakyf_(o0);
                 o1 = leakyf_(o1);
@@ -431,7 +441,7 @@ constexpr size_t kEgMaxLds = 160 * 1024 - 256;
 
 int launch_nnconv_eg(const float *h, const int32_t *tile_grp_ptr, const int32_t *grp, const float *wimg, int32_t n_types, const float *bias, int64_t n_nodes, int32_t act, float *out,
                      double *bn_partial, int32_t *n_partials_host, hipStream_t s, const unsigned *h_max, const unsigned *root_max,
-                     unsigned long long *stamp, const EgShardPack *pack) {
+                     unsigned long long *stamp, const EgShardPack *pack, const float *sum_root_rows) {
 #ifdef TGNN_ABL_EGW8                                        // (ablation: two 8-wave blocks per CU instead of one 16-wave block)
     constexpr int WAVES = 8, kBlocksPerCu = 2;
 #else
@@ -439,10 +449,16 @@ int launch_nnconv_eg(const float *h, const int32_t *tile_grp_ptr, const int32_t 
 #endif
     const bool leaky = act == TGNN_ACT_LEAKY_RELU;
     const bool shard = pack && pack->counter && bn_partial && leaky;
-    auto kern = shard ? nnconv32_eg_kernel<WAVES, 4, TGNN_ACT_LEAKY_RELU, true>
-                      : leaky ? nnconv32_eg_kernel<WAVES, 4, TGNN_ACT_LEAKY_RELU> : nnconv32_eg_kernel<WAVES, 4, TGNN_ACT_NONE>;
-    static LdsOptIn site[3];
-    TGNN_CHECK_HIP(opt_in_dynamic_lds(kern, (int)kEgMaxLds, site[shard ? 2 : leaky]));
+    const bool sum = sum_root_rows != nullptr;               // (the adjoint's form: act, bias, bn_partial and pack are not read)
+    auto kern = sum     ? nnconv32_eg_kernel<WAVES, 4, TGNN_ACT_NONE, false, true>
+                : shard ? nnconv32_eg_kernel<WAVES, 4, TGNN_ACT_LEAKY_RELU, true>
+                        : leaky ? nnconv32_eg_kernel<WAVES, 4, TGNN_ACT_LEAKY_RELU> : nnconv32_eg_kernel<WAVES, 4, TGNN_ACT_NONE>;
+    static LdsOptIn site[4];
+    TGNN_CHECK_HIP(opt_in_dynamic_lds(kern, (int)kEgMaxLds, site[sum ? 3 : shard ? 2 : leaky]));
+    if (sum) {
+        bias = sum_root_rows;
+        bn_partial = nullptr;
+    }
     EgShard sh{};
     if (shard) sh = EgShard{pack->send_row_ptr, pack->send_row_slot, pack->msg, pack->msg_idx, pack->n_msg, pack->sums, pack->counter, pack->group_rows};
     const int64_t n_tiles = (n_nodes + 15) / 16;
@@ -489,5 +505,5 @@ extern "C" int tgnn_nnconv_mean_eg_fwd(const float *h, int64_t ldh, int64_t n_sr
     launch_absmax(h, n_src_rows * 32, bounds_scratch, s);
     launch_nnconv_weight_image(wtab, &root, n_types, 1, wimg_scratch, s, bounds_scratch + 1, kEgImageScale);
     return launch_nnconv_eg(h, tile_grp_ptr, grp, wimg_scratch, n_types, bias, n_nodes, act, out, bn_partial,
-                            n_partials_host, s, bounds_scratch, bounds_scratch + 1, nullptr, nullptr);
+                            n_partials_host, s, bounds_scratch, bounds_scratch + 1, nullptr, nullptr, nullptr);
 }

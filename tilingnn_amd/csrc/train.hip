@@ -9,13 +9,15 @@
 // Walk, given d loss / d probs:
 //   final Linear_trans (sigmoid, no BN)  ->  final MLP (4 x Linear/LeakyReLU/BatchNorm)  ->  d cat [N, (D+1) C]
 //   for i = D-1 .. 0:  merge backward (+ both BatchNorm reductions)  ->  BatchNorm/LeakyReLU apply, twice
-//                      ->  NNConv adjoint (one type-sum pass over the transposed graph; dense products; edge MLP)
+//                      ->  NNConv adjoint (one type-sum pass over the transposed graph; dense products; edge MLP --
+//                          or, tgnn_set_nnconv_bwd_eg with tgnn_backward_groups: the edge-group adjoint, nnconv_bwd_eg.hip)
 //                      ->  GIN adjoint (sigmoid MLP, aggregation over the transposed collision graph)
 //   init MLP (2 x Linear/LeakyReLU/BatchNorm)
 // Gradients go to grads_host[k], indexed like params_host (entries of buffers -- running statistics, GIN's eps -- are
 // not touched).
 #include "mlp_bwd64_plan.h"
 #include "mlp_bwd_plan.h"
+#include "nnconv_bwd_eg_plan.h"
 #include "tgnn_common.h"
 
 namespace tgnn {
@@ -45,8 +47,8 @@ static constexpr int64_t kRowMajorKBlock = 32;
 
 struct BwdBuffers {
     float *dcat, *buf[3], *dy1, *dy2, *dz1, *gsc, *dz2, *sbwd, *wd, *dh1, *dw_in, *dwcat, *rows, *carry[2], *coef, *wt, *zero;
-    void *red, *wg, *mlp;
-    size_t red_bytes, wg_bytes, mlp_bytes, total;
+    void *red, *wg, *mlp, *eg;
+    size_t red_bytes, wg_bytes, mlp_bytes, eg_bytes, total;
 };
 
 static BwdBuffers carve_bwd(const tgnn_model_dims &d, int64_t n, int32_t T, void *ws, size_t ws_bytes) {
@@ -92,6 +94,10 @@ static BwdBuffers carve_bwd(const tgnn_model_dims &d, int64_t n, int32_t T, void
         if (v > mlp) mlp = v;
     b.mlp_bytes = mlp;
     b.mlp = a.bytes(mlp);
+    // the edge-group NNConv adjoint (nnconv_bwd_eg.hip) has an area of its own wherever its shape limits hold, whatever
+    // tgnn_set_nnconv_bwd_eg says: the same rule
+    b.eg_bytes = nnconv_bwd_eg_workspace_bytes(nn, 0, T, c);
+    b.eg = b.eg_bytes ? a.bytes(b.eg_bytes) : nullptr;
     b.total = a.off + 256;
     return b;
 }
@@ -115,6 +121,14 @@ extern "C" int tgnn_backward(const tgnn_model_dims *dims, const void *const *par
                              const float *x, const float *adj_edge_attr, const tgnn_graph *graph,
                              const tgnn_train_graph *tgraph, const tgnn_train_save *keep, const float *probs,
                              const float *dprobs, void *ws, size_t ws_bytes, tgnn_stream_t stream) {
+    return tgnn_backward_groups(dims, params_host, grads_host, x, adj_edge_attr, graph, tgraph, nullptr, keep, probs, dprobs, ws, ws_bytes,
+                                stream);
+}
+
+extern "C" int tgnn_backward_groups(const tgnn_model_dims *dims, const void *const *params_host, void *const *grads_host,
+                                    const float *x, const float *adj_edge_attr, const tgnn_graph *graph,
+                                    const tgnn_train_graph *tgraph, const tgnn_train_groups *groups, const tgnn_train_save *keep,
+                                    const float *probs, const float *dprobs, void *ws, size_t ws_bytes, tgnn_stream_t stream) {
     DeviceGuard guard__(stream);
     TGNN_CHECK_ARG(dims && params_host && grads_host && x && graph && tgraph && keep && probs && dprobs, "null pointer");
     const int c = dims->network_width, D = dims->network_depth, fx = dims->node_features_dim,
@@ -192,6 +206,12 @@ extern "C" int tgnn_backward(const tgnn_model_dims *dims, const void *const *par
     // tgnn_set_mlp_bwd_tall64, read once per call and on its own: the GIN adjoint at width 64 on mlp_bwd_tall64_kernel
     const bool tall64_gin = tgnn_set_mlp_bwd_tall64(-1) == 1 && mlp_bwd_tall64_ok(n, c, 32, 64, c);
     const auto mlp_bwd_gin = tall64_gin ? tgnn_sigmoid_mlp_bwd_tall64 : fused_gin ? tgnn_sigmoid_mlp_bwd_fused : tgnn_sigmoid_mlp_bwd;
+    // tgnn_set_nnconv_bwd_eg, read once per call: the NNConv adjoint on edge groups iff the switch is on, the groups were given and
+    // nnconv_bwd_eg_plan.h's predicate holds; else the chain below exactly as before
+    const bool eg_nnconv = tgnn_set_nnconv_bwd_eg(-1) == 1 && groups && b.eg &&
+                           nnconv_bwd_eg_ok(c, n, T, groups->max_in_degree, groups->max_out_degree,
+                                            groups->fwd_tile_grp_ptr && groups->fwd_grp && groups->type_major,
+                                            groups->bwd_tile_grp_ptr && groups->bwd_grp);
     auto slot = [&](int k) { return b.dcat + (size_t)k * c; };           // row stride cat
     const float *carry = nullptr;
     for (int i = D - 1; i >= 0; --i) {
@@ -209,15 +229,21 @@ extern "C" int tgnn_backward(const tgnn_model_dims *dims, const void *const *par
         // NNConv adjoint
         const float *h = keep->skip + (size_t)i * n * c;
         const float *wtab = keep->wtab + (size_t)i * (T > 0 ? T : 1) * c * c;
-        TGNN_TRYB(tgnn_nnconv_type_sum(b.gsc, c, b.gsc, c, tgraph->deg, tgraph->adjT_rowptr, tgraph->adjT_src, tgraph->adjT_type,
-                                       n, T, c, b.sbwd, stream));
-        TGNN_TRYB(tgnn_swap_leading(wtab, T, c, c, b.wd, T + 1, stream));
-        TGNN_TRYB(tgnn_swap_leading(P.f(pb + 6), 1, c, c, b.wd + (size_t)T * c, T + 1, stream));
-        TGNN_TRYB(tgnn_dense_act_fwd(b.sbwd, (int64_t)(T + 1) * c, kRowMajorKBlock, nullptr, b.wd, b.zero, n, (T + 1) * c, c, TGNN_ACT_NONE,
-                                     b.dh1, c, nullptr, nullptr, stream));
-        TGNN_TRYB(tgnn_wgrad(h, c, b.sbwd, (int64_t)(T + 1) * c, 0, n, c, (T + 1) * c, b.dw_in, nullptr, b.wg, b.wg_bytes,
-                             stream));
-        TGNN_TRYB(tgnn_swap_leading(b.dw_in, c, T + 1, c, b.dwcat, c, stream));
+        if (eg_nnconv) {
+            TGNN_TRYB(tgnn_nnconv_bwd_eg(h, c, b.dz1, b.gsc, groups->fwd_tile_grp_ptr, groups->fwd_grp, groups->bwd_tile_grp_ptr,
+                                         groups->bwd_grp, groups->type_major, groups->n_list, wtab, P.f(pb + 6), n, T, c,
+                                         groups->max_in_degree, groups->max_out_degree, b.dh1, b.dwcat, b.eg, b.eg_bytes, stream));
+        } else {
+            TGNN_TRYB(tgnn_nnconv_type_sum(b.gsc, c, b.gsc, c, tgraph->deg, tgraph->adjT_rowptr, tgraph->adjT_src, tgraph->adjT_type,
+                                           n, T, c, b.sbwd, stream));
+            TGNN_TRYB(tgnn_swap_leading(wtab, T, c, c, b.wd, T + 1, stream));
+            TGNN_TRYB(tgnn_swap_leading(P.f(pb + 6), 1, c, c, b.wd + (size_t)T * c, T + 1, stream));
+            TGNN_TRYB(tgnn_dense_act_fwd(b.sbwd, (int64_t)(T + 1) * c, kRowMajorKBlock, nullptr, b.wd, b.zero, n, (T + 1) * c, c,
+                                         TGNN_ACT_NONE, b.dh1, c, nullptr, nullptr, stream));
+            TGNN_TRYB(tgnn_wgrad(h, c, b.sbwd, (int64_t)(T + 1) * c, 0, n, c, (T + 1) * c, b.dw_in, nullptr, b.wg, b.wg_bytes,
+                                 stream));
+            TGNN_TRYB(tgnn_swap_leading(b.dw_in, c, T + 1, c, b.dwcat, c, stream));
+        }
         TGNN_CHECK_HIP(hipMemcpyAsync(G(pb + 6), b.dwcat + (size_t)T * c * c, sizeof(float) * c * c, hipMemcpyDeviceToDevice, s));
         TGNN_TRYB(tgnn_colsum(b.dz1, c, n, c, G(pb + 7), b.red, b.red_bytes, stream));
         TGNN_TRYB(tgnn_add_into(b.dh1, c, n, c, slot(i), cat, stream));

@@ -22,7 +22,9 @@ Adjoints, per forward kernel (C = network width, T edge types, D layers):
   GIN              t1, t2 re-derived from the kept aggregate; three sigmoid/Linear adjoints; the aggregation's adjoint is
                    the aggregation on the transposed collision graph (tgnn_gin_aggregate).
   (set_mlp_bwd_fused(1): the sigmoid-MLP adjoints of both branches as kernels of their own, csrc/mlp_bwd.hip -- opt-in;
-   set_mlp_bwd_tall64(1): the GIN adjoint at width 64 as a kernel of its own, same file -- opt-in, a switch of its own.)
+   set_mlp_bwd_tall64(1): the GIN adjoint at width 64 as a kernel of its own, same file -- opt-in, a switch of its own;
+   set_nnconv_bwd_eg(1): the NNConv adjoint on edge groups, csrc/nnconv_bwd_eg.hip -- dh = the forward's edge-group kernel over the
+   transposed graph, the weight gradients as per-type sums of 16-edge outer products, no S' -- opt-in, a switch of its own.)
 Widths 32 (the reference's network_width, inputs/config.py:38) and 64 (BASELINE config 3); other widths raise.  Width 64
 runs the same schedule: the width-64 forms of the adjoint kernels (type sums one wave per row, merge backward, GIN
 aggregation, the slot-major weight gradient over 64-wide slots) and the forward's generic GIN kernel keeping the aggregate.
@@ -190,6 +192,48 @@ class TrainGraph:
         self.deg = torch.empty(n, dtype=torch.float32, device=dev)
         self.inv_deg = torch.empty(n, dtype=torch.float32, device=dev)
         check(lib.tgnn_csr_degree(ptr(graph.adj_rowptr), n, ptr(self.deg), ptr(self.inv_deg), _lib.current_stream(dev)))
+        self.groups_t: Optional[TransposedGroups] = None             # built by ensure_groups_t: nothing of it exists until asked for
+
+    def ensure_groups_t(self) -> Optional["TransposedGroups"]:
+        """What the edge-group NNConv adjoint reads beyond the forward's structure, built on first use (set_nnconv_bwd_eg(1) or
+        nnconv_backward(kernel="eg")) and kept: the edge groups of the transposed adjacency CSR, the type-major list of the forward
+        structure's groups, and -- the ONE read-back, here and never in the layer loop -- both largest degrees and the list's
+        length.  None where the layout has more edge types than the group structure takes."""
+        if self.groups_t is not None or self.__dict__.get("_groups_t_none"):
+            return self.groups_t
+        g = self.g
+        n, ea, T = g.n_nodes, g.n_adj_edges, g.n_types
+        fwd = ops.graph_groups(g) if T >= 1 else None
+        bwd = ops.build_nnconv_groups(n, ea, T, self.adjT_rowptr, self.adjT_src, self.adjT_type) if fwd is not None else None
+        if fwd is None or bwd is None:
+            self.__dict__["_groups_t_none"] = True
+            return None
+        dev = self.adjT_rowptr.device
+        cap = int(fwd.grp.shape[0]) // 16
+        type_major = torch.empty(int(lib.tgnn_nnconv_bwd_eg_list_ints(cap)), dtype=torch.int32, device=dev)
+        check(lib.tgnn_nnconv_bwd_eg_build(ptr(fwd.tile_grp_ptr), ptr(fwd.grp), n, T, ptr(type_major), _lib.current_stream(dev)))
+        out_deg = (self.adjT_rowptr[1:n + 1] - self.adjT_rowptr[:n]).max()
+        in_deg = (g.adj_rowptr[1:n + 1] - g.adj_rowptr[:n]).max()
+        words = torch.stack([out_deg, in_deg, type_major[T + 1]]).tolist()
+        self.groups_t = TransposedGroups(fwd, bwd, type_major, int(words[2]), int(words[1]), int(words[0]), cap)
+        return self.groups_t
+
+    def groups_desc(self) -> Optional["_lib.TrainGroupsDesc"]:
+        gt = self.groups_t
+        if gt is None:
+            return None
+        return _lib.TrainGroupsDesc(gt.fwd.tile_grp_ptr.data_ptr(), gt.fwd.grp.data_ptr(), gt.bwd.tile_grp_ptr.data_ptr(),
+                                    gt.bwd.grp.data_ptr(), gt.type_major.data_ptr(), gt.n_list, gt.max_in_degree, gt.max_out_degree)
+
+
+class TransposedGroups:
+    """TrainGraph.groups_t: `bwd` = ops.NNConvGroups over adjT_rowptr / adjT_src / adjT_type, `fwd` = the forward's, `type_major`
+    = tgnn_nnconv_bwd_eg_build's list of the forward groups (n_list of them), both largest degrees of the adjacency graph."""
+
+    def __init__(self, fwd, bwd, type_major, n_list, max_in_degree, max_out_degree, groups_cap):
+        self.fwd, self.bwd, self.type_major, self.n_list = fwd, bwd, type_major, n_list
+        self.max_in_degree, self.max_out_degree, self.groups_cap = max_in_degree, max_out_degree, groups_cap
+        self.tile_grp_ptr, self.grp = bwd.tile_grp_ptr, bwd.grp
 
 
 def _train_graph(net, n: int, adj_e_index: Tensor, adj_e_features: Tensor, col_e_idx: Tensor) -> TrainGraph:
@@ -288,6 +332,31 @@ def set_mlp_bwd_tall64(on: int) -> int:
     return int(lib.tgnn_set_mlp_bwd_tall64(int(on)))
 
 
+def set_nnconv_bwd_eg(on: int) -> int:
+    """1: tgnn_backward_groups and `nnconv_backward(kernel=None)` run the NNConv adjoint on edge groups (csrc/nnconv_bwd_eg.hip)
+    where its predicate holds (widths 32 / 64, 1 <= T <= 22 / 18, degrees up to 2 048) (tgnn_set_nnconv_bwd_eg; default off).
+    Returns the previous setting; anything but 0 / 1 only queries."""
+    return int(lib.tgnn_set_nnconv_bwd_eg(int(on)))
+
+
+def _nnconv_bwd_eg_why_not(tg: "TrainGraph", c: int) -> Optional[str]:
+    """None where the edge-group adjoint takes the layout at width c (builds groups_t on first use), else the limit that fails."""
+    g = tg.g
+    n, T = g.n_nodes, g.n_types
+    if c not in (32, 64):
+        return f"width {c}: the edge-group NNConv adjoint is built for widths 32 and 64"
+    t_max = int(lib.tgnn_nnconv64_eg_max_types()) if c == 64 else int(lib.tgnn_nnconv_cols_max_types())
+    if not 1 <= T <= t_max:
+        return f"{T} edge types: the edge-group NNConv adjoint takes 1 .. {t_max} at width {c}"
+    gt = tg.ensure_groups_t()
+    if gt is None:
+        return "the layout has no edge groups"
+    if lib.tgnn_nnconv_bwd_eg_ok(c, n, T, gt.max_in_degree, gt.max_out_degree, 1, 1) != 1:
+        return (f"in-degree {gt.max_in_degree}, out-degree {gt.max_out_degree}, {n} rows: the edge-group NNConv adjoint takes degrees "
+                f"1 .. 2048 and rows within 2 GB")
+    return None
+
+
 def sigmoid_mlp_backward(weights, x: Tensor, t3: Tensor, d_out: Tensor, grads: Dict[str, Tensor], names, need_dx: bool,
                          kernel: Optional[str] = None):
     """Three Linear + Sigmoid layers without BatchNorm (GraphConv's edge MLP, GINConv's MLP) in one library call.
@@ -328,13 +397,26 @@ def sigmoid_mlp_backward(weights, x: Tensor, t3: Tensor, d_out: Tensor, grads: D
 
 
 def nnconv_backward(conv, prefix: str, tg: TrainGraph, wtab: Tensor, h: Tensor, dz: Tensor, g_scaled: Tensor,
-                    edge_attr: Tensor, grads: Dict[str, Tensor]) -> Tensor:
+                    edge_attr: Tensor, grads: Dict[str, Tensor], kernel: Optional[str] = None) -> Tensor:
     """Adjoint of NNConv mean (edge_conv.py:25).  wtab [T, C, C]: the edge-type matrices the forward used; h: the layer's
     input; dz: gradient at the conv's output; g_scaled = dz / deg.  Fills the gradients of root, bias and the edge MLP
-    under `prefix`; returns the gradient at h."""
+    under `prefix`; returns the gradient at h.
+    kernel: "chain" = the type sums S' and the dense products, "eg" = tgnn_nnconv_bwd_eg (raises ValueError naming the limit where
+    its predicate fails; never falls back), None = what tgnn_backward_groups takes: eg iff set_nnconv_bwd_eg is on and the
+    predicate holds, else the chain."""
     g = tg.g
     n, T, c = g.n_nodes, g.n_types, int(h.shape[1])
     dev = h.device
+    if kernel not in (None, "chain", "eg"):
+        raise ValueError("nnconv_backward: kernel is None, 'chain' or 'eg'")
+    if kernel is None:
+        kernel = "eg" if set_nnconv_bwd_eg(-1) == 1 and _nnconv_bwd_eg_why_not(tg, c) is None else "chain"
+    elif kernel == "eg":
+        why = _nnconv_bwd_eg_why_not(tg, c)
+        if why is not None:
+            raise ValueError("nnconv_backward(kernel='eg'): " + why)
+    if kernel == "eg":
+        return _nnconv_backward_eg(conv, prefix, tg, wtab, h, dz, g_scaled, edge_attr, grads)
     # ONE gather pass serves both gradients: S'[j][t] = sum over the out-edges (j -> v) of type t of g[v]  (type sums over
     # the TRANSPOSED graph; root slot = g[j] deg[j] = dz[j]).
     #   input gradient:   dh[j]  = sum_t S'[j][t] W_t^T + dz[j] root^T              = S' . [W_t^T; root^T]   (dense)
@@ -348,6 +430,37 @@ def nnconv_backward(conv, prefix: str, tg: TrainGraph, wtab: Tensor, h: Tensor, 
     dwcat = torch.empty((T + 1) * c, c, dtype=torch.float32, device=dev)                          # [t][in][out]
     check(lib.tgnn_swap_leading(ptr(dw_in_major), c, T + 1, c, ptr(dwcat), c, _s(dwcat)))
     grads[prefix + ".nnConv.root"] = dwcat[T * c:]
+    _nnconv_backward_tail(conv, prefix, tg, wtab, dz, dwcat, edge_attr, grads)
+    return dh
+
+
+def _nnconv_backward_eg(conv, prefix, tg, wtab, h, dz, g_scaled, edge_attr, grads) -> Tensor:
+    """nnconv_backward on tgnn_nnconv_bwd_eg: dh and dwcat [T+1][C][C] (entry T: d root) from one library call."""
+    g, gt = tg.g, tg.groups_t
+    n, T, c = g.n_nodes, g.n_types, int(h.shape[1])
+    dev = h.device
+    for name, t in (("h", h), ("dz", dz), ("g_scaled", g_scaled)):
+        if not t.is_contiguous() or tuple(t.shape) != (n, c):
+            raise ValueError(f"nnconv_backward(kernel='eg'): `{name}` must be a packed [{n}, {c}] array")
+    root = conv.root if conv.root.is_contiguous() else conv.root.contiguous()
+    wt = wtab if wtab.is_contiguous() else wtab.contiguous()
+    dh = torch.empty(n, c, dtype=torch.float32, device=dev)
+    dwcat = torch.empty((T + 1) * c, c, dtype=torch.float32, device=dev)
+    nb = int(lib.tgnn_nnconv_bwd_eg_workspace_bytes(n, gt.groups_cap, T, c))
+    ws = _Scratch.get("nnconv_bwd_eg", nb, dev)
+    check(lib.tgnn_nnconv_bwd_eg(ptr(h), c, ptr(dz), ptr(g_scaled), ptr(gt.fwd.tile_grp_ptr), ptr(gt.fwd.grp), ptr(gt.bwd.tile_grp_ptr),
+                                 ptr(gt.bwd.grp), ptr(gt.type_major), gt.n_list, ptr(wt), ptr(root), n, T, c, gt.max_in_degree,
+                                 gt.max_out_degree, ptr(dh), ptr(dwcat), ptr(ws), nb, _s(h)))
+    grads[prefix + ".nnConv.root"] = dwcat[T * c:]
+    _nnconv_backward_tail(conv, prefix, tg, wtab, dz, dwcat, edge_attr, grads)
+    return dh
+
+
+def _nnconv_backward_tail(conv, prefix, tg, wtab, dz, dwcat, edge_attr, grads) -> None:
+    """d bias, and the edge MLP behind the T weight matrices: the same on both routes."""
+    g = tg.g
+    T, c = g.n_types, int(dz.shape[1])
+    dev = dz.device
     grads[prefix + ".nnConv.bias"] = colsum(dz)
     # the edge MLP behind the T weight matrices (edge_conv.py:17-18), on the T distinct attribute rows
     ew = conv._edge_mlp_params()
@@ -361,7 +474,6 @@ def nnconv_backward(conv, prefix: str, tg: TrainGraph, wtab: Tensor, h: Tensor, 
         for k in range(3):
             grads[names[k] + ".linear.weight"] = torch.zeros_like(ew[2 * k])
             grads[names[k] + ".linear.bias"] = torch.zeros_like(ew[2 * k + 1])
-    return dh
 
 
 def gin_backward(conv, prefix: str, tg: TrainGraph, u: Tensor, t3: Tensor, dz: Tensor, grads: Dict[str, Tensor]) -> Tensor:
@@ -464,8 +576,13 @@ def backward_library(net, sv, dprobs: Tensor) -> Dict[str, Tensor]:
     ws = _Scratch.get("bwd", nb, dev)
     gs = g.c_struct()
     dp = ops._f32c(dprobs, "grad of probs")
-    check(lib.tgnn_backward(C.byref(dims), table, gtable, ptr(sv.x), ptr(sv.ea), C.byref(gs), C.byref(tgd), C.byref(keep),
-                            ptr(sv.probs), ptr(dp), ptr(ws), nb, _lib.current_stream(dev)))
+    # the edge groups of both directions travel only under set_nnconv_bwd_eg(1) (built on first use, TrainGraph.ensure_groups_t)
+    grp = None
+    if set_nnconv_bwd_eg(-1) == 1 and _nnconv_bwd_eg_why_not(tg, net.network_width) is None:
+        grp = tg.groups_desc()
+    check(lib.tgnn_backward_groups(C.byref(dims), table, gtable, ptr(sv.x), ptr(sv.ea), C.byref(gs), C.byref(tgd),
+                                   C.byref(grp) if grp is not None else None, C.byref(keep), ptr(sv.probs), ptr(dp), ptr(ws), nb,
+                                   _lib.current_stream(dev)))
     return grads
 
 
