@@ -379,6 +379,33 @@ typedef struct tgnn_graph {
 
 size_t tgnn_forward_workspace_bytes(const tgnn_model_dims *dims, int64_t n_nodes, int32_t n_types);
 
+/* Where the pieces of the forward workspace lie that a test has to read: byte_offsets[TGNN_WS_*] = the piece's offset from the
+ * workspace's base, for a forward over n_nodes own rows whose gathered buffers carry n_rows >= n_nodes rows (single device:
+ * n_rows == n_nodes; sharded: + the halo rows).  Read-only, host only (no device is touched); n >= TGNN_WS_MAP_ENTRIES.  The
+ * offsets do not depend on n_types up to 16 (what tgnn_forward_begin relies on).
+ *   MID      float [depth + 1][n_rows][width]  the skip buffer, slot k = middle[k] (slot 0: the init MLP's output)
+ *   A1       float [n_rows][width]             the adjacency branch's pre-BatchNorm activations of the layer in flight
+ *   F1 F2 F3 float [n_nodes][256 / 128 / 64]   the final MLP's hidden activations, BEFORE their BatchNorm
+ *   BOUNDS   uint32 words, see below
+ *   BOUNDS64 uint32 words, width 64 only (else -1): [i] max |middle[i]|, [depth + i] max |root_i|, i < depth
+ *
+ * The words of BOUNDS (D = network_depth).  The fp16-pair kernels scale every operand by a power of two taken from a bound of
+ * its magnitude; each bound is a word here, the BIT PATTERN of a non-negative float, and every forward that runs fp16 pairs
+ * establishes it anew -- cleared first, then folded with atomicMax (exact, whatever the order) or stored:
+ *   [0, D]             max |middle[k]| over ALL rows a consumer gathers (own and halo rows), by the kernel that writes the slot
+ *   [D + 1, 2 D]       max |root_i| of layer i's NNConv
+ *   [2 D + 1]          max |W_0| of the final MLP's first Linear
+ *   [2 D + 2 l, + 1]   l = 1, 2: max |W_l| of the final MLP's layer l, then a bound of |BatchNorm(input of l)| from the
+ *                      BatchNorm's parameters alone: max_c (|gamma_c| sqrt(n) + |beta_c|) (Samuelson's inequality)
+ *   [2 D + 6]          the mid-size kernel's count of finished edge-weight blocks (not a bound)
+ *   [2 D + 8, + 1]     the same pair for layer 3, where the row count takes the resident dense kernel (else 0)
+ *   [2 D + 10, ...)    BatchNorm fold tickets of the collision branch and the final MLP (not bounds)
+ * A word no kernel of the path writes is 0 behind the forward where the head clears it: [0, 2 D + 7) on every fp16-pair path,
+ * [0, 2 D + 95) with the lean head (tgnn_set_lean_head bit 0). */
+enum { TGNN_WS_MID = 0, TGNN_WS_A1, TGNN_WS_F1, TGNN_WS_F2, TGNN_WS_F3, TGNN_WS_BOUNDS, TGNN_WS_BOUNDS64, TGNN_WS_MAP_ENTRIES };
+int tgnn_forward_workspace_map(const tgnn_model_dims *dims, int64_t n_nodes, int64_t n_rows, int32_t n_types, int64_t *byte_offsets,
+                               int32_t n);
+
 /* probs [N, output_dim].  BatchNorm runs with batch statistics and updates the running buffers
  * in `params` when update_running != 0 (train mode); with use_running_stats != 0 it normalises
  * with the running buffers instead (eval mode; never used by the reference's solver).

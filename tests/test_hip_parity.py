@@ -663,6 +663,31 @@ def test_sharded_hip_path_matches_unsharded(dev, world, general_schedule, bf16x3
             assert float((a[k + ".running_var"] - b[k + ".running_var"]).abs().max()) < 1e-5
 
 
+def run_thread_ranks(dev, runners, hub):
+    """One step() of every thread-simulated rank (dist.FusedShardForward over dist.ThreadSimCollectives), each on a thread of its own;
+    returns the ranks' probabilities, synchronised.  The runners keep their last workspace (runner.workspace)."""
+    import threading
+    world = len(runners)
+    parts, errors = [None] * world, []
+
+    def work(r):
+        try:
+            torch.cuda.set_device(dev)
+            parts[r] = runners[r].step()
+        except BaseException as exc:                     # a dead rank must not leave the others in the barrier
+            errors.append(exc)
+            hub.barrier.abort()
+
+    threads = [threading.Thread(target=work, args=(r,)) for r in range(world)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(timeout=120)
+    assert not errors, errors
+    torch.cuda.synchronize()
+    return parts
+
+
 @pytest.mark.parametrize("world,one_collective,split", [(1, True, False), (2, True, False), (4, True, False), (3, True, False),
                                                         (2, False, False), (4, False, False), (2, True, True), (4, True, True),
                                                         (3, True, True)])
@@ -671,7 +696,6 @@ def test_fused_sharded_forward_matches_unsharded(dev, world, one_collective, spl
     virtual ranks = P threads on this one GPU (ThreadSimCollectives) against the unsharded forward; both collective
     schemes: one all-to-all per layer carrying raw halo rows + BatchNorm sums (default) and all-reduce + all-to-all;
     running statistics come from the GLOBAL sums."""
-    import threading
     from tilingnn_amd import dist as tdist
     from tilingnn_amd.synth import make_super_graph
     sg = make_super_graph(6000, 60000, 75000, tile_count=2, n_edge_types=13, seed=8)
@@ -688,24 +712,7 @@ def test_fused_sharded_forward_matches_unsharded(dev, world, one_collective, spl
                    for r in range(world)]
         for rn in runners:       # split: one all-to-all per BRANCH and layer, the collision branch's chain on the side stream
             rn.two_streams = split
-        parts, errors = [None] * world, []
-
-        def work(r):
-            try:
-                torch.cuda.set_device(dev)
-                parts[r] = runners[r].step()
-            except BaseException as exc:                     # a dead rank must not leave the others in the barrier
-                errors.append(exc)
-                hub.barrier.abort()
-
-        threads = [threading.Thread(target=work, args=(r,)) for r in range(world)]
-        for t in threads:
-            t.start()
-        for t in threads:
-            t.join(timeout=120)
-        assert not errors, errors
-        torch.cuda.synchronize()
-        got = torch.cat(parts)
+        got = torch.cat(run_thread_ranks(dev, runners, hub))
         err = float((got - want).abs().max())
         print(f"one call, world {world}, one collective per layer {one_collective}, depth {depth}: "
               f"max |sharded - unsharded| = {err:.2e}")

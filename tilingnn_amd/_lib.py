@@ -143,6 +143,7 @@ def _load() -> C.CDLL:
         "tgnn_param_count": (i32, [C.POINTER(ModelDims)]),
         "tgnn_param_name": (C.c_int, [C.POINTER(ModelDims), i32, C.c_char_p, sz]),
         "tgnn_forward_workspace_bytes": (sz, [C.POINTER(ModelDims), i64, i32]),
+        "tgnn_forward_workspace_map": (C.c_int, [C.POINTER(ModelDims), i64, i64, i32, C.POINTER(C.c_int64), i32]),
         "tgnn_forward": (C.c_int, [C.POINTER(ModelDims), C.POINTER(C.c_void_p), p, p, C.POINTER(Graph), i32, i32,
                                    p, p, sz, p, p]),
         "tgnn_forward_begin": (C.c_int, [C.POINTER(ModelDims), C.POINTER(C.c_void_p), p, i64, i32, p, sz, p, p]),
@@ -309,7 +310,7 @@ EXPORTED_SYMBOLS = (
     "tgnn_gin64_fwd", "tgnn_set_gin64_mfma", "tgnn_gin32_fwd",
     "tgnn_ubench_row_gather", "tgnn_mid_entries_words", "tgnn_mid_entries_build", "tgnn_forward_path_counts", "tgnn_set_mid_layout_limit", "tgnn_get_mid_layout_limit", "tgnn_mid_layout_max_nodes",
     "tgnn_spin_error_poll", "tgnn_set_spin_budget_us", "tgnn_persist_fallback", "tgnn_spin_error_peek", "tgnn_gin_fwd", "tgnn_dense_act_fwd", "tgnn_dense_act_slots_fwd", "tgnn_dense_act_slots_f16_fwd", "tgnn_bn_finalize", "tgnn_bn_apply",
-    "tgnn_merge_fwd", "tgnn_param_count", "tgnn_param_name", "tgnn_forward_workspace_bytes", "tgnn_forward", "tgnn_forward_begin", "tgnn_forward_resume",
+    "tgnn_merge_fwd", "tgnn_param_count", "tgnn_param_name", "tgnn_forward_workspace_bytes", "tgnn_forward_workspace_map", "tgnn_forward", "tgnn_forward_begin", "tgnn_forward_resume",
     "tgnn_forward_profiled", "tgnn_forward_profiled_two_stream", "tgnn_forward_stamped", "tgnn_forward_many", "tgnn_forward_union", "tgnn_forward_union_plan", "tgnn_forward_union_counts", "tgnn_graph_prep_small_max_nodes", "tgnn_graph_prep_small_max_edges", "tgnn_graph_prep_small_tmp_ints",
     "tgnn_graph_prep_small", "tgnn_graph_prep_workspace_bytes", "tgnn_graph_prep", "tgnn_graph_prep_wait", "tgnn_graph_prep_small_many", "tgnn_graph_prep_small_many_wait", "tgnn_graph_prep_small_many_plan", "tgnn_graph_prep_small_many_counts", "tgnn_set_small_layout_limit", "tgnn_get_small_layout_limit", "tgnn_set_split_precision", "tgnn_set_gin_fused", "tgnn_set_gin_mlp_f16", "tgnn_set_mid_tail", "tgnn_set_nnconv_eg", "tgnn_set_dense_rows_mode", "tgnn_set_lean_head", "tgnn_set_prep_words_poll", "tgnn_forward_begin_weights", "tgnn_forward_bf16_begin", "tgnn_forward_bf16_drop", "tgnn_forward_small_prepass", "tgnn_rccl_available", "tgnn_rccl_unique_id_bytes", "tgnn_rccl_unique_id", "tgnn_rccl_comm_create", "tgnn_rccl_comm_destroy", "tgnn_rccl_counters", "tgnn_forward_train", "tgnn_backward_workspace_bytes", "tgnn_backward", "tgnn_forward_sharded_workspace_bytes", "tgnn_forward_sharded",
     "tgnn_rows_gather", "tgnn_rows_scatter", "tgnn_unsupervised_loss_workspace_bytes", "tgnn_unsupervised_loss", "tgnn_solution_score_sums",
@@ -328,6 +329,16 @@ EXPORTED_SYMBOLS = (
     "tgnn_nnconv_type_sum", "tgnn_csr_degree", "tgnn_unsupervised_loss_bwd",
     "tgnn_f32_to_bf16", "tgnn_nnconv64_image_elems", "tgnn_nnconv64_bf16_fwd", "tgnn_nnconv64_bf16_eg_fwd", "tgnn_gin64_bf16_fwd", "tgnn_collconv64_bf16_fwd", "tgnn_merge_bf16_fwd",
     "tgnn_dense_bf16_slots_fwd", "tgnn_forward_bf16_workspace_bytes", "tgnn_forward_bf16")
+
+
+WS_MAP_PIECES = ("mid", "a1", "f1", "f2", "f3", "bounds", "bounds64")     # TGNN_WS_* of include/tgnn.h, in order
+
+
+def forward_workspace_map(dims, n_nodes, n_rows=None, n_types=0):
+    """{piece: byte offset in the forward workspace} (tgnn_forward_workspace_map; host only).  bounds64 is -1 unless the width is 64."""
+    out = (C.c_int64 * len(WS_MAP_PIECES))()
+    check(lib.tgnn_forward_workspace_map(C.byref(dims), n_nodes, n_nodes if n_rows is None else n_rows, n_types, out, len(WS_MAP_PIECES)))
+    return {name: int(v) for name, v in zip(WS_MAP_PIECES, out)}
 
 
 def forward_path_counts():

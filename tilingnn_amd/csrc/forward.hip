@@ -92,6 +92,7 @@ struct Workspace {
     unsigned *small_ctr;
     void *dimg[4];                 // fp16-pair operand images of the final MLP's four Linears (dense_f16_image_build; [r6] the fourth, 64 -> 32)
     unsigned *bounds;            // [0, D]: max |middle[k]| as float bits; [D + 1, 2 D]: max |root_i|; [2 D + 1]: max |final W_0|
+                                 // (every word and the contract they keep: include/tgnn.h at tgnn_forward_workspace_map)
     float *stat1, *stat2[2], *stat_i[2], *stat_f[4];
     size_t bytes;
 };
@@ -251,6 +252,23 @@ extern "C" size_t tgnn_forward_sharded_workspace_bytes(const tgnn_model_dims *di
                                                        int32_t n_types) {
     if (!dims_ok(dims) || n_own < 0 || n_rows < n_own) return 0;
     return carve(*dims, n_own, n_rows, n_types, nullptr, 0).bytes;
+}
+
+// The carve itself on a null base: the pieces' addresses ARE their byte offsets, so the map cannot drift from the layout.  Host only.
+extern "C" int tgnn_forward_workspace_map(const tgnn_model_dims *dims, int64_t n_nodes, int64_t n_rows, int32_t n_types,
+                                          int64_t *byte_offsets, int32_t n) {
+    TGNN_CHECK_ARG(dims_ok(dims) && n_nodes >= 0 && n_rows >= n_nodes, "model dims / row counts");
+    TGNN_CHECK_ARG(byte_offsets && n >= TGNN_WS_MAP_ENTRIES, "byte_offsets holds fewer than TGNN_WS_MAP_ENTRIES entries");
+    const Workspace w = carve(*dims, n_nodes, n_rows, n_types, nullptr, 0);
+    const auto off = [](const void *p) { return (int64_t) reinterpret_cast<uintptr_t>(p); };
+    byte_offsets[TGNN_WS_MID] = off(w.mid);
+    byte_offsets[TGNN_WS_A1] = off(w.a1);
+    byte_offsets[TGNN_WS_F1] = off(w.f1);
+    byte_offsets[TGNN_WS_F2] = off(w.f2);
+    byte_offsets[TGNN_WS_F3] = off(w.f3);
+    byte_offsets[TGNN_WS_BOUNDS] = off(w.bounds);
+    byte_offsets[TGNN_WS_BOUNDS64] = dims->network_width == 64 ? off(w.bounds64) : -1;
+    return TGNN_OK;
 }
 
 #define TGNN_TRY(expr)               \

@@ -635,6 +635,7 @@ __global__ __launch_bounds__(256) void dense_bounds_kernel(DenseBoundJobs jobs, 
     if (blockIdx.y != 0 || !j.gamma) return;                  // (uniform)
     float a = 0.f;
     for (int c = threadIdx.x; c < j.f; c += 256) a = fmaxf(a, fmaf(fabsf(j.gamma[c]), sqrt_n, fabsf(j.beta[c])));
+    __syncthreads();                                          // (wave 0 may still be reading the first call's wave_max: see absmax_flush)
     absmax_flush(a, j.a_max);
 }
 void launch_dense_bounds(int n_jobs, const float *const *w, const int64_t *w_n, const float *const *gamma, const float *const *beta,

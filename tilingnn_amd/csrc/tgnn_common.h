@@ -214,6 +214,9 @@ __device__ __host__ __forceinline__ float pow2_scale_for(unsigned bound_bits, in
 // Same-address atomics cost ~5 ns each at the L2 and the waves of an element-wise kernel all finish together: one atomic per
 // wavefront made a 256-block merge 25 us slower, so the block folds its waves through LDS first and thread 0 sends one
 // (fire and forget: reading the word first to skip the atomic put a second L2 round trip on the tail of every block).
+// ONE call per block and path: the function ends without a barrier (the element-wise kernels end there), so a second call could
+// store into wave_max while wave 0 still reads the first call's values -- a block that folds twice (dense_bounds_kernel) puts a
+// __syncthreads() between the calls.
 __device__ __forceinline__ void absmax_flush(float m, unsigned *out) {
     if (!out) return;                                         // (uniform)
     __shared__ float wave_max[16];

@@ -594,6 +594,7 @@ class FusedShardForward:
         table, _ = net._param_table()
         ws_bytes = _lib.lib.tgnn_forward_sharded_workspace_bytes(C.byref(dims), sh.n_own, sh.n_rows, graph.n_types)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.dev)
+        self.workspace, self.n_types = ws, graph.n_types      # (the last step's: tests read the skip buffer and the bounds out of it)
         probs = torch.empty(sh.n_own, net.output_dim, dtype=torch.float32, device=self.dev)
         desc = _lib.ShardDesc(sh.n_own, sh.n_rows, sh.n_total, inp["send_idx"].data_ptr(), self.n_send,
                               self.sum_buf.data_ptr(), self.send_buf.data_ptr(), self.recv_buf.data_ptr(),
