@@ -1246,6 +1246,30 @@ int tgnn_union_area(const double *ring_xy, const int32_t *ring_ptr, int64_t n_ti
                     const int32_t *col_idx, const int32_t *alive, int64_t n_masks, double tol, double *area_out,
                     int32_t *err_flag, void *ws, size_t ws_bytes, tgnn_stream_t stream);
 
+/* ---- topology of the union of the alive tiles of K masks (csrc/union_topology.hip): what the reference's
+ * BrickLayout.detect_holes (tiling/brick_layout.py:229-240) asks of a solved layout.  One call for all K masks, no host
+ * synchronisation, integer sums only: the same bits on every run.  For masks whose alive tiles do NOT overlap; a mask in which
+ * two alive tiles collide is reported, not answered.
+ *   ring_xy, ring_ptr, col_ptr, col_idx, alive, tol: as for tgnn_union_area (rings NOT closed, COUNTER-CLOCKWISE).
+ *   touch_ptr [n_tiles + 1], touch_idx: the contact relation as CSR, row i = the tiles j != i with a vertex of one within tol of
+ *   the ring of the other, symmetric (tilingnn_amd.tiling.region.contact_geometry; touch_idx may be NULL when touch_ptr is all
+ *   0).  An entry of col_idx or touch_idx outside [0, n_tiles) is skipped and reported.
+ *   (dir_x, dir_y) = (cos theta, sin theta), a unit vector: the direction of the sweep's level lines.  No tile side may lie
+ *   along it: every side direction at least 1e-3 rad away (mod pi), distinct side directions at least 1e-3 rad apart
+ *   (tilingnn_amd.tiling.region.sweep_direction picks and checks).
+ *   out [K][3] int32 = {components, holes, status}: the connected components of the closed union of the alive tiles (tiles that
+ *   share a single point are connected), the bounded components of its complement (a gap sealed by a corner contact counts), and
+ *   status 0; or {-1, -1, 1} when two alive tiles of the mask collide.  {0, 0, 0} for an empty mask.
+ *   *err_flag (device, required, zeroed by the caller) gets TGNN_TOPO_ERR_* bits OR-ed in: then out is not to be used.
+ *   ws: tgnn_union_topology_workspace_bytes(K, n_tiles) bytes, 4-byte aligned; its contents on entry do not matter. */
+#define TGNN_TOPO_ERR_INDEX 1  /* a col_idx or touch_idx entry outside [0, n_tiles) */
+#define TGNN_TOPO_ERR_WEDGES 2 /* more than 16 tiles meet in one point */
+size_t tgnn_union_topology_workspace_bytes(int64_t n_masks, int64_t n_tiles);
+int tgnn_union_topology(const double *ring_xy, const int32_t *ring_ptr, int64_t n_tiles, const int32_t *col_ptr,
+                        const int32_t *col_idx, const int32_t *touch_ptr, const int32_t *touch_idx, const int32_t *alive,
+                        int64_t n_masks, double tol, double dir_x, double dir_y, int32_t *out /* [K][3] */, int32_t *err_flag,
+                        void *ws, size_t ws_bytes, tgnn_stream_t stream);
+
 /* ---- the disjoint union of B layouts of a packed set (csrc/batch_union.hip): what PyG's DataLoader hands the reference's training
  * step for batch_size B (Batch.from_data_list: arrays concatenated, edge ends shifted by the member's node offset).  ONE launch,
  * no host synchronisation, no atomics: the same bits on every call.

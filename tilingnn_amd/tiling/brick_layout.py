@@ -1,11 +1,13 @@
 """`BrickLayout` -- the data side (/root/reference/tiling/brick_layout.py:22-56, :242-286).
 
 A layout is five numpy arrays + the index maps to the complete graph.  The reference's class also draws, unions and
-measures polygons through shapely (`show_*`, `get_super_contour_poly`, `detect_holes`, ...): geometry is outside this
-package and those methods are not mirrored -- hand the arrays of this object to the reference's class when they are
-needed (same constructor arguments).  One number of that geometry is here, because every score divides by it: the AREA of the
-union of the layout's tiles, `compute_super_contour_area` (on the GPU, csrc/union_area.hip) -> `super_contour_area`; there is
-deliberately no method called `get_super_contour_poly`.  What `ML_Solver.predict` and the greedy loop read is here:
+measures polygons through shapely (`show_*`, `get_super_contour_poly`, ...): geometry is outside this package and those
+methods are not mirrored -- hand the arrays of this object to the reference's class when they are needed (same constructor
+arguments).  Two facts of that geometry are here.  The AREA of the union of the layout's tiles, because every score divides by
+it: `compute_super_contour_area` (on the GPU, csrc/union_area.hip) -> `super_contour_area`; there is deliberately no method
+called `get_super_contour_poly`.  And whether a solution leaves an enclosed gap, the validity bit the reference asks every
+solved layout for: `detect_holes` (:229-240), with `count_holes` and the many-layout `detect_holes_many` (on the GPU,
+csrc/union_topology.hip).  What `ML_Solver.predict` and the greedy loop read is here:
 `get_data_as_torch_tensor` (:242-246) and `compute_sub_layout` (:248-286, vectorised: one membership mask instead of
 four comprehensions over every edge).
 """
@@ -69,6 +71,22 @@ class BrickLayout:
         self.super_contour_area = float(on_device.union_areas(torch.from_numpy(alive).to(on_device.device)).item())
         return self.super_contour_area
 
+    def selected_tiles(self):
+        """Complete-graph ids (int64) of the tiles with `predict == 1`, through `inverse_index`."""
+        nodes = np.flatnonzero(np.asarray(self.predict) == 1)
+        return np.fromiter((self.inverse_index[int(i)] for i in nodes), dtype=np.int64, count=nodes.shape[0])
+
+    def count_holes(self, device=None):
+        """(components, holes) of the union of the selected tiles (`predict == 1`): its connected components, tiles that touch
+        in a single corner being connected as under the reference's 1e-7 buffer, and the enclosed gaps it leaves.  Computed on
+        the GPU (csrc/union_topology.hip); ValueError when two selected tiles collide (a solution never does).  There is no host
+        fallback."""
+        return detect_holes_many([self], device)[0]
+
+    def detect_holes(self, device=None):
+        """True when the selected tiles enclose a gap -- the reference's `detect_holes` (:229-240)."""
+        return self.count_holes(device)[1] > 0
+
     def compute_sub_layout(self, predict):
         """:248-286.  `predict`: a SelectionSolution-like object with dicts `labelled_nodes` / `unlabelled_nodes`."""
         assert len(self.node_feature) == len(predict.labelled_nodes) + len(predict.unlabelled_nodes)
@@ -103,3 +121,33 @@ class BrickLayout:
                      "align_edge_features"):
             assert np.array_equal(getattr(a, name), getattr(b, name)), name
         assert dict(a.re_index) == dict(b.re_index)
+
+
+def detect_holes_many(layouts, device=None):
+    """[(components, holes)] of K solved layouts of ONE complete graph -- `BrickLayout.count_holes` of each -- with one kernel
+    call and one read-back for all of them (csrc/union_topology.hip).  ValueError when a layout's selected tiles collide;
+    RuntimeError without a GPU: there is no host fallback."""
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("detect_holes runs on the GPU (csrc/union_topology.hip) and no GPU is available; "
+                           "there is no host fallback")
+    layouts = list(layouts)
+    if not layouts:
+        return []
+    graph = layouts[0].complete_graph
+    if any(l.complete_graph is not graph for l in layouts):
+        raise ValueError("detect_holes_many takes layouts of one complete graph")
+    from ..util.data_util import graph_on_device
+    on_device = graph_on_device(graph, device)
+    alive = np.zeros((len(layouts), on_device.n_tiles), dtype=np.int32)
+    for k, layout in enumerate(layouts):
+        tiles = layout.selected_tiles()
+        if tiles.size and (tiles.min() < 0 or tiles.max() >= on_device.n_tiles):
+            raise ValueError(f"layout {k}: inverse_index names a tile outside [0, {on_device.n_tiles})")
+        alive[k, tiles] = 1
+    out = on_device.union_topology(torch.from_numpy(alive).to(on_device.device)).cpu().numpy()
+    bad = np.flatnonzero(out[:, 2] != 0)
+    if bad.size:
+        raise ValueError(f"layout {int(bad[0])}: two selected tiles collide (detect_holes is defined for a solution, whose "
+                         f"tiles do not overlap); {bad.size} of {len(layouts)} layouts do")
+    return [(int(c), int(h)) for c, h, _ in out]

@@ -297,6 +297,107 @@ def vertex_side_distances(ring_xy, ring_ptr, pairs):
     return np.concatenate(out)
 
 
+def _pair_gaps(ring_xy, ring_ptr, u, v):
+    """Per pair (u[k], v[k]): the smallest distance from a vertex of tile v[k] to a side of tile u[k]."""
+    out = np.full(u.shape[0], np.inf)
+    if u.shape[0] == 0:
+        return out
+    size = np.diff(ring_ptr).astype(np.int64)
+    shape_key = size[u] * (int(size.max()) + 1) + size[v]
+    for key in np.unique(shape_key):
+        sel = np.flatnonzero(shape_key == key)
+        uu, vv = u[sel], v[sel]
+        nu, nv = int(size[uu[0]]), int(size[vv[0]])
+        for s in range(0, sel.shape[0], 1 << 16):               # bounded temporaries whatever the graph's size
+            us, vs = uu[s:s + (1 << 16)], vv[s:s + (1 << 16)]
+            a = ring_xy[ring_ptr[us][:, None] + np.arange(nu)[None, :]]
+            b = ring_xy[ring_ptr[us][:, None] + (np.arange(nu)[None, :] + 1) % nu]
+            p = ring_xy[ring_ptr[vs][:, None] + np.arange(nv)[None, :]]
+            out[sel[s:s + (1 << 16)]] = _point_segment_distances(p, a, b).reshape(us.shape[0], -1).min(axis=1)
+    return out
+
+
+def contact_geometry(ring_xy, ring_ptr, tol=UNION_TOL):
+    """The contact relation of tgnn_union_topology (csrc/union_topology.hip) as a CSR: touch_ptr [n + 1] i32, touch_idx i32, row
+    i = the tiles j != i with a vertex of one within `tol` of the closed ring of the other; symmetric, rows sorted.  For tiles
+    that do not overlap this is every pair that shares a point: an isolated shared point is a vertex of one of the two, and a
+    shared stretch ends in vertices.  It is NOT the union of the graph's two edge lists (on ring 9 most of its pairs, the
+    corner-to-corner contacts, are in neither).  `ring_xy`, `ring_ptr`: what `union_geometry` returns.  Pairs whose boxes,
+    grown by tol, do not meet are never measured."""
+    ring_xy = np.asarray(ring_xy, dtype=np.float64).reshape(-1, 2)
+    ring_ptr = np.asarray(ring_ptr, dtype=np.int64)
+    n = ring_ptr.shape[0] - 1
+    if n <= 0:
+        return np.zeros(max(n, 0) + 1, dtype=np.int32), np.zeros(0, dtype=np.int32)
+    if np.any(np.diff(ring_ptr) < 3):
+        raise ValueError("a tile ring with fewer than three vertices")
+    starts = ring_ptr[:-1]
+    lo = np.stack([np.minimum.reduceat(ring_xy[:, 0], starts), np.minimum.reduceat(ring_xy[:, 1], starts)], axis=1) - tol
+    hi = np.stack([np.maximum.reduceat(ring_xy[:, 0], starts), np.maximum.reduceat(ring_xy[:, 1], starts)], axis=1) + tol
+    us, vs = [], []
+    for s in range(0, n, 1024):                                     # box prefilter, a block of rows at a time
+        e = min(s + 1024, n)
+        near = ((lo[s:e, None, 0] <= hi[None, :, 0]) & (hi[s:e, None, 0] >= lo[None, :, 0]) &
+                (lo[s:e, None, 1] <= hi[None, :, 1]) & (hi[s:e, None, 1] >= lo[None, :, 1]))
+        i, j = np.nonzero(near)
+        i = i + s
+        keep = i < j
+        us.append(i[keep])
+        vs.append(j[keep])
+    u, v = np.concatenate(us).astype(np.int64), np.concatenate(vs).astype(np.int64)
+    gap = np.minimum(_pair_gaps(ring_xy, ring_ptr, u, v), _pair_gaps(ring_xy, ring_ptr, v, u))
+    u, v = u[gap <= tol], v[gap <= tol]
+    keys = np.unique(np.concatenate([u * n + v, v * n + u]))
+    if keys.size >= 2 ** 31:
+        raise ValueError("too many contact pairs for one call")
+    touch_ptr = np.searchsorted(keys // n, np.arange(n + 1))
+    return touch_ptr.astype(np.int32), (keys % n).astype(np.int32)
+
+
+SWEEP_CANDIDATES = (0.1234, 0.5678, 0.9876, 1.4142, 1.7321, 2.2361, 2.7183)     # radians; the first that qualifies is used
+SWEEP_ANGLE_TOL = 1e-5    # side directions closer than this are one direction (the kernel merges arcs that meet within it)
+SWEEP_MIN_GAP = 1e-3      # every side direction keeps this distance (mod pi) from the level lines, and 100 tolerances from each other
+
+
+def side_directions(ring_xy, ring_ptr):
+    """The distinct directions (radians in [0, pi), ascending) of the sides of the rings, sides within SWEEP_ANGLE_TOL of each
+    other counted once.  Raises ValueError when two distinct directions are closer than 100 x SWEEP_ANGLE_TOL: the kernel's
+    angular tolerance could then not tell a shared side from a thin gap."""
+    ring_xy = np.asarray(ring_xy, dtype=np.float64).reshape(-1, 2)
+    ring_ptr = np.asarray(ring_ptr, dtype=np.int64)
+    if ring_xy.shape[0] == 0:
+        return np.zeros(0)
+    nxt = np.arange(ring_xy.shape[0]) + 1
+    nxt[ring_ptr[1:] - 1] = ring_ptr[:-1]                           # the last vertex of a ring goes back to its first
+    d = ring_xy[nxt] - ring_xy
+    d = d[(d[:, 0] != 0.0) | (d[:, 1] != 0.0)]
+    ang = np.sort(np.mod(np.arctan2(d[:, 1], d[:, 0]), math.pi))
+    if ang.size == 0:
+        return ang
+    first = np.concatenate([[True], np.diff(ang) > SWEEP_ANGLE_TOL])
+    dirs = ang[first]
+    if dirs.size > 1 and dirs[0] + math.pi - ang[-1] <= SWEEP_ANGLE_TOL:        # the group that wraps around pi
+        dirs = dirs[1:]
+    if dirs.size > 1:
+        gaps = np.diff(np.concatenate([dirs, [dirs[0] + math.pi]]))
+        if gaps.min() < 100.0 * SWEEP_ANGLE_TOL:
+            raise ValueError(f"two side directions of the graph are {float(gaps.min()):.3g} rad apart, less than "
+                             f"{100.0 * SWEEP_ANGLE_TOL:g}: the union topology's angular tolerance cannot tell them apart safely")
+    return dirs
+
+
+def sweep_direction(ring_xy, ring_ptr, candidates=SWEEP_CANDIDATES):
+    """The angle theta of the level lines tgnn_union_topology sweeps with: the first of `candidates` that every side direction of
+    the rings keeps at least SWEEP_MIN_GAP rad away from (mod pi), so that no side lies along a level line.  ValueError when
+    none qualifies."""
+    dirs = side_directions(ring_xy, ring_ptr)
+    for theta in candidates:
+        off = np.mod(dirs - theta, math.pi)
+        if dirs.size == 0 or float(np.minimum(off, math.pi - off).min()) >= SWEEP_MIN_GAP:
+            return float(theta)
+    raise ValueError(f"every candidate sweep direction {tuple(candidates)} lies within {SWEEP_MIN_GAP:g} rad of a side of the graph")
+
+
 def check_tolerance_gap(ring_xy, ring_ptr, col_ptr, col_idx, tol=UNION_TOL):
     """tgnn_union_area snaps what lies within `tol` of a side onto it, which is only sound when nothing real is that small:
     raises ValueError when a vertex of a tile lies between tol and 100 tol from a side of a tile it collides with."""

@@ -17,6 +17,7 @@ hands back for an empty edge list) as the reference's module; what changed is ho
 """
 from __future__ import annotations
 
+import math
 import os
 import pickle
 from collections import defaultdict
@@ -183,6 +184,7 @@ class CompleteGraphOnDevice:
         self._graph = graph
         self._geometry = None
         self._union = None
+        self._topology = None
 
     def layout(self, tiles_super_set):
         """DeviceLayout of the given tiles (ASCENDING complete-graph ids: the order get_all_placement_in_polygon,
@@ -293,6 +295,54 @@ class CompleteGraphOnDevice:
                 raise _lib.TgnnError(f"tgnn_union_area: device error word {code} (1: collision index out of range, 2: a tile "
                                      "side is covered in more separate stretches than the kernel's interval list holds)")
         return area
+
+    # -------------------------------------------------------------------------- the topology of a union of tiles
+    def _topology_geometry(self):
+        """The contact relation as CSR and the sweep direction of tgnn_union_topology (region.contact_geometry,
+        region.sweep_direction), made from the graph's rings and uploaded on first use."""
+        if self._topology is None:
+            import torch
+            from ..tiling.region import contact_geometry, sweep_direction, union_geometry
+            g = self._graph
+            ring_xy, ring_ptr, _, _ = union_geometry([t.tile_poly.exterior for t in g.tiles], g.arrays.colli_edges, self.n_tiles)
+            theta = sweep_direction(ring_xy, ring_ptr)
+            touch = contact_geometry(ring_xy, ring_ptr)
+            self._topology = tuple(torch.from_numpy(a if a.size else np.zeros(1, dtype=a.dtype)).to(self.device)
+                                   for a in touch) + (math.cos(theta), math.sin(theta))
+        return self._topology
+
+    def union_topology(self, alive):
+        """[K, 3] int32 on the device: {components, holes, status} of the union of the tiles with alive[k, i] != 0 (`alive`
+        [K, n_tiles] or [n_tiles], any integer or bool tensor on this device) -- the connected components of the closed union
+        (tiles sharing a single point are connected) and the bounded components of its complement, what the reference's
+        `detect_holes` looks for.  For selections that do not overlap: a mask with two colliding alive tiles gets
+        {-1, -1, 1}.  csrc/union_topology.hip; one device-to-host copy of the error word."""
+        import torch
+        from .. import _lib
+        from .._lib import check, lib, ptr
+        from ..tiling.region import UNION_TOL
+        alive = torch.as_tensor(alive, device=self.device)
+        if alive.dim() == 1:
+            alive = alive[None, :]
+        if alive.dim() != 2 or alive.shape[1] != self.n_tiles:
+            raise ValueError(f"alive must be [K, {self.n_tiles}], got {tuple(alive.shape)}")
+        alive = (alive != 0).to(torch.int32).contiguous() if alive.dtype != torch.int32 else alive.contiguous()
+        k = int(alive.shape[0])
+        out = torch.empty(k, 3, dtype=torch.int32, device=self.device)
+        if k:
+            ring_xy, ring_ptr, col_ptr, col_idx = self._union_geometry()
+            touch_ptr, touch_idx, dir_x, dir_y = self._topology_geometry()
+            err = torch.zeros(1, dtype=torch.int32, device=self.device)
+            ws_bytes = int(lib.tgnn_union_topology_workspace_bytes(k, self.n_tiles))
+            ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=self.device)
+            check(lib.tgnn_union_topology(ptr(ring_xy), ptr(ring_ptr), self.n_tiles, ptr(col_ptr), ptr(col_idx), ptr(touch_ptr),
+                                          ptr(touch_idx), ptr(alive), k, UNION_TOL, dir_x, dir_y, ptr(out), ptr(err), ptr(ws),
+                                          ws_bytes, _lib.current_stream(self.device)))
+            code = int(err.item())
+            if code:
+                raise _lib.TgnnError(f"tgnn_union_topology: device error word {code} (1: collision or contact index out of "
+                                     "range, 2: more tiles meet in one point than the kernel's wedge list holds)")
+        return out
 
     def layouts_in_regions(self, regions, with_area=False):
         """One DeviceLayout per region: the tiles inside it cut out of the complete graph (what `layout` gives for that
