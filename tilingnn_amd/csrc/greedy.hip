@@ -52,7 +52,9 @@ __global__ void greedy_beaten_kernel(const int64_t *__restrict__ col, int64_t ec
         if (u == v) continue;                                     // (GINConv drops self loops; so does the collision test)
         const double pu = p[u], pv = p[v];
         // the later of the two in the visiting order is beaten -- marked from EITHER direction of the pair, so that a collision
-        // stored one way only (the reference stores both, tile_graph.py:206-207) still keeps the two apart
+        // stored one way only still keeps the two apart WITHIN THIS ROUND.  Labelling follows the stored direction only
+        // (greedy_label_kernel), so the final selection is collision free only when both directions are stored, as the
+        // reference stores them (tile_graph.py:206-207)
         if (pv > pu || (pv == pu && v < u)) flags[u] = 1;         // (every writer stores the same word)
         else flags[v] = 1;
     }
