@@ -1289,6 +1289,32 @@ int tgnn_batch_union(const float *x, const int64_t *adj, const float *attr, cons
                      const int64_t *table, int32_t batch, float *x_out, float *attr_out, int64_t *adj_out, int64_t *col_out,
                      tgnn_stream_t stream);
 
+/* ---- fused Adam step (csrc/adam.hip, csrc/adam_plan.h): torch.optim.Adam's non-capturable single-tensor update of every
+ * parameter tensor of a group in ONE launch, fp32, no atomics, no workspace, no host synchronisation.
+ *   g = grad (+ weight_decay p when weight_decay != 0);  m' = beta1 m + (1 - beta1) g;  v' = beta2 v + (1 - beta2) g g;
+ *   p' = p - step_size m' / (sqrt(v') rsqrt_bc2 + eps),   step_size = lr / (1 - beta1^t),  rsqrt_bc2 = 1 / sqrt(1 - beta2^t)
+ *   (the caller computes both in double; they are rounded to fp32 once).
+ * The table: n_segments segments of 32 bytes {float *param; int64 grad_off (BYTES from grad_base, a multiple of 4, any sign);
+ * int64 moment_off (FLOATS into exp_avg / exp_avg_sq, a multiple of 64); int64 numel}, followed by n_chunks chunks of 16 bytes
+ * {int64 start; int32 segment; int32 0}: chunk = elements [start, start + tgnn_adam_chunk_elems()) of its segment, cut off at the
+ * segment's end; start is a multiple of the chunk size.  tgnn_adam_table_build writes the image into HOST memory (8-byte
+ * aligned, tgnn_adam_table_bytes(n_segments, tgnn_adam_chunk_count(numel, n_segments)) bytes) from one array entry per segment and
+ * checks it: a null parameter with elements, a negative count, a moment slice that is misaligned or ends outside
+ * [0, moment_floats) is TGNN_ERR_INVALID_ARG.  The caller copies the image to the device once and reuses it for as long as the
+ * parameters stay where they are and the gradients keep their distances from each other: only grad_base changes from step to step.
+ * tgnn_adam_step takes the host image AND its device copy (the same bytes): it checks the host image again -- a chunk that names no
+ * segment or starts outside its own is TGNN_ERR_INVALID_ARG before anything is queued -- and launches one block per chunk on `stream`.
+ * exp_avg / exp_avg_sq: device, moment_floats floats each, 256-byte aligned, distinct.  n_chunks == 0: nothing is queued. */
+int64_t tgnn_adam_chunk_elems(void);
+int64_t tgnn_adam_chunk_count(const int64_t *numel, int32_t n_segments); /* -1: negative count / too many chunks */
+size_t tgnn_adam_table_bytes(int32_t n_segments, int64_t n_chunks);
+int tgnn_adam_table_build(const void *const *params, const int64_t *grad_off_bytes, const int64_t *moment_off,
+                          const int64_t *numel, int32_t n_segments, int64_t moment_floats, void *table_host,
+                          size_t table_bytes, int64_t *n_chunks_out);
+int tgnn_adam_step(const void *table_host, const void *table_dev, int32_t n_segments, int64_t n_chunks, const void *grad_base,
+                   float *exp_avg, float *exp_avg_sq, int64_t moment_floats, double step_size, double rsqrt_bc2, double beta1,
+                   double beta2, double eps, double weight_decay, tgnn_stream_t stream);
+
 int tgnn_rows_gather(const float *src, int64_t ld_src, const int32_t *idx, int64_t n_idx, int32_t c,
                      float *out, int64_t ld_out, tgnn_stream_t stream);
 int tgnn_rows_scatter(const float *in, const int32_t *idx, int64_t n_idx, int32_t c, float *dst,

@@ -6,6 +6,7 @@ Public surface = the reference's own for this path:
     tilingnn_amd.get_network_prediction          graph_networks/network_utils.py
     tilingnn_amd.solver.ml_solver.ML_Solver      predict / get_predict_probs / load_saved_network
 plus `tilingnn_amd.ops` (torch-tensor front end of the C ABI in include/tgnn.h),
+`tilingnn_amd.optim.Adam` (torch.optim.Adam's step as one kernel launch; also `tilingnn_amd.Adam`),
 `tilingnn_amd.weights` (state-dict layout + seeded recipe) and `tilingnn_amd.synth`
 (seeded synthetic super-graphs).  Importing the GPU-facing parts requires the built
 libtgnn.so; `weights` and `synth` are pure numpy/torch and import anywhere.
@@ -14,7 +15,9 @@ __version__ = "0.1.0"
 
 _GPU_ATTRS = {"TilinGNN": ("graph_networks.networks.TilinGNN", "TilinGNN"),
               "get_network_prediction": ("graph_networks.network_utils", "get_network_prediction"),
-              "ops": ("ops", None)}
+              "ops": ("ops", None),
+              "optim": ("optim", None),
+              "Adam": ("optim", "Adam")}
 
 
 def __getattr__(name):          # lazy: `import tilingnn_amd.weights` must not need the shared library

@@ -277,6 +277,11 @@ def _load() -> C.CDLL:
         "tgnn_forward_bf16": (C.c_int, [C.POINTER(ModelDims), C.POINTER(C.c_void_p), p, p, C.POINTER(Graph), i32, p, p, sz, p, p]),
         "tgnn_forward_bf16_begin": (C.c_int, [C.POINTER(ModelDims), C.POINTER(C.c_void_p), p, i64, i32, p, sz, p]),
         "tgnn_forward_bf16_drop": (C.c_int, [i32]),
+        "tgnn_adam_chunk_elems": (i64, []),
+        "tgnn_adam_chunk_count": (i64, [p, i32]),
+        "tgnn_adam_table_bytes": (sz, [i32, i64]),
+        "tgnn_adam_table_build": (C.c_int, [p, p, p, p, i32, i64, p, sz, C.POINTER(C.c_int64)]),
+        "tgnn_adam_step": (C.c_int, [p, p, i32, i64, p, p, p, i64] + [C.c_double] * 6 + [p]),
         "tgnn_rows_gather": (C.c_int, [p, i64, p, i64, i32, p, i64, p]),
         "tgnn_rows_scatter": (C.c_int, [p, p, i64, i32, p, i64, p]),
     }
@@ -331,7 +336,8 @@ EXPORTED_SYMBOLS = (
     "tgnn_nnconv_bwd_eg_dw_blocks", "tgnn_nnconv_bwd_eg_build", "tgnn_nnconv_bwd_eg", "tgnn_set_nnconv_bwd_eg",
     "tgnn_nnconv_type_sum", "tgnn_csr_degree", "tgnn_unsupervised_loss_bwd",
     "tgnn_f32_to_bf16", "tgnn_nnconv64_image_elems", "tgnn_nnconv64_bf16_fwd", "tgnn_nnconv64_bf16_eg_fwd", "tgnn_gin64_bf16_fwd", "tgnn_collconv64_bf16_fwd", "tgnn_merge_bf16_fwd",
-    "tgnn_dense_bf16_slots_fwd", "tgnn_forward_bf16_workspace_bytes", "tgnn_forward_bf16")
+    "tgnn_dense_bf16_slots_fwd", "tgnn_forward_bf16_workspace_bytes", "tgnn_forward_bf16",
+    "tgnn_adam_chunk_elems", "tgnn_adam_chunk_count", "tgnn_adam_table_bytes", "tgnn_adam_table_build", "tgnn_adam_step")
 
 
 WS_MAP_PIECES = ("mid", "a1", "f1", "f2", "f3", "bounds", "bounds64")     # TGNN_WS_* of include/tgnn.h, in order
