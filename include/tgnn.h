@@ -1270,6 +1270,43 @@ int tgnn_union_topology(const double *ring_xy, const int32_t *ring_ptr, int64_t 
                         int64_t n_masks, double tol, double dir_x, double dir_y, int32_t *out /* [K][3] */, int32_t *err_flag,
                         void *ws, size_t ws_bytes, tgnn_stream_t stream);
 
+/* ---- the outline of the union of the alive tiles of K masks (csrc/union_contour.hip): what the reference's
+ * BrickLayout.get_selected_tiles_union_polygon (tiling/brick_layout.py:223-227) returns for a solved layout.  One call for all K
+ * masks, no host synchronisation, no floating-point atomics: the same bits in every output on every run.  For masks whose alive
+ * tiles do NOT overlap; a mask in which two alive tiles collide is reported, not answered.
+ *   ring_xy, ring_ptr, col_ptr, col_idx, touch_ptr, touch_idx, alive, tol: as for tgnn_union_topology.
+ *   The boundary of the closed union is cut into pieces at every vertex of an alive tile; a piece continues with the first piece
+ *   that leaves its end point counter-clockwise from its own reversed direction, so tiles meeting in a single corner are joined
+ *   and a ring may touch itself but never crosses.  One counter-clockwise ring (area > 0) per component, one clockwise ring
+ *   (area < 0) per hole.  A mask's rings come in the order of their lowest piece (tile, side, position along the side); a ring
+ *   lists the start points of its pieces from that piece on, without the points it runs straight through (within 1e-5 rad).
+ *   Every listed point is a vertex of an alive tile: the lowest-numbered one with a vertex within tol, its lowest such vertex.
+ *   A mask lists at most 2 x the vertex count of its alive tiles.
+ *   cap_rings, cap_points: the capacity of ring_out / ring_area and of pts_xy / pts_src, over the whole call.
+ *   mask_out [K][4] int32 = {rings, first ring, points, status}; status 1 when two alive tiles of the mask collide (0 rings, 0
+ *   points), else 0; {0, ., 0, 0} for an empty mask.
+ *   ring_out [cap_rings][4] int32 = {first point (index into pts_xy / pts_src), points, component (the lowest alive tile of the
+ *   ring's component), +1 exterior / -1 hole}; ring_area [cap_rings] fp64, signed (shoelace about the ring's first point, in
+ *   listed order).  pts_xy [cap_points][2] fp64 = ring_xy[pts_src] bit for bit; pts_src [cap_points] int32 indexes ring_xy.
+ *   total_out [2] int64 = the rings and points the call needs.
+ *   *err_flag (device, required, zeroed by the caller) gets TGNN_CONTOUR_ERR_* bits OR-ed in.  On CAPACITY alone nothing is
+ *   written past either capacity and mask_out's counts and total_out are valid: a second call can be sized from them.  With any
+ *   other bit the outputs are not to be used.
+ *   ws: tgnn_union_contour_workspace_bytes(K, n_tiles, max_pieces) bytes, 8-byte aligned, contents on entry do not matter.
+ *   max_pieces bounds the boundary pieces of all masks together; 2 x the vertex count of the alive tiles, summed over the masks,
+ *   always suffices.  A workspace sized for fewer sets CAPACITY and leaves the masks that did not fit without rings. */
+#define TGNN_CONTOUR_ERR_INDEX 1     /* a col_idx or touch_idx entry outside [0, n_tiles) */
+#define TGNN_CONTOUR_ERR_WEDGES 2    /* more than 16 boundary pieces leave one point */
+#define TGNN_CONTOUR_ERR_SPLITS 4    /* more than 8 foreign vertex positions inside one tile side */
+#define TGNN_CONTOUR_ERR_CAPACITY 8  /* cap_rings, cap_points or the workspace's piece capacity is too small */
+#define TGNN_CONTOUR_ERR_TRACE 16    /* the successor relation of a mask is no permutation (its tiles overlap): no rings */
+size_t tgnn_union_contour_workspace_bytes(int64_t n_masks, int64_t n_tiles, int64_t max_pieces);
+int tgnn_union_contour(const double *ring_xy, const int32_t *ring_ptr, int64_t n_tiles, const int32_t *col_ptr,
+                       const int32_t *col_idx, const int32_t *touch_ptr, const int32_t *touch_idx, const int32_t *alive,
+                       int64_t n_masks, double tol, int64_t cap_rings, int64_t cap_points, int32_t *mask_out /* [K][4] */,
+                       int32_t *ring_out /* [cap_rings][4] */, double *ring_area, double *pts_xy, int32_t *pts_src,
+                       int64_t *total_out /* [2] */, int32_t *err_flag, void *ws, size_t ws_bytes, tgnn_stream_t stream);
+
 /* ---- the disjoint union of B layouts of a packed set (csrc/batch_union.hip): what PyG's DataLoader hands the reference's training
  * step for batch_size B (Batch.from_data_list: arrays concatenated, edge ends shifted by the member's node offset).  ONE launch,
  * no host synchronisation, no atomics: the same bits on every call.

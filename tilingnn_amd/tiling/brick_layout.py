@@ -3,11 +3,13 @@
 A layout is five numpy arrays + the index maps to the complete graph.  The reference's class also draws, unions and
 measures polygons through shapely (`show_*`, `get_super_contour_poly`, ...): geometry is outside this package and those
 methods are not mirrored -- hand the arrays of this object to the reference's class when they are needed (same constructor
-arguments).  Two facts of that geometry are here.  The AREA of the union of the layout's tiles, because every score divides by
+arguments).  Three facts of that geometry are here.  The AREA of the union of the layout's tiles, because every score divides by
 it: `compute_super_contour_area` (on the GPU, csrc/union_area.hip) -> `super_contour_area`; there is deliberately no method
 called `get_super_contour_poly`.  And whether a solution leaves an enclosed gap, the validity bit the reference asks every
 solved layout for: `detect_holes` (:229-240), with `count_holes` and the many-layout `detect_holes_many` (on the GPU,
-csrc/union_topology.hip).  What `ML_Solver.predict` and the greedy loop read is here:
+csrc/union_topology.hip).  And the outline of a solution: `get_selected_tiles_union_polygon` (:223-227) and the many-layout
+`union_polygons_many` (on the GPU, csrc/union_contour.hip), as `tiling.region.Region`s instead of a shapely polygon.  What
+`ML_Solver.predict` and the greedy loop read is here:
 `get_data_as_torch_tensor` (:242-246) and `compute_sub_layout` (:248-286, vectorised: one membership mask instead of
 four comprehensions over every edge).
 """
@@ -87,6 +89,14 @@ class BrickLayout:
         """True when the selected tiles enclose a gap -- the reference's `detect_holes` (:229-240)."""
         return self.count_holes(device)[1] > 0
 
+    def get_selected_tiles_union_polygon(self, device=None):
+        """The outline of the union of the selected tiles (`predict == 1`) -- the reference's method of this name (:223-227) --
+        as a list of `tiling.region.Region`, one per connected component (tiles that touch in a single corner are connected,
+        where shapely's unbuffered union would return them apart), exterior counter-clockwise, holes clockwise, every point a
+        vertex of a selected tile.  Computed on the GPU (csrc/union_contour.hip); ValueError when two selected tiles collide.
+        There is no host fallback."""
+        return union_polygons_many([self], device)[0]
+
     def compute_sub_layout(self, predict):
         """:248-286.  `predict`: a SelectionSolution-like object with dicts `labelled_nodes` / `unlabelled_nodes`."""
         assert len(self.node_feature) == len(predict.labelled_nodes) + len(predict.unlabelled_nodes)
@@ -123,6 +133,43 @@ class BrickLayout:
         assert dict(a.re_index) == dict(b.re_index)
 
 
+def _selection_masks(layouts, what, device):
+    """(on_device, alive [K, n_tiles] int32 on the host) of K solved layouts of ONE complete graph: the mask construction
+    `detect_holes_many` and `union_polygons_many` share."""
+    graph = layouts[0].complete_graph
+    if any(l.complete_graph is not graph for l in layouts):
+        raise ValueError(f"{what} takes layouts of one complete graph")
+    from ..util.data_util import graph_on_device
+    on_device = graph_on_device(graph, device)
+    alive = np.zeros((len(layouts), on_device.n_tiles), dtype=np.int32)
+    for k, layout in enumerate(layouts):
+        tiles = layout.selected_tiles()
+        if tiles.size and (tiles.min() < 0 or tiles.max() >= on_device.n_tiles):
+            raise ValueError(f"layout {k}: inverse_index names a tile outside [0, {on_device.n_tiles})")
+        alive[k, tiles] = 1
+    return on_device, alive
+
+
+def union_polygons_many(layouts, device=None):
+    """[`BrickLayout.get_selected_tiles_union_polygon` of each] for K solved layouts of ONE complete graph, with one kernel call
+    and one read-back of the rings for all of them (csrc/union_contour.hip).  ValueError when a layout's selected tiles
+    collide; RuntimeError without a GPU: there is no host fallback."""
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("get_selected_tiles_union_polygon runs on the GPU (csrc/union_contour.hip) and no GPU is available; "
+                           "there is no host fallback")
+    layouts = list(layouts)
+    if not layouts:
+        return []
+    on_device, alive = _selection_masks(layouts, "union_polygons_many", device)
+    contours = on_device.union_contours(torch.from_numpy(alive).to(on_device.device))
+    bad = np.flatnonzero(contours.host()[0][:, 3] != 0)
+    if bad.size:
+        raise ValueError(f"layout {int(bad[0])}: two selected tiles collide (the union polygon is defined for a solution, whose "
+                         f"tiles do not overlap); {bad.size} of {len(layouts)} layouts do")
+    return [contours.polygons(k) for k in range(len(layouts))]
+
+
 def detect_holes_many(layouts, device=None):
     """[(components, holes)] of K solved layouts of ONE complete graph -- `BrickLayout.count_holes` of each -- with one kernel
     call and one read-back for all of them (csrc/union_topology.hip).  ValueError when a layout's selected tiles collide;
@@ -134,17 +181,7 @@ def detect_holes_many(layouts, device=None):
     layouts = list(layouts)
     if not layouts:
         return []
-    graph = layouts[0].complete_graph
-    if any(l.complete_graph is not graph for l in layouts):
-        raise ValueError("detect_holes_many takes layouts of one complete graph")
-    from ..util.data_util import graph_on_device
-    on_device = graph_on_device(graph, device)
-    alive = np.zeros((len(layouts), on_device.n_tiles), dtype=np.int32)
-    for k, layout in enumerate(layouts):
-        tiles = layout.selected_tiles()
-        if tiles.size and (tiles.min() < 0 or tiles.max() >= on_device.n_tiles):
-            raise ValueError(f"layout {k}: inverse_index names a tile outside [0, {on_device.n_tiles})")
-        alive[k, tiles] = 1
+    on_device, alive = _selection_masks(layouts, "detect_holes_many", device)
     out = on_device.union_topology(torch.from_numpy(alive).to(on_device.device)).cpu().numpy()
     bad = np.flatnonzero(out[:, 2] != 0)
     if bad.size:

@@ -354,6 +354,9 @@ def contact_geometry(ring_xy, ring_ptr, tol=UNION_TOL):
     return touch_ptr.astype(np.int32), (keys % n).astype(np.int32)
 
 
+CONTOUR_MAX_SPLITS = 8    # foreign vertex positions tgnn_union_contour keeps inside one tile side (union_contour_piece.h: kMaxSplits)
+CONTOUR_LDS_PIECES = 3072  # boundary pieces of one mask up to which its trace works in LDS (csrc/union_contour.hip: kLdsPieces)
+
 SWEEP_CANDIDATES = (0.1234, 0.5678, 0.9876, 1.4142, 1.7321, 2.2361, 2.7183)     # radians; the first that qualifies is used
 SWEEP_ANGLE_TOL = 1e-5    # side directions closer than this are one direction (the kernel merges arcs that meet within it)
 SWEEP_MIN_GAP = 1e-3      # every side direction keeps this distance (mod pi) from the level lines, and 100 tolerances from each other

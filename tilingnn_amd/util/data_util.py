@@ -344,6 +344,55 @@ class CompleteGraphOnDevice:
                                      "range, 2: more tiles meet in one point than the kernel's wedge list holds)")
         return out
 
+    # -------------------------------------------------------------------------- the outline of a union of tiles
+    def union_contours(self, alive):
+        """`UnionContours` of the K masks `alive` ([K, n_tiles] or [n_tiles], any integer or bool tensor on this device): the
+        boundary rings of the closed union of the tiles with alive[k, i] != 0, one counter-clockwise ring per component (tiles
+        sharing a single point are connected) and one clockwise ring per hole -- the reference's
+        `get_selected_tiles_union_polygon` of that selection.  For selections that do not overlap: a mask with two colliding
+        alive tiles gets status 1 and no rings.  csrc/union_contour.hip; the outputs are sized by the bound of 2 points per
+        vertex of an alive tile (one device reduction), one device-to-host copy brings back the error word and the totals."""
+        import torch
+        from .. import _lib
+        from .._lib import check, lib, ptr
+        from ..tiling.region import UNION_TOL
+        alive = torch.as_tensor(alive, device=self.device)
+        if alive.dim() == 1:
+            alive = alive[None, :]
+        if alive.dim() != 2 or alive.shape[1] != self.n_tiles:
+            raise ValueError(f"alive must be [K, {self.n_tiles}], got {tuple(alive.shape)}")
+        alive = (alive != 0).to(torch.int32).contiguous() if alive.dtype != torch.int32 else alive.contiguous()
+        k = int(alive.shape[0])
+        ring_xy, ring_ptr, col_ptr, col_idx = self._union_geometry()
+        i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=self.device)
+        f64 = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=self.device)
+        if k == 0:
+            return UnionContours(ring_xy, ring_ptr, i32(0, 4), i32(0, 4), f64(0), f64(0, 2), i32(0))
+        touch_ptr, touch_idx, _, _ = self._topology_geometry()
+        verts = (ring_ptr[1:] - ring_ptr[:-1]).to(torch.float64)             # (exact in fp64: the counts are far below 2^53)
+        bound = 2 * int(((alive != 0).to(torch.float64) @ verts).sum().item())
+        if bound >= 2 ** 31:
+            raise ValueError("too many tile vertices for one call; split the masks")
+        cap_rings = bound // 3 + 1                               # (a ring has at least three points)
+        mask_out, ring_out, ring_area = i32(k, 4), i32(cap_rings, 4), f64(cap_rings)
+        pts_xy, pts_src = f64(max(bound, 1), 2), i32(max(bound, 1))
+        word = torch.zeros(3, dtype=torch.int64, device=self.device)          # the error word (int32) and total_out [2]
+        ws_bytes = int(lib.tgnn_union_contour_workspace_bytes(k, self.n_tiles, bound))
+        ws = torch.empty(ws_bytes // 8 + 1, dtype=torch.int64, device=self.device)
+        check(lib.tgnn_union_contour(ptr(ring_xy), ptr(ring_ptr), self.n_tiles, ptr(col_ptr), ptr(col_idx), ptr(touch_ptr),
+                                     ptr(touch_idx), ptr(alive), k, UNION_TOL, cap_rings, bound, ptr(mask_out), ptr(ring_out),
+                                     ptr(ring_area), ptr(pts_xy), ptr(pts_src), ptr(word[1:]), ptr(word), ptr(ws), ws_bytes,
+                                     _lib.current_stream(self.device)))
+        code, rings, points = (int(v) for v in word.cpu().tolist())
+        code &= 0xFFFFFFFF
+        if code:
+            names = {1: "a collision or contact index out of range", 2: "more boundary pieces leave one point than the kernel's "
+                     "wedge list holds", 4: "more foreign vertices inside one tile side than the kernel's split list holds",
+                     8: "an output or the workspace is too small", 16: "the boundary of a mask does not close: its tiles overlap"}
+            raise _lib.TgnnError(f"tgnn_union_contour: device error word {code} ("
+                                 + "; ".join(f"{b}: {t}" for b, t in names.items() if code & b) + ")")
+        return UnionContours(ring_xy, ring_ptr, mask_out, ring_out[:rings], ring_area[:rings], pts_xy[:points], pts_src[:points])
+
     def layouts_in_regions(self, regions, with_area=False):
         """One DeviceLayout per region: the tiles inside it cut out of the complete graph (what `layout` gives for that
         tile set).  Each layout owns its buffers.  with_area: every layout also carries `super_contour_area`, the area of
@@ -358,6 +407,46 @@ class CompleteGraphOnDevice:
                                     sub.collide_edge_index.clone(), sub.inverse_index.clone()))
             if with_area:
                 out[-1].super_contour_area = areas[k]
+        return out
+
+
+class UnionContours:
+    """What `CompleteGraphOnDevice.union_contours` returns: the five device tensors of tgnn_union_contour, cut to the call's
+    totals.  mask [K, 4] int32 = {rings, first ring, points, status}; ring [R, 4] int32 = {first point, points, component,
+    +1 exterior / -1 hole}; ring_area [R] float64, signed; pts_xy [P, 2] float64; pts_src [P] int32, the index of each point into
+    the graph's ring_xy (`pts_xy` holds exactly those coordinates).  `polygons(k)` reads all of them back once."""
+
+    def __init__(self, ring_xy, ring_ptr, mask, ring, ring_area, pts_xy, pts_src):
+        self.ring_xy, self.ring_ptr = ring_xy, ring_ptr
+        self.mask, self.ring, self.ring_area, self.pts_xy, self.pts_src = mask, ring, ring_area, pts_xy, pts_src
+        self._host = None
+
+    def __len__(self):
+        return int(self.mask.shape[0])
+
+    def host(self):
+        """(mask, ring, ring_area, pts_xy, pts_src) as numpy arrays, read back on first use."""
+        if self._host is None:
+            self._host = tuple(t.cpu().numpy() for t in (self.mask, self.ring, self.ring_area, self.pts_xy, self.pts_src))
+        return self._host
+
+    def polygons(self, k):
+        """The union of mask k as a list of `tiling.region.Region(exterior, holes, validate=False)`, one per connected
+        component in ascending component label (the lowest tile of the component), holes in ring order.  A ring that passes a
+        pinch point touches itself there, which is why the regions are not validated.  ValueError when the mask's tiles
+        collide."""
+        from ..tiling.region import Region
+        mask, ring, _, pts_xy, _ = self.host()
+        rings, first, _, status = (int(v) for v in mask[k])
+        if status != 0:
+            raise ValueError(f"mask {k}: two alive tiles collide (the union polygon is defined for a solution, whose tiles do "
+                             "not overlap)")
+        rows = ring[first:first + rings]
+        cut = lambda r: pts_xy[r[0]:r[0] + r[1]].copy()
+        out = []
+        for label in sorted({int(r[2]) for r in rows if r[3] > 0}):
+            (ext,) = [r for r in rows if r[2] == label and r[3] > 0]
+            out.append(Region(cut(ext), [cut(r) for r in rows if r[2] == label and r[3] < 0], validate=False))
         return out
 
 
