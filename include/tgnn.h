@@ -1270,6 +1270,34 @@ int tgnn_union_topology(const double *ring_xy, const int32_t *ring_ptr, int64_t 
                         int64_t n_masks, double tol, double dir_x, double dir_y, int32_t *out /* [K][3] */, int32_t *err_flag,
                         void *ws, size_t ws_bytes, tgnn_stream_t stream);
 
+/* ---- what every candidate tile would do to the topology of K collision-free masks (csrc/union_hole_delta.hip): the map behind
+ * the reference's hole veto (util/algorithms.py:150-152, check_holes -> exist_hole refuses a tile whose union with the selection
+ * has an interior ring).  One call for all K masks and all their tiles, no host synchronisation, integer sums only, every output
+ * word written on every call: the same bytes in both arrays on every run.  No polygon is built: holes = components - chi
+ * (Euler), and one tile changes the components and the local terms of chi only near itself (csrc/union_hole_delta_point.h).
+ *   ring_xy, ring_ptr, col_ptr, col_idx, touch_ptr, touch_idx, alive, tol, (dir_x, dir_y): as for tgnn_union_topology; an entry
+ *   of col_idx or touch_idx outside [0, n_tiles) is skipped and reported.
+ *   state_out [K][n_tiles] int32 = TGNN_HOLE_STATE_*: REFUSED for every tile of a mask in which two alive tiles collide
+ *   (tgnn_union_topology's status 1); ALIVE: t is in the mask; BLOCKED: t collides with an alive tile (collision CSR) or has
+ *   fewer than 3 vertices; CANDIDATE: t may be added.
+ *   delta_out [K][n_tiles][2] int32 = {d components, d holes} = tgnn_union_topology(mask k + {t}) - tgnn_union_topology(mask k),
+ *   field by field, for a CANDIDATE; {0, 0} in every other state.  A candidate that touches no alive tile (a tile floating inside
+ *   a hole included) is {+1, 0}; so is every candidate of the empty mask.
+ *   With t counted at most 16 tiles may meet in one point.
+ *   *err_flag (device, required, zeroed by the caller) gets TGNN_TOPO_ERR_* bits OR-ed in: then the outputs are not to be used.
+ *   ws: tgnn_union_hole_delta_workspace_bytes(K, n_tiles) = 4 K (n_tiles + 1) bytes, 4-byte aligned; its contents on entry do
+ *   not matter.  K == 0 or n_tiles == 0: nothing is queued. */
+#define TGNN_HOLE_STATE_CANDIDATE 0
+#define TGNN_HOLE_STATE_ALIVE 1
+#define TGNN_HOLE_STATE_BLOCKED 2
+#define TGNN_HOLE_STATE_REFUSED 3
+size_t tgnn_union_hole_delta_workspace_bytes(int64_t n_masks, int64_t n_tiles);
+int tgnn_union_hole_delta(const double *ring_xy, const int32_t *ring_ptr, int64_t n_tiles, const int32_t *col_ptr,
+                          const int32_t *col_idx, const int32_t *touch_ptr, const int32_t *touch_idx, const int32_t *alive,
+                          int64_t n_masks, double tol, double dir_x, double dir_y, int32_t *delta_out /* [K][n_tiles][2] */,
+                          int32_t *state_out /* [K][n_tiles] */, int32_t *err_flag, void *ws, size_t ws_bytes,
+                          tgnn_stream_t stream);
+
 /* ---- the outline of the union of the alive tiles of K masks (csrc/union_contour.hip): what the reference's
  * BrickLayout.get_selected_tiles_union_polygon (tiling/brick_layout.py:223-227) returns for a solved layout.  One call for all K
  * masks, no host synchronisation, no floating-point atomics: the same bits in every output on every run.  For masks whose alive

@@ -80,9 +80,11 @@ TGNN_TOPO_FN void add_vertex_wedge(const Tiles &g, Arcs &arcs, int &cnt, int &er
 }
 
 // 1 - m(p) for vertex v of alive tile i of the mask `alive` [n_tiles]; 0 when another tile owns the point (the lowest-numbered
-// alive tile with a vertex within tol of it does).  err gets kErr* bits OR-ed in.
-template <class Arcs>
-TGNN_TOPO_FN int point_term(const Tiles &g, const int32_t *alive, int64_t i, int v, Arcs &arcs, int &err) {
+// alive tile with a vertex within tol of it does).  err gets kErr* bits OR-ed in.  kExtra: tile `extra` counts as alive too,
+// for the alive test and for the owner rule alike (union_hole_delta_point.h: the mask with one candidate added); without it
+// `extra` is not looked at and the code is the one point_term always was.
+template <bool kExtra, class Arcs>
+TGNN_TOPO_FN int point_term_with(const Tiles &g, const int32_t *alive, int64_t extra, int64_t i, int v, Arcs &arcs, int &err) {
     const int v0 = g.ring_ptr[i], n = g.ring_ptr[i + 1] - v0;
     const Pt p = g.ring_xy[v0 + v];
     const double tol2 = g.tol * g.tol;
@@ -94,7 +96,7 @@ TGNN_TOPO_FN int point_term(const Tiles &g, const int32_t *alive, int64_t i, int
             err |= kErrIndex;
             continue;
         }
-        if (j == i || alive[j] == 0) continue;
+        if (j == i || (alive[j] == 0 && !(kExtra && j == extra))) continue;
         const int w0 = g.ring_ptr[j], m = g.ring_ptr[j + 1] - w0;
         if (m < 3) continue;
         const Pt *r = g.ring_xy + w0;
@@ -135,6 +137,11 @@ TGNN_TOPO_FN int point_term(const Tiles &g, const int32_t *alive, int64_t i, int
         merged += reached ? 0 : 1;
     }
     return 1 - merged;
+}
+
+template <class Arcs>
+TGNN_TOPO_FN int point_term(const Tiles &g, const int32_t *alive, int64_t i, int v, Arcs &arcs, int &err) {
+    return point_term_with<false>(g, alive, -1, i, v, arcs, err);
 }
 
 }  // namespace topo

@@ -122,19 +122,27 @@ class ML_Solver:
                                       adj_e_features=adj_edge_features, col_e_idx=collide_edge_index,
                                       col_e_features=collide_edge_features)
 
-    def solve(self, brick_layout):
+    def solve(self, brick_layout, check_holes=False):
         """ml_solver.py:64-73.  Default loop: tilingnn_amd.util.algorithms.solve_by_probablistic_greedy (layout resident
         on the GPU; score = Losses.solution_score when the layout carries its complete graph and super-contour area, or
-        `score_fn`, else None); `greedy_solver=` swaps in another one, e.g. the reference's own."""
+        `score_fn`, else None); `greedy_solver=` swaps in another one, e.g. the reference's own.
+        check_holes: the reference's hole veto (algorithms.py:150-152) in that loop -- a tile that would enclose a gap is passed
+        over, so the solution has no hole (`solve_by_probablistic_greedy(check_holes=True)`, csrc/union_hole_delta.hip).  Always
+        the sequential sweep, whatever `device_greedy_min_nodes` says: the batched acceptance has no hole rule."""
         if self._greedy_solver is None:
             from ...util.algorithms import solve_by_device_greedy, solve_by_probablistic_greedy
             n_nodes = int(brick_layout.node_feature.shape[0])
-            if self.device_greedy_min_nodes is not None and n_nodes >= self.device_greedy_min_nodes:
+            if check_holes:                                      # the sequential sweep only: tiles accepted at once can close a gap jointly
+                output_solution, score, predict_order = solve_by_probablistic_greedy(self, brick_layout, score_fn=self._score_fn,
+                                                                                     check_holes=True)
+            elif self.device_greedy_min_nodes is not None and n_nodes >= self.device_greedy_min_nodes:
                 # large layouts: the acceptance batched on the device (a documented substitute of the sequential sweep)
                 output_solution, score, predict_order = solve_by_device_greedy(self, brick_layout, seed=self.device_greedy_seed,
                                                                                score_fn=self._score_fn)
             else:
                 output_solution, score, predict_order = solve_by_probablistic_greedy(self, brick_layout, score_fn=self._score_fn)
+        elif check_holes:
+            raise ValueError("check_holes is an option of the default greedy loop; hand it to the `greedy_solver` given instead")
         else:
             output_solution, score, predict_order = self._greedy_solver(self, brick_layout)
         output_layout = deepcopy(brick_layout)

@@ -8,7 +8,9 @@ it: `compute_super_contour_area` (on the GPU, csrc/union_area.hip) -> `super_con
 called `get_super_contour_poly`.  And whether a solution leaves an enclosed gap, the validity bit the reference asks every
 solved layout for: `detect_holes` (:229-240), with `count_holes` and the many-layout `detect_holes_many` (on the GPU,
 csrc/union_topology.hip).  And the outline of a solution: `get_selected_tiles_union_polygon` (:223-227) and the many-layout
-`union_polygons_many` (on the GPU, csrc/union_contour.hip), as `tiling.region.Region`s instead of a shapely polygon.  What
+`union_polygons_many` (on the GPU, csrc/union_contour.hip), as `tiling.region.Region`s instead of a shapely polygon.  And what
+adding each further tile would do to the holes of a selection, the question behind the reference's `check_holes` veto
+(util/algorithms.py:150-152): `hole_deltas` (on the GPU, csrc/union_hole_delta.hip).  What
 `ML_Solver.predict` and the greedy loop read is here:
 `get_data_as_torch_tensor` (:242-246) and `compute_sub_layout` (:248-286, vectorised: one membership mask instead of
 four comprehensions over every edge).
@@ -88,6 +90,34 @@ class BrickLayout:
     def detect_holes(self, device=None):
         """True when the selected tiles enclose a gap -- the reference's `detect_holes` (:229-240)."""
         return self.count_holes(device)[1] > 0
+
+    def hole_deltas(self, selection=None, device=None):
+        """(dcomponents, dholes, state), int32 arrays with one entry per node of this layout: what adding the node's tile to
+        `selection` (one 0/1 entry per node; default `predict`) would do to `count_holes()` of it, where state is 0 (the tile
+        may be added); state 1: the node is selected, 2: its tile collides with a selected one -- both deltas 0 there.  The
+        reference's hole veto (util/algorithms.py:150-152) refuses the nodes with dholes > 0; the ones with dholes < 0 plug
+        a gap.  Tiles of the complete graph outside the layout are not reported.  Computed on the GPU
+        (csrc/union_hole_delta.hip); ValueError when two selected tiles collide.  There is no host fallback."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("hole_deltas runs on the GPU (csrc/union_hole_delta.hip) and no GPU is available; "
+                               "there is no host fallback")
+        from ..util.data_util import graph_on_device
+        on_device = graph_on_device(self.complete_graph, device)
+        n = len(self.node_feature)
+        chosen = np.asarray(self.predict if selection is None else selection).reshape(-1)
+        if chosen.shape[0] != n:
+            raise ValueError(f"selection must have one entry per node ({n}), got {chosen.shape[0]}")
+        tiles = np.fromiter((self.inverse_index[i] for i in range(n)), dtype=np.int64, count=n)
+        if n and (tiles.min() < 0 or tiles.max() >= on_device.n_tiles):
+            raise ValueError(f"inverse_index names a tile outside [0, {on_device.n_tiles})")
+        alive = np.zeros(on_device.n_tiles, dtype=np.int32)
+        alive[tiles[chosen == 1]] = 1
+        delta, state = on_device.hole_deltas(torch.from_numpy(alive).to(on_device.device))
+        both = torch.cat([delta[0], state[0][:, None]], dim=1).cpu().numpy()[tiles]       # one read-back
+        if n and (both[:, 2] == 3).any():
+            raise ValueError("two selected tiles collide (hole_deltas is defined for a selection whose tiles do not overlap)")
+        return both[:, 0].copy(), both[:, 1].copy(), both[:, 2].copy()
 
     def get_selected_tiles_union_polygon(self, device=None):
         """The outline of the union of the selected tiles (`predict == 1`) -- the reference's method of this name (:223-227) --

@@ -17,6 +17,10 @@ layout carries what it needs -- its complete graph (tile rings, max_area, max_al
 contour (`layout.super_contour_area`, or the reference class's `get_super_contour_poly()`); a bare `DeviceLayout` has
 neither and scores `None` unless `score_fn(selection, origin_layout)` is given.
 
+`check_holes=True` adds the reference's hole veto (algorithms.py:150-152) to that sweep: `HoleGuard` keeps, per node, what adding
+its tile would do to the holes of the selection (csrc/union_hole_delta.hip) and the sweep passes over the tiles that would
+enclose a gap, before the draw.
+
 `solve_many_by_device_greedy` runs K such device-greedy solves (the crops of one silhouette, Tiling-Shape.py:60-64) in one loop
 over `PackedLayouts`: one compaction, one read-back and one acceptance call per round for all of them (csrc/greedy_many.hip).
 """
@@ -122,9 +126,11 @@ class HostSweep:
     def ids(self) -> np.ndarray:
         return np.flatnonzero(self.unlabelled)
 
-    def round(self, ids: np.ndarray, prob) -> list:
+    def round(self, ids: np.ndarray, prob, guard=None) -> list:
         """One round: `prob` = the network's probabilities of the nodes `ids` (ascending original numbers).  Returns the original
-        numbers of the nodes labelled in this round (selected ones and their collision neighbours)."""
+        numbers of the nodes labelled in this round (selected ones and their collision neighbours).  guard: a `HoleGuard`; a
+        node it vetoes is passed over BEFORE the draw (the reference's order, algorithms.py:150-152), so it consumes no random
+        number and stays unlabelled; without one the path and the RNG stream are the ones they always were."""
         prob = np.asarray(prob, dtype=np.float64).reshape(-1)
         prob_per_node = np.power(np.power(self.prob_saved[ids], self.round_cnt - 1) * prob, 1 / self.round_cnt)     # (:33-34)
         self.prob_saved[ids] = prob_per_node
@@ -133,11 +139,15 @@ class HostSweep:
             origin_idx = ids[idx]
             if not unlabelled[origin_idx]:                      # (:47-48)
                 break
+            if guard and guard.vetoed(origin_idx):              # (:150-152)
+                continue
             if np.exp((prob_per_node[idx] - 1) * 1.0) > self.uniform():     # (:51)
                 unlabelled[origin_idx] = False
                 self.selection[origin_idx] = 1
                 self.order.append(int(origin_idx))
                 killed.append(origin_idx)
+                if guard:
+                    guard.accept(origin_idx)
                 if self.has_col:                                # label_collision_neighbor (:196-207)
                     for v in self.nbr[self.starts[origin_idx]:self.starts[origin_idx + 1]]:
                         if unlabelled[v]:
@@ -147,22 +157,87 @@ class HostSweep:
         return killed
 
 
-def solve_by_probablistic_greedy(ml_solver, origin_layout, score_fn=None, on_round=None):
-    """algorithms.py:18-62.  `origin_layout`: BrickLayout-like numpy arrays (uploaded once) or a DeviceLayout."""
+class HoleGuard:
+    """The hole veto of the reference's assembly (algorithms.py:150-152, check_holes -> exist_hole: refuse a tile whose union
+    with the selection has an interior ring) for the sweep of `HostSweep`: holds, per node of the layout, what adding its tile
+    would do to the holes of the current selection (`CompleteGraphOnDevice.hole_deltas`, csrc/union_hole_delta.hip) and vetoes
+    the nodes with d holes > 0.  The selection starts empty with 0 holes and only tiles with d holes <= 0 are accepted, so every
+    prefix of the order has 0 holes -- and with 0 holes "the union has an interior ring" IS d holes > 0.  Built from the layout's
+    `complete_graph` and `inverse_index` (node -> tile).  `accept(node)` queues ONE kernel call and reads its map back once (the
+    map and the error word in one copy); `launches` and `vetoes` count both."""
+
+    def __init__(self, complete_graph, inverse_index, n: int, device=None):
+        from .data_util import graph_on_device
+        self.on_device = graph_on_device(complete_graph, device)
+        dev, n_tiles = self.on_device.device, self.on_device.n_tiles
+        self.tiles = np.fromiter((inverse_index[i] for i in range(n)), dtype=np.int64, count=n)
+        if n and (self.tiles.min() < 0 or self.tiles.max() >= n_tiles):
+            raise ValueError(f"inverse_index names a tile outside [0, {n_tiles})")
+        self._alive = torch.zeros(n_tiles, dtype=torch.int32, device=dev)
+        self._out = torch.zeros(3 * n_tiles + 1, dtype=torch.int32, device=dev)          # delta [n_tiles][2] | state [n_tiles] | error word
+        self._host = torch.empty(3 * n_tiles + 1, dtype=torch.int32, pin_memory=True)
+        self.dholes = np.zeros(n, dtype=np.int32)               # the empty selection: every tile adds {+1, 0}
+        self.state = np.zeros(n, dtype=np.int32)
+        self.launches = self.vetoes = 0
+
+    def vetoed(self, node) -> bool:
+        if self.dholes[node] > 0:
+            self.vetoes += 1
+            return True
+        return False
+
+    def all_vetoed(self, nodes) -> bool:
+        """Whether every one of `nodes` is vetoed under the current selection (the stop rule; counts nothing)."""
+        return bool((self.dholes[nodes] > 0).all())
+
+    def accept(self, node):
+        od, n_tiles = self.on_device, self.on_device.n_tiles
+        self._alive[int(self.tiles[node])] = 1
+        self._out[-1:].zero_()
+        od.hole_deltas_into(self._alive[None, :], self._out[:2 * n_tiles], self._out[2 * n_tiles:3 * n_tiles], self._out[-1:])
+        self._host.copy_(self._out, non_blocking=True)
+        torch.cuda.current_stream(od.device).synchronize()
+        self.launches += 1
+        words = self._host.numpy()
+        if words[-1]:
+            raise _lib.TgnnError(f"tgnn_union_hole_delta: device error word {int(words[-1])} (1: collision or contact index out "
+                                 "of range, 2: more tiles meet in one point than the kernel's wedge list holds)")
+        self.state = words[2 * n_tiles:3 * n_tiles][self.tiles]
+        if (self.state == 3).any():
+            raise ValueError("HoleGuard: two accepted tiles collide")
+        self.dholes = words[:2 * n_tiles].reshape(n_tiles, 2)[self.tiles, 1]
+
+
+def solve_by_probablistic_greedy(ml_solver, origin_layout, score_fn=None, on_round=None, check_holes=False):
+    """algorithms.py:18-62.  `origin_layout`: BrickLayout-like numpy arrays (uploaded once) or a DeviceLayout.
+    check_holes: the reference's hole veto (:150-152) in this sweep, through a `HoleGuard` (kept as
+    `solve_by_probablistic_greedy.last_guard`): a tile that would enclose a gap is passed over, so the selection never has a
+    hole; the layout must carry its `complete_graph` and `inverse_index`.  A round after which every unlabelled node is vetoed
+    ends the loop with those nodes unselected: nothing can change any more.  Like the reference's, the veto cannot close a
+    tiling around a hole the target region itself has."""
+    if check_holes and getattr(origin_layout, "complete_graph", None) is None:
+        raise ValueError("check_holes needs the layout's complete graph (tile rings) and inverse_index: a BrickLayout, not a "
+                         "bare DeviceLayout")
     device = ml_solver.device
     origin = origin_layout if isinstance(origin_layout, DeviceLayout) else DeviceLayout.upload(origin_layout, device)
     n = int(origin.node_feature.shape[0])
     sweep = HostSweep(n, origin.collide_edge_index.cpu().numpy())
     builder = SubLayoutBuilder(origin)
     alive_dev = torch.ones(n, dtype=torch.int32, device=origin.node_feature.device)
+    guard = None
+    if check_holes:
+        guard = HoleGuard(origin_layout.complete_graph, origin_layout.inverse_index, n, origin.node_feature.device)
+        solve_by_probablistic_greedy.last_guard = guard
     while sweep.unlabelled.any():
         temp_layout = builder.build(alive_dev)
         ids = sweep.ids()                                       # == temp_layout.inverse_index (kept on the device)
         if on_round is not None:
             on_round(temp_layout)
-        killed = sweep.round(ids, ml_solver.predict(temp_layout))
+        killed = sweep.round(ids, ml_solver.predict(temp_layout), guard)
         if killed:
             alive_dev[torch.from_numpy(np.asarray(killed, dtype=np.int64)).to(alive_dev.device)] = 0
+        if guard and guard.all_vetoed(sweep.ids()):             # (the map is at hand: no launch)
+            sweep.unlabelled[:] = False
     score = create_score(sweep.selection, origin_layout, score_fn, device)
     return sweep.selection, score, sweep.order
 

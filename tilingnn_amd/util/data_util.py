@@ -344,6 +344,50 @@ class CompleteGraphOnDevice:
                                      "range, 2: more tiles meet in one point than the kernel's wedge list holds)")
         return out
 
+    def hole_deltas(self, alive):
+        """(delta [K, n_tiles, 2] int32, state [K, n_tiles] int32) on the device: for every tile t of every mask (`alive` as for
+        `union_topology`) what adding t would do -- delta[k, t] = {d components, d holes} = union_topology(mask k + {t}) -
+        union_topology(mask k) -- where state[k, t] is 0 (a candidate); state 1: t is alive, 2: t collides with an alive tile,
+        3: two alive tiles of the mask collide (the whole row); the delta is {0, 0} there.  What the reference's hole veto asks
+        per tile (util/algorithms.py:150-152), for all tiles at once.  csrc/union_hole_delta.hip; one device-to-host copy of
+        the error word."""
+        import torch
+        from .. import _lib
+        alive = torch.as_tensor(alive, device=self.device)
+        if alive.dim() == 1:
+            alive = alive[None, :]
+        if alive.dim() != 2 or alive.shape[1] != self.n_tiles:
+            raise ValueError(f"alive must be [K, {self.n_tiles}], got {tuple(alive.shape)}")
+        alive = (alive != 0).to(torch.int32).contiguous() if alive.dtype != torch.int32 else alive.contiguous()
+        k = int(alive.shape[0])
+        delta = torch.empty(k, self.n_tiles, 2, dtype=torch.int32, device=self.device)
+        state = torch.empty(k, self.n_tiles, dtype=torch.int32, device=self.device)
+        if k and self.n_tiles:
+            err = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.hole_deltas_into(alive, delta, state, err)
+            code = int(err.item())
+            if code:
+                raise _lib.TgnnError(f"tgnn_union_hole_delta: device error word {code} (1: collision or contact index out of "
+                                     "range, 2: more tiles meet in one point than the kernel's wedge list holds)")
+        return delta, state
+
+    def hole_deltas_into(self, alive, delta, state, err):
+        """The call of `hole_deltas` alone, queued on the current stream with nothing read back: `alive` [K, n_tiles] int32
+        contiguous, `delta` / `state` / `err` int32 device buffers of 2 K n_tiles / K n_tiles / 1 words, `err` zeroed by the
+        caller (util.algorithms.HoleGuard keeps the three in one buffer and reads it back in one copy)."""
+        import torch
+        from .. import _lib
+        from .._lib import check, lib, ptr
+        from ..tiling.region import UNION_TOL
+        k = int(alive.shape[0])
+        ring_xy, ring_ptr, col_ptr, col_idx = self._union_geometry()
+        touch_ptr, touch_idx, dir_x, dir_y = self._topology_geometry()
+        ws_bytes = int(lib.tgnn_union_hole_delta_workspace_bytes(k, self.n_tiles))
+        ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=self.device)
+        check(lib.tgnn_union_hole_delta(ptr(ring_xy), ptr(ring_ptr), self.n_tiles, ptr(col_ptr), ptr(col_idx), ptr(touch_ptr),
+                                        ptr(touch_idx), ptr(alive), k, UNION_TOL, dir_x, dir_y, ptr(delta), ptr(state),
+                                        ptr(err), ptr(ws), ws_bytes, _lib.current_stream(self.device)))
+
     # -------------------------------------------------------------------------- the outline of a union of tiles
     def union_contours(self, alive):
         """`UnionContours` of the K masks `alive` ([K, n_tiles] or [n_tiles], any integer or bool tensor on this device): the
