@@ -177,6 +177,14 @@ int tgnn_nnconv_mean_cols_f16_fwd(const float *h, int64_t ldh, int64_t n_src_row
  * of the build: tgnn_nnconv_cols_workspace_bytes(N).  tgnn_nnconv_mean_eg_fwd is the op for tests (bounds and the fp16-pair
  * weight image computed inside, as tgnn_nnconv_mean_cols_f16_fwd does); width 32, packed rows (ldh == 32). */
 int64_t tgnn_nnconv_eg_max_groups(int64_t n_nodes, int64_t n_edges, int32_t n_types);
+/* The register and LDS footprint of a kernel of the general schedule's layer loop (csrc/nnconv_eg_plan.h: 0 NNConv on edge groups,
+ * 1 GIN aggregate, 2 GIN MLP, 3 merge), as hipFuncGetAttributes reports it for the loaded code object.  out [6]: waves of a block,
+ * waves of a block on one SIMD, the register cap the kernel is pinned to, the registers per lane the runtime reports, LDS bytes of
+ * a block (static + dynamic at n_types edge types), maxThreadsPerBlock.  Counts only: nothing is launched. */
+int tgnn_kernel_footprint(int32_t kernel, int32_t n_types, int32_t *out);
+/* gin32_mlp_kernel in 4-wave blocks, one per 64 rows (twice the partial rows): 0 nowhere, 1 (default) in the inference forward of
+ * the general schedule, 2 in tgnn_gin32_fwd as well (tests).  Returns the previous mode.  Rows keep their bits in every mode. */
+int32_t tgnn_set_gin_mlp_half_blocks(int32_t mode);
 int tgnn_nnconv_eg_build(const int32_t *rowptr, const int32_t *col_src, const int32_t *col_type, int64_t n_nodes,
                          int32_t n_types, int32_t *tile_grp_ptr, int32_t *grp, void *ws, size_t ws_bytes, tgnn_stream_t stream);
 int tgnn_nnconv_mean_eg_fwd(const float *h, int64_t ldh, int64_t n_src_rows, const int32_t *tile_grp_ptr,
@@ -320,6 +328,13 @@ int tgnn_bn_apply(const float *v, int64_t ldv, const float *stat, int64_t n_rows
 
 /* Branch merge (TilinGNN.py:64-71):  out = BN1(a1) * BN2(a2) [+ resid];  optionally also writes
  * h2 = BN2(a2) (NULL to skip).  All [N, C] dense. */
+/* The general schedule's merge at width 32 with the first BatchNorm's finalize inside (csrc/bn_merge.hip: merge_bn1_kernel up to 128
+ * partial rows, merge_bn1_wide_kernel above): out = BN1(a1) * BN2(a2) (+ resid), BN1's record derived by every block from the
+ * partial rows [n_partials][2][32] with tgnn_bn_finalize's tree (the same bits; written to stat1_out [4][32] when given), BN2 as
+ * the record stat2.  No running statistics.  The op for tests: tgnn_forward reaches the same launcher. */
+int tgnn_merge_bn1_fwd(const float *a1, const double *partials, int32_t n_partials, const float *gamma, const float *beta,
+                       int64_t n_rows_total, float eps, const float *a2, const float *stat2, const float *resid,
+                       int64_t n_nodes, float *out, float *stat1_out, tgnn_stream_t stream);
 int tgnn_merge_fwd(const float *a1, const float *stat1, const float *a2, const float *stat2,
                    const float *resid, int64_t n_nodes, int32_t c, float *out, float *h2_out,
                    tgnn_stream_t stream);

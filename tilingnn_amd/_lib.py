@@ -116,6 +116,9 @@ def _load() -> C.CDLL:
         "tgnn_nnconv_mean_cols_f16_fwd": (C.c_int, [p, i64, i64, p, p, p, p, i32, p, p, i64, i32, i32, p, p, p, p, pi32, p]),
         "tgnn_nnconv_eg_max_groups": (i64, [i64, i64, i32]),
         "tgnn_nnconv_eg_build": (C.c_int, [p, p, p, i64, i32, p, p, p, sz, p]),
+        "tgnn_kernel_footprint": (C.c_int, [i32, i32, pi32]),
+        "tgnn_set_gin_mlp_half_blocks": (i32, [i32]),
+        "tgnn_merge_bn1_fwd": (C.c_int, [p, p, i32, p, p, i64, C.c_float, p, p, p, i64, p, p, p]),
         "tgnn_nnconv_mean_eg_fwd": (C.c_int, [p, i64, i64, p, p, p, i32, p, p, i64, i32, p, p, p, p, pi32, p]),
         "tgnn_nnconv64_eg_max_types": (i32, []),
         "tgnn_nnconv64_eg_image_floats": (sz, [i32]),
@@ -316,7 +319,7 @@ EXPORTED_SYMBOLS = (
     "tgnn_version", "tgnn_last_error", "tgnn_csr_workspace_bytes", "tgnn_csr_build",
     "tgnn_edge_dedup_workspace_bytes", "tgnn_edge_type_dedup", "tgnn_gather_i32", "tgnn_edge_weight_table",
     "tgnn_nnconv_mean_fwd", "tgnn_nnconv_cols_max_columns", "tgnn_nnconv_cols_workspace_bytes",
-    "tgnn_nnconv_cols_build", "tgnn_nnconv_cols_max_types", "tgnn_nnconv_weight_image_floats", "tgnn_nnconv_mean_cols_fwd", "tgnn_nnconv_mean_cols_f16_fwd", "tgnn_nnconv_eg_max_groups", "tgnn_nnconv_eg_build", "tgnn_nnconv_mean_eg_fwd",
+    "tgnn_nnconv_cols_build", "tgnn_nnconv_cols_max_types", "tgnn_nnconv_weight_image_floats", "tgnn_nnconv_mean_cols_fwd", "tgnn_nnconv_mean_cols_f16_fwd", "tgnn_nnconv_eg_max_groups", "tgnn_nnconv_eg_build", "tgnn_kernel_footprint", "tgnn_set_gin_mlp_half_blocks", "tgnn_merge_bn1_fwd", "tgnn_nnconv_mean_eg_fwd",
     "tgnn_nnconv64_eg_max_types", "tgnn_nnconv64_eg_image_floats", "tgnn_nnconv64_mean_eg_fwd", "tgnn_set_nnconv64_eg",
     "tgnn_gin64_fwd", "tgnn_set_gin64_mfma", "tgnn_gin32_fwd",
     "tgnn_ubench_row_gather", "tgnn_mid_entries_words", "tgnn_mid_entries_build", "tgnn_forward_path_counts", "tgnn_set_mid_layout_limit", "tgnn_get_mid_layout_limit", "tgnn_mid_layout_max_nodes",

@@ -10,6 +10,7 @@
 // 4-row stat record consumed while loading (mean split hi/lo so that v - mean stays exact for the
 // near-constant columns the collision branch produces).  Deterministic: fixed reduction tree.
 #include "tgnn_common.h"
+#include "nnconv_eg_plan.h"
 
 namespace tgnn {
 
@@ -285,11 +286,16 @@ __global__ __launch_bounds__(256) void merge_bn1_kernel(const float *__restrict_
 // reduce them exactly as bn_finalize_kernel does (16 row groups x 64 columns, every thread ONE batch of independent loads,
 // then the fixed 16-way fold: the same tree, the same bits), so that NNConv -> merge needs no launch in between.  256 blocks
 // x 115 KB of partial rows come out of L2; the element-wise part then walks ~3 float4 per thread.
-__global__ __launch_bounds__(1024) void merge_bn1_wide_kernel(const float *__restrict__ a1, BnJob j1, int64_t n_total, float eps,
-                                                              float momentum, const float *__restrict__ a2,
-                                                              const float *__restrict__ st2, const float *__restrict__ resid,
-                                                              int64_t n4, float *__restrict__ out, unsigned *__restrict__ absmax_out) {
+// THREADS = 512 (the co-residency study's 8-wave shape, profiles/coresident_stage0.txt): a thread reduces the row groups g and g + 8,
+// sixteen rows of each per round trip (from row 256 on: a second one), every group's rows still added in ascending order -- the same bits.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS, 4) void merge_bn1_wide_kernel(const float *__restrict__ a1, BnJob j1, int64_t n_total, float eps,
+                                                                    float momentum, const float *__restrict__ a2,
+                                                                    const float *__restrict__ st2, const float *__restrict__ resid,
+                                                                    int64_t n4, float *__restrict__ out, unsigned *__restrict__ absmax_out) {
     constexpr int c = 32, two_f = 64, groups = 16;
+    static_assert(THREADS == 1024 || THREADS == 512, "one or two row groups per thread");
+    constexpr int kGpt = groups * two_f / THREADS, kBatch = 32 / kGpt;       // row groups per thread, rows of a group per round trip
     __shared__ double red[groups * two_f];
     __shared__ double tot[two_f];
     __shared__ __attribute__((aligned(16))) float st1[4 * c];
@@ -304,7 +310,7 @@ __global__ __launch_bounds__(1024) void merge_bn1_wide_kernel(const float *__res
             pre_rv = j1.running_var[tid];
         }
     }
-    if (tid >= 1024 - 4 * c) st2s[tid - (1024 - 4 * c)] = st2[tid - (1024 - 4 * c)];
+    if (tid >= THREADS - 4 * c) st2s[tid - (THREADS - 4 * c)] = st2[tid - (THREADS - 4 * c)];
     // [r5] ONE round trip for the partial rows -- every thread asks for its <= 32 rows (g, g + 16, ..) at once through a buffer
     // descriptor that ends with the rows (a row past the end returns 0.0 without touching memory and adds nothing: the same
     // sum, term by term, as bn_finalize_kernel's batches) -- and the first kPf items' operands go out BEHIND them: the wait
@@ -319,22 +325,37 @@ __global__ __launch_bounds__(1024) void merge_bn1_wide_kernel(const float *__res
         const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<double *>(j1.partials), 0, (int)((uint32_t)j1.n_partials * (uint32_t)two_f * 8u), 0x00020000);
         static_assert(TGNN_BN_MAX_PARTIALS <= 32 * groups, "32 rows per thread cover every partial row");
-        u32x2_ v[32];
+        double acc[kGpt];
 #pragma unroll
-        for (int q = 0; q < 32; ++q)
-            v[q] = __builtin_amdgcn_raw_buffer_load_b64(prs, ((uint32_t)(g + q * groups) * (uint32_t)two_f + (uint32_t)j) * 8u, 0, 0);
+        for (int u = 0; u < kGpt; ++u) acc[u] = 0.0;
 #pragma unroll
-        for (int k = 0; k < kPf; ++k) {
-            const int64_t i = i_first + k * i_step;
-            const int64_t ii = i < n4 ? i : n4 - 1;          // (clamped: nothing is loaded inside a branch)
-            px1[k] = reinterpret_cast<const float4 *>(a1)[ii];
-            px2[k] = reinterpret_cast<const float4 *>(a2)[ii];
-            pr[k] = resid ? reinterpret_cast<const float4 *>(resid)[ii] : float4{0.f, 0.f, 0.f, 0.f};
+        for (int q0 = 0; q0 < 32; q0 += kBatch) {
+            // (a later round trip only where its rows exist: rows past the end are zeros, and x + 0.0 = x)
+            if (q0 > 0 && j1.n_partials <= q0 * groups) break;
+            u32x2_ v[kGpt][kBatch];
+#pragma unroll
+            for (int u = 0; u < kGpt; ++u)
+#pragma unroll
+                for (int q = 0; q < kBatch; ++q)
+                    v[u][q] = __builtin_amdgcn_raw_buffer_load_b64(
+                        prs, ((uint32_t)(g + u * (THREADS / two_f) + (q0 + q) * groups) * (uint32_t)two_f + (uint32_t)j) * 8u, 0, 0);
+            if (q0 == 0) {
+#pragma unroll
+                for (int k = 0; k < kPf; ++k) {
+                    const int64_t i = i_first + k * i_step;
+                    const int64_t ii = i < n4 ? i : n4 - 1;      // (clamped: nothing is loaded inside a branch)
+                    px1[k] = reinterpret_cast<const float4 *>(a1)[ii];
+                    px2[k] = reinterpret_cast<const float4 *>(a2)[ii];
+                    pr[k] = resid ? reinterpret_cast<const float4 *>(resid)[ii] : float4{0.f, 0.f, 0.f, 0.f};
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kGpt; ++u)
+#pragma unroll
+                for (int q = 0; q < kBatch; ++q) acc[u] += __builtin_bit_cast(double, v[u][q]);
         }
-        double acc = 0.0;
 #pragma unroll
-        for (int q = 0; q < 32; ++q) acc += __builtin_bit_cast(double, v[q]);
-        red[tid] = acc;
+        for (int u = 0; u < kGpt; ++u) red[tid + u * THREADS] = acc[u];
     }
     __syncthreads();
     if (tid < two_f) {
@@ -391,11 +412,29 @@ __global__ __launch_bounds__(1024) void merge_bn1_wide_kernel(const float *__res
         const int64_t i = i_first + k * i_step;
         if (i < n4) item(px1[k], px2[k], pr[k], i);
     }
-    for (int64_t i = i_first + kPf * i_step; i < n4; i += i_step) {
-        const float4 x1 = reinterpret_cast<const float4 *>(a1)[i];
-        const float4 x2 = reinterpret_cast<const float4 *>(a2)[i];
-        const float4 r = resid ? reinterpret_cast<const float4 *>(resid)[i] : float4{0.f, 0.f, 0.f, 0.f};
-        item(x1, x2, r, i);
+    if constexpr (THREADS == 512) {                          // (half the threads: twice the items, kPf of them in flight at a time)
+        for (int64_t i0 = i_first + kPf * i_step; i0 < n4; i0 += kPf * i_step) {
+#pragma unroll
+            for (int k = 0; k < kPf; ++k) {
+                const int64_t i = i0 + k * i_step;
+                const int64_t ii = i < n4 ? i : n4 - 1;
+                px1[k] = reinterpret_cast<const float4 *>(a1)[ii];
+                px2[k] = reinterpret_cast<const float4 *>(a2)[ii];
+                pr[k] = resid ? reinterpret_cast<const float4 *>(resid)[ii] : float4{0.f, 0.f, 0.f, 0.f};
+            }
+#pragma unroll
+            for (int k = 0; k < kPf; ++k) {
+                const int64_t i = i0 + k * i_step;
+                if (i < n4) item(px1[k], px2[k], pr[k], i);
+            }
+        }
+    } else {
+        for (int64_t i = i_first + kPf * i_step; i < n4; i += i_step) {
+            const float4 x1 = reinterpret_cast<const float4 *>(a1)[i];
+            const float4 x2 = reinterpret_cast<const float4 *>(a2)[i];
+            const float4 r = resid ? reinterpret_cast<const float4 *>(resid)[i] : float4{0.f, 0.f, 0.f, 0.f};
+            item(x1, x2, r, i);
+        }
     }
     absmax_flush(am, absmax_out);
 }
@@ -781,13 +820,27 @@ void launch_shard_sum_peers(const double *peer_sums, const double *own, int worl
     shard_sum_peers_kernel<<<1, 128, 0, s>>>(peer_sums, own, world, rank, total);
 }
 
+// 8-wave blocks, two waves per SIMD at <= 128 registers: a block fits a CU beside a 4-wave block of the collision chain's GIN MLP
+// (nnconv_eg_plan.h: kCoResidentPairs; profiles/coresident_stage0.txt)
+#ifdef TGNN_ABL_MERGEW16
+constexpr int kWideThreads = 1024;                           // (timing switch: the 16-wave shape)
+#else
+constexpr int kWideThreads = 512;
+#endif
+static_assert(kWideThreads == 1024 || kLayerFootprints[kLayerMerge].waves_per_block * 64 == kWideThreads, "nnconv_eg_plan.h states the shape");
+
+int merge_wide_func_attributes(hipFuncAttributes *attr, int *waves) {
+    *waves = kWideThreads / 64;
+    return (int)hipFuncGetAttributes(attr, reinterpret_cast<const void *>(merge_bn1_wide_kernel<kWideThreads>));
+}
+
 void launch_merge_bn1(const float *a1, const BnJob &j1, int64_t n_total, float eps, float momentum, const float *a2,
                       const float *stat2, const float *resid, int64_t n_nodes, float *out, hipStream_t s, unsigned *absmax_out) {
     const int64_t n4 = n_nodes * 32 / 4;
     if (j1.n_partials > 128) {
-        int64_t blocks = (n4 + 1023) / 1024;
+        int64_t blocks = (n4 + kWideThreads - 1) / kWideThreads;
         if (blocks > 256) blocks = 256;
-        merge_bn1_wide_kernel<<<(unsigned)blocks, 1024, 0, s>>>(a1, j1, n_total, eps, momentum, a2, stat2, resid, n4, out, absmax_out);
+        merge_bn1_wide_kernel<kWideThreads><<<(unsigned)blocks, kWideThreads, 0, s>>>(a1, j1, n_total, eps, momentum, a2, stat2, resid, n4, out, absmax_out);
         return;
     }
     int64_t blocks = (n4 + 255) / 256;
@@ -859,6 +912,21 @@ extern "C" int tgnn_bn_apply(const float *v, int64_t ldv, const float *stat, int
     if (n_rows <= 0) return TGNN_OK;
     TGNN_CHECK_ARG(v && stat && out && f >= 1 && ldv >= f && ldo >= f, "arguments");
     launch_bn_apply(v, ldv, stat, n_rows, f, out, ldo, nullptr, static_cast<hipStream_t>(stream));
+    TGNN_CHECK_LAUNCH();
+    return TGNN_OK;
+}
+
+extern "C" int tgnn_merge_bn1_fwd(const float *a1, const double *partials, int32_t n_partials, const float *gamma, const float *beta,
+                                  int64_t n_rows_total, float eps, const float *a2, const float *stat2, const float *resid,
+                                  int64_t n_nodes, float *out, float *stat1_out, tgnn_stream_t stream) {
+    DeviceGuard guard__(stream);
+    if (n_nodes <= 0) return TGNN_OK;
+    TGNN_CHECK_ARG(a1 && partials && gamma && beta && a2 && stat2 && out, "null pointer");
+    TGNN_CHECK_ARG(n_partials >= 1 && n_partials <= TGNN_BN_MAX_PARTIALS && n_rows_total >= 1, "partial rows / row count");
+    TGNN_CHECK_ARG(((uintptr_t)a1 | (uintptr_t)a2 | (uintptr_t)out | (uintptr_t)resid | (uintptr_t)stat2 | (uintptr_t)partials) % 16 == 0,
+                   "pointers must be 16-byte aligned");
+    launch_merge_bn1(a1, BnJob{partials, n_partials, nullptr, gamma, beta, nullptr, nullptr, nullptr, stat1_out}, n_rows_total, eps, 0.f,
+                     a2, stat2, resid, n_nodes, out, static_cast<hipStream_t>(stream), nullptr);
     TGNN_CHECK_LAUNCH();
     return TGNN_OK;
 }

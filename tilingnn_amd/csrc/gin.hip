@@ -25,6 +25,7 @@
 
 #include "forward_persist.h"
 #include "gin32_plan.h"
+#include "nnconv_eg_plan.h"
 
 namespace tgnn {
 
@@ -34,8 +35,13 @@ namespace tgnn {
 // block; width 64: 16 lanes, 16 rows per block), rows of one XCD contiguous so that its private L2 holds the activations
 // its gathers touch; no LDS, few registers -> full occupancy hides the rowptr -> col_src -> a[src] dependent-load chain.
 // ------------------------------------------------------------------------------------------
+#ifdef TGNN_ABL_AGG8
+#define TGNN_AGG_BOUNDS __launch_bounds__(256, 8)           // (timing switch: 8 gathers in flight per lane group, still <= 64 registers)
+#else
+#define TGNN_AGG_BOUNDS __launch_bounds__(256)
+#endif
 template <int C>
-__global__ __launch_bounds__(256) void gin_aggregate_kernel(
+__global__ TGNN_AGG_BOUNDS void gin_aggregate_kernel(
     const float *__restrict__ a, int64_t lda, const float *__restrict__ in_stat, const int *__restrict__ rowptr,
     const int *__restrict__ col_src, const float *__restrict__ eps_p, int64_t n, float *__restrict__ z) {
     constexpr int LPR = C / 4, RPB = 256 / LPR;            // lanes per row, rows per block
@@ -60,17 +66,29 @@ __global__ __launch_bounds__(256) void gin_aggregate_kernel(
     const float4 self = *reinterpret_cast<const float4 *>(a + v * lda + 4 * q);
     float4 acc = make_float4(0, 0, 0, 0);
     int e = beg;
+#define TGNN_ACC(X)                          \
+    acc.x += ((X).x - mhi.x) - mlo.x;        \
+    acc.y += ((X).y - mhi.y) - mlo.y;        \
+    acc.z += ((X).z - mhi.z) - mlo.z;        \
+    acc.w += ((X).w - mhi.w) - mlo.w;
+#ifdef TGNN_ABL_AGG8
+    for (; e + 8 <= end; e += 8) {  // (timing switch) 8 independent gathers in flight, summed in edge order: the same bits
+        int sidx[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) sidx[u] = col_src[e + u];
+        float4 xx[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) xx[u] = *reinterpret_cast<const float4 *>(a + (int64_t)sidx[u] * lda + 4 * q);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { TGNN_ACC(xx[u]) }
+    }
+#endif
     for (; e + 4 <= end; e += 4) {  // 4 independent gathers in flight, summed in edge order
         const int s0 = col_src[e], s1 = col_src[e + 1], s2 = col_src[e + 2], s3 = col_src[e + 3];
         const float4 x0 = *reinterpret_cast<const float4 *>(a + (int64_t)s0 * lda + 4 * q);
         const float4 x1 = *reinterpret_cast<const float4 *>(a + (int64_t)s1 * lda + 4 * q);
         const float4 x2 = *reinterpret_cast<const float4 *>(a + (int64_t)s2 * lda + 4 * q);
         const float4 x3 = *reinterpret_cast<const float4 *>(a + (int64_t)s3 * lda + 4 * q);
-#define TGNN_ACC(X)                          \
-    acc.x += ((X).x - mhi.x) - mlo.x;        \
-    acc.y += ((X).y - mhi.y) - mlo.y;        \
-    acc.z += ((X).z - mhi.z) - mlo.z;        \
-    acc.w += ((X).w - mhi.w) - mlo.w;
         TGNN_ACC(x0) TGNN_ACC(x1) TGNN_ACC(x2) TGNN_ACC(x3)
     }
     for (; e < end; ++e) {
@@ -106,9 +124,15 @@ __global__ __launch_bounds__(256) void gin_aggregate_kernel(
 // the same chain register-resident in fp32 24.6 us (not the LDS traffic but matrix-pipe time and the 4-vs-3.05
 // tiles-per-SIMD quantisation of 32-row tiles were the cost); this one: see profiles/.
 // ------------------------------------------------------------------------------------------
-constexpr int kMlpWaves = 8, kMlpThreads = kMlpWaves * 64;
-static_assert(kGin32BlockRows == kGin32TileRows * kMlpWaves && kGin32MaxPartials == TGNN_BN_MAX_PARTIALS &&
-              kGin32ActLeakyRelu == TGNN_ACT_LEAKY_RELU, "gin32_plan.h restates these");
+// Two block shapes (template WAVES).  8 waves, two per SIMD, one block per 128 rows: the op (tgnn_gin32_fwd, tgnn_gin_fwd), the
+// training and the sharded forward.  4 waves, ONE per SIMD, one block per 64 rows -- twice the blocks, the same waves on the
+// device: the inference forward of the general schedule (gin32_fwd_folded), where a 4-wave block (1 x 232 registers per SIMD)
+// fits a CU beside a block of the adjacency chain's 8-wave merge (2 x 120): nnconv_eg_plan.h, kCoResidentPairs;
+// profiles/coresident_stage0.txt.  Same per-row arithmetic, same bits per row; the BatchNorm partial rows regroup (fp64).
+constexpr int kMlpWaves = 8, kMlpThreads = kMlpWaves * 64, kMlpHalfWaves = 4;
+static_assert(kGin32BlockRows == kGin32TileRows * kMlpWaves, "gin32_plan.h restates this");
+static_assert(kLayerFootprints[kLayerGinMlp].waves_per_block == kMlpHalfWaves, "nnconv_eg_plan.h states the forward's shape");
+static_assert(kGin32MaxPartials == TGNN_BN_MAX_PARTIALS && kGin32ActLeakyRelu == TGNN_ACT_LEAKY_RELU, "gin32_plan.h restates these");
 constexpr int kGinGroupRow0 = TGNN_BN_MAX_PARTIALS - 16;      // [r6] the 16 group rows of gin32_mlp_kernel's two-level BatchNorm fold
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
@@ -133,7 +157,8 @@ __device__ __forceinline__ f32x4 gin_mma6(const bf16x8 *wpl, int plane_stride, c
 
 // (2 waves per SIMD on purpose: the compiler then keeps all 30 weight fragments in registers, 232 VGPRs; with
 //  16 waves per block and 128 VGPRs the same code spills: 59.6 us)
-__global__ __launch_bounds__(kMlpThreads, 2) void gin32_mlp_kernel(
+template <int WAVES>
+__global__ __launch_bounds__(WAVES * 64, 2) void gin32_mlp_kernel(
     const float *__restrict__ z, const float *__restrict__ w1, const float *__restrict__ b1,
     const float *__restrict__ w2, const float *__restrict__ b2, const float *__restrict__ w3,
     const float *__restrict__ b3, int64_t n, int act, float *__restrict__ out, double *__restrict__ bn_partial, GinFin fin) {
@@ -142,7 +167,9 @@ __global__ __launch_bounds__(kMlpThreads, 2) void gin32_mlp_kernel(
     __shared__ bf16x8 W2s[3 * 4 * 64];          // K = 32 in kf order
     __shared__ bf16x8 W3s[3 * 2 * 2 * 64];      // [plane][M block][K step][..], K = 64 in kf order
     __shared__ __attribute__((aligned(16))) float Bs[128];   // b1 | b2 | b3
-    __shared__ double red[kMlpWaves * 64];
+    __shared__ double red[WAVES * 64];
+    static_assert(WAVES == kMlpWaves || WAVES == kMlpHalfWaves, "two waves of a SIMD split its slot's run, or one walks it");
+    constexpr int kMlpThreads = WAVES * 64, kMlpWaves = WAVES;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fn = lane & 15, fq = lane >> 4;
 #ifdef TGNN_ABL_EMPTYGIN
@@ -150,7 +177,8 @@ __global__ __launch_bounds__(kMlpThreads, 2) void gin32_mlp_kernel(
 #endif
 
     // ---- tile share of this wave (16-row tiles): balanced per SIMD (waves w, w + 4 of a block run on SIMD w & 3)
-    const Gin32Tiles share = gin32_wave_share(n, (int)gridDim.x, (int)blockIdx.x, wave);   // gin32_plan.h
+    const Gin32Tiles share = WAVES == 8 ? gin32_wave_share(n, (int)gridDim.x, (int)blockIdx.x, wave)    // gin32_plan.h
+                                        : gin32_slot_share(n, (int)gridDim.x, (int)blockIdx.x, wave);   // (one wave per SIMD)
     const int64_t t0 = share.t0, t1 = share.t1;
 
     // Z rows of a tile: lane (n, q) reads floats 8 q .. 8 q + 7 of row n; one tile ahead
@@ -799,11 +827,45 @@ extern "C" void tgnn_debug_set_block_caps(int32_t nnconv_blocks, int32_t gin_mlp
 namespace tgnn {
 // blocks of the MLP / fused kernels inside the forward: one per CU (the weight prologue is paid once per block), minus a few CUs left
 // to the other chain's small kernels (see launch_cols_t in nnconv_cols.hip), or what tgnn_debug_set_block_caps asks for
-static int gin32_grid(int64_t n_nodes) {
+static int gin32_cap() {
     constexpr int reserve = 32;
     int cap = cus_minus(reserve);
     if (const int dbg = g_debug_block_cap[1].load(); dbg > 0) cap = dbg < device_cus() ? dbg : device_cus();
-    return gin32_blocks(n_nodes, cap);                       // gin32_plan.h
+    return cap;
+}
+static int gin32_grid(int64_t n_nodes) { return gin32_blocks(n_nodes, gin32_cap()); }   // gin32_plan.h
+
+int gin32_func_attributes(int which, hipFuncAttributes *attr, int *waves) {
+    *waves = which == kLayerGinMlp ? kMlpHalfWaves : 4;
+    return (int)hipFuncGetAttributes(attr, which == kLayerGinMlp ? reinterpret_cast<const void *>(gin32_mlp_kernel<kMlpHalfWaves>)
+                                                                 : reinterpret_cast<const void *>(gin_aggregate_kernel<32>));
+}
+
+// gin32_mlp_kernel in 4-wave blocks (tgnn_set_gin_mlp_half_blocks): 0 nowhere, 1 (default) the inference forward of the general
+// schedule, 2 the op as well (tests)
+static std::atomic<int> g_gin_mlp_half{1};
+static bool gin32_half_blocks(bool forward) {
+#ifdef TGNN_ABL_GINMLPW8
+    return false;                                            // (timing switch: the 8-wave shape everywhere)
+#else
+    const int mode = g_gin_mlp_half.load(std::memory_order_relaxed);
+    return mode == 2 || (mode == 1 && forward);
+#endif
+}
+
+}  // namespace tgnn
+extern "C" int32_t tgnn_set_gin_mlp_half_blocks(int32_t mode) { return tgnn::g_gin_mlp_half.exchange(mode < 0 ? 0 : (mode > 2 ? 2 : mode)); }
+namespace tgnn {
+
+// blocks of gin32_mlp_kernel: gin32_plan.h, or -- 4-wave blocks -- one per 64 rows, twice as many, below the 16 group rows of the
+// two-level BatchNorm fold (kGinGroupRow0)
+static int gin32_mlp_grid(int64_t n_nodes, int cap, bool half) {
+    if (!half) return gin32_blocks(n_nodes, cap);
+    int64_t nb = (n_nodes + kGin32TileRows * kMlpHalfWaves - 1) / (kGin32TileRows * kMlpHalfWaves);
+    if (nb > 2 * (int64_t)cap) nb = 2 * (int64_t)cap;
+    if (nb > kGinGroupRow0) nb = kGinGroupRow0;
+    if (nb >= 8) nb &= ~int64_t(7);
+    return nb < 1 ? 1 : (int)nb;
 }
 
 static void launch_gin32_aggregate(const float *a, int64_t lda, const float *in_stat, const int32_t *rowptr, const int32_t *col_src,
@@ -816,9 +878,11 @@ static void launch_gin32_aggregate(const float *a, int64_t lda, const float *in_
 // the MLP on an aggregate z [N][32]: kGin32Bf16x3 (gin32_mlp_kernel) or kGin32F16 (gin32_mlp16_kernel, LeakyReLU only)
 static int launch_gin32_mlp_variant(Gin32Variant variant, const float *z, const float *w1, const float *b1, const float *w2, const float *b2,
                                     const float *w3, const float *b3, int64_t n_nodes, int32_t act, float *out, double *bn_partial,
-                                    int32_t *n_partials_host, hipStream_t s, const GinFin *fin) {
-    const int blocks = gin32_grid(n_nodes);
+                                    int32_t *n_partials_host, hipStream_t s, const GinFin *fin, bool forward = false) {
+    int blocks = gin32_grid(n_nodes);
     GinFin f{};
+    const bool half = gin32_half_blocks(forward);
+    if (variant != kGin32F16) blocks = gin32_mlp_grid(n_nodes, gin32_cap(), half);
     if (variant == kGin32F16) {
         // the inference forward's opt-in kernel: fp16 pairs in layers 2 / 3 (the kernel fills in the record's job itself)
         if (fin && bn_partial) f = *fin;
@@ -829,7 +893,8 @@ static int launch_gin32_mlp_variant(Gin32Variant variant, const float *z, const 
             f.job.partials = bn_partial;
             f.job.n_partials = blocks;
         }
-        gin32_mlp_kernel<<<blocks, kMlpThreads, 0, s>>>(z, w1, b1, w2, b2, w3, b3, n_nodes, act, out, bn_partial, f);
+        if (half) gin32_mlp_kernel<kMlpHalfWaves><<<blocks, kMlpHalfWaves * 64, 0, s>>>(z, w1, b1, w2, b2, w3, b3, n_nodes, act, out, bn_partial, f);
+        else gin32_mlp_kernel<kMlpWaves><<<blocks, kMlpThreads, 0, s>>>(z, w1, b1, w2, b2, w3, b3, n_nodes, act, out, bn_partial, f);
     }
     if (n_partials_host) *n_partials_host = blocks;
     TGNN_CHECK_LAUNCH();
@@ -841,7 +906,7 @@ static int launch_gin32_mlp_variant(Gin32Variant variant, const float *z, const 
 static int launch_gin32_variant(Gin32Variant variant, const float *a, int64_t lda, const float *in_stat, const int32_t *rowptr,
                                 const int32_t *col_src, const float *eps, const float *w1, const float *b1, const float *w2, const float *b2,
                                 const float *w3, const float *b3, int64_t n_nodes, int32_t act, float *out, float *z_scratch,
-                                double *bn_partial, int32_t *n_partials_host, const GinFin *fin, hipStream_t s) {
+                                double *bn_partial, int32_t *n_partials_host, const GinFin *fin, hipStream_t s, bool forward = false) {
     if (variant == kGin32Fused) {
         // one launch, no z round trip (gin32_fused_kernel)
         const int blocks = gin32_grid(n_nodes);
@@ -857,7 +922,7 @@ static int launch_gin32_variant(Gin32Variant variant, const float *a, int64_t ld
         return TGNN_OK;
     }
     launch_gin32_aggregate(a, lda, in_stat, rowptr, col_src, eps, n_nodes, z_scratch, s);
-    return launch_gin32_mlp_variant(variant, z_scratch, w1, b1, w2, b2, w3, b3, n_nodes, act, out, bn_partial, n_partials_host, s, fin);
+    return launch_gin32_mlp_variant(variant, z_scratch, w1, b1, w2, b2, w3, b3, n_nodes, act, out, bn_partial, n_partials_host, s, fin, forward);
 }
 
 int gin32_fwd_folded(const float *a, int64_t lda, const float *in_stat, const int32_t *rowptr, const int32_t *col_src, const float *eps,
@@ -874,7 +939,7 @@ int gin32_fwd_folded(const float *a, int64_t lda, const float *in_stat, const in
     const Gin32Variant variant = gin32_variant(need_z, lda, act, n_nodes, g_gin_fused.load(std::memory_order_relaxed),
                                                g_gin_mlp16.load(std::memory_order_relaxed));
     return launch_gin32_variant(variant, a, lda, in_stat, rowptr, col_src, eps, w1, b1, w2, b2, w3, b3, n_nodes, act, out, z_scratch, bn_partial,
-                                n_partials_host, &fin, s);
+                                n_partials_host, &fin, s, /*forward=*/!need_z);
 }
 }  // namespace tgnn
 
@@ -939,7 +1004,7 @@ extern "C" int tgnn_gin_fwd(const float *a, int64_t lda, const float *in_stat, c
         // prologue is paid once per block), minus a few CUs left to the other chain's small kernels (see launch_cols_t in
         // nnconv_cols.hip); the debug cap does not apply to this entry
         blocks = gin32_blocks(n_nodes, cus_minus(32));
-        gin32_mlp_kernel<<<blocks, kMlpThreads, 0, s>>>(z_scratch, w1, b1, w2, b2, w3, b3, n_nodes, act, out,
+        gin32_mlp_kernel<kMlpWaves><<<blocks, kMlpThreads, 0, s>>>(z_scratch, w1, b1, w2, b2, w3, b3, n_nodes, act, out,
                                                         bn_partial, GinFin{});
     } else {
         blocks = producer_blocks(n_nodes, 4);

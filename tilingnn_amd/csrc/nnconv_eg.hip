@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "tgnn_common.h"
+#include "nnconv_eg_plan.h"
 #include "split_pair_f16.h"
 
 namespace tgnn {
@@ -75,19 +76,10 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void nnconv32_eg_kernel(
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fj = lane & 15, fq = lane >> 4;
     constexpr int kThreads = WAVES * 64;
-    // ---- this wave's run of 16-row tiles (as nnconv_cols.hip: shares follow the XCD, the block, the SIMD)
-    static_assert(WAVES % 4 == 0, "whole SIMD quads");
-    // (32-bit arithmetic: a 64-bit division is ~150 instructions and this prologue is a fifth of a wave's vector work)
-    const uint32_t n_tiles = (uint32_t)((n + 15) / 16);
-    const uint32_t nblk = gridDim.x;
-    uint32_t blk = blockIdx.x;
-    if (nblk >= 8 && (nblk & 7) == 0) blk = (blockIdx.x & 7) * (nblk >> 3) + (blockIdx.x >> 3);
-    const uint32_t slot = blk * 4 + (wave & 3), n_slots = nblk * 4;
-    const uint32_t tq = n_tiles / n_slots, tr = n_tiles % n_slots;          // n_tiles * slot / n_slots without the wide product
-    const uint32_t q0 = tq * slot + tr * slot / n_slots, q1 = tq * (slot + 1) + tr * (slot + 1) / n_slots;
-    constexpr uint32_t kSubs = WAVES / 4;
-    const uint32_t sub = wave >> 2;
-    const int64_t t0 = q0 + (q1 - q0) * sub / kSubs, t1 = q0 + (q1 - q0) * (sub + 1) / kSubs;
+    // ---- this wave's run of 16-row tiles (nnconv_eg_plan.h: shares follow the XCD, the block, the SIMD, then the waves of a SIMD)
+    static_assert(WAVES % kEgSimds == 0, "whole SIMD quads");
+    const EgTiles share = nnconv_eg_wave_share(nnconv_eg_n_tiles(n), gridDim.x, blockIdx.x, (uint32_t)wave, WAVES);
+    const int64_t t0 = share.t0, t1 = share.t1;
     const int cbeg = __builtin_amdgcn_readfirstlane(tile_grp_ptr[t0]);
     const int cend = __builtin_amdgcn_readfirstlane(tile_grp_ptr[t1]);
 
@@ -439,20 +431,33 @@ static size_t eg_lds_bytes(int n_types, int waves) {
 
 constexpr size_t kEgMaxLds = 160 * 1024 - 256;
 
+// Block shape (nnconv_eg_plan.h: kLayerFootprints).  Timing switches of the co-residency study (profiles/coresident_stage0.txt):
+#if defined(TGNN_ABL_EGW8)                                  // two 8-wave blocks per CU instead of one 16-wave block
+constexpr int kEgWaves = 8, kEgOcc = 4, kEgBlocksPerCu = 2;
+#elif defined(TGNN_ABL_EGW12)                               // 3 waves per SIMD x 128 registers: 128 left to the other chain
+constexpr int kEgWaves = 12, kEgOcc = 4, kEgBlocksPerCu = 1;
+#elif defined(TGNN_ABL_EGW16C96)                            // 4 waves per SIMD capped at 96 registers (spills: 124 bytes of scratch)
+constexpr int kEgWaves = 16, kEgOcc = 5, kEgBlocksPerCu = 1;
+#else
+constexpr int kEgWaves = kLayerFootprints[kLayerNnconvEg].waves_per_block, kEgOcc = kSimdVgprs / kLayerFootprints[kLayerNnconvEg].vgpr_cap;
+constexpr int kEgBlocksPerCu = 1;
+#endif
+
+int nnconv_eg_func_attributes(hipFuncAttributes *attr, int *waves) {
+    *waves = kEgWaves;
+    return (int)hipFuncGetAttributes(attr, reinterpret_cast<const void *>(nnconv32_eg_kernel<kEgWaves, kEgOcc, TGNN_ACT_LEAKY_RELU>));
+}
+
 int launch_nnconv_eg(const float *h, const int32_t *tile_grp_ptr, const int32_t *grp, const float *wimg, int32_t n_types, const float *bias, int64_t n_nodes, int32_t act, float *out,
                      double *bn_partial, int32_t *n_partials_host, hipStream_t s, const unsigned *h_max, const unsigned *root_max,
                      unsigned long long *stamp, const EgShardPack *pack, const float *sum_root_rows) {
-#ifdef TGNN_ABL_EGW8                                        // (ablation: two 8-wave blocks per CU instead of one 16-wave block)
-    constexpr int WAVES = 8, kBlocksPerCu = 2;
-#else
-    constexpr int WAVES = 16, kBlocksPerCu = 1;
-#endif
+    constexpr int WAVES = kEgWaves, OCC = kEgOcc, kBlocksPerCu = kEgBlocksPerCu;
     const bool leaky = act == TGNN_ACT_LEAKY_RELU;
     const bool shard = pack && pack->counter && bn_partial && leaky;
     const bool sum = sum_root_rows != nullptr;               // (the adjoint's form: act, bias, bn_partial and pack are not read)
-    auto kern = sum     ? nnconv32_eg_kernel<WAVES, 4, TGNN_ACT_NONE, false, true>
-                : shard ? nnconv32_eg_kernel<WAVES, 4, TGNN_ACT_LEAKY_RELU, true>
-                        : leaky ? nnconv32_eg_kernel<WAVES, 4, TGNN_ACT_LEAKY_RELU> : nnconv32_eg_kernel<WAVES, 4, TGNN_ACT_NONE>;
+    auto kern = sum     ? nnconv32_eg_kernel<WAVES, OCC, TGNN_ACT_NONE, false, true>
+                : shard ? nnconv32_eg_kernel<WAVES, OCC, TGNN_ACT_LEAKY_RELU, true>
+                        : leaky ? nnconv32_eg_kernel<WAVES, OCC, TGNN_ACT_LEAKY_RELU> : nnconv32_eg_kernel<WAVES, OCC, TGNN_ACT_NONE>;
     static LdsOptIn site[4];
     TGNN_CHECK_HIP(opt_in_dynamic_lds(kern, (int)kEgMaxLds, site[sum ? 3 : shard ? 2 : leaky]));
     if (sum) {
@@ -461,15 +466,16 @@ int launch_nnconv_eg(const float *h, const int32_t *tile_grp_ptr, const int32_t 
     }
     EgShard sh{};
     if (shard) sh = EgShard{pack->send_row_ptr, pack->send_row_slot, pack->msg, pack->msg_idx, pack->n_msg, pack->sums, pack->counter, pack->group_rows};
-    const int64_t n_tiles = (n_nodes + 15) / 16;
-    constexpr int tiles_per_block = 4;
-    int64_t blocks = (n_tiles + tiles_per_block - 1) / tiles_per_block;
-    constexpr int reserve = 32;                              // (CUs left to the collision chain: nnconv_cols.hip)
+#ifdef TGNN_ABL_EGRES0
+    constexpr int reserve = 0;                               // (timing switch: every CU)
+#else
+    // (CUs left to the collision chain: nnconv_cols.hip.  Re-measured with 12-wave blocks, which leave the aggregate room on
+    //  every CU: reserve 0 is still 2.7 % slower than reserve 32 in the step, profiles/coresident_stage0.txt)
+    constexpr int reserve = 32;
+#endif
     int64_t cap = (int64_t)cus_minus(reserve) * kBlocksPerCu;
     if (const int dbg = g_debug_block_cap[0].load(); dbg > 0) cap = dbg < device_cus() ? dbg : device_cus();
-    if (blocks > cap) blocks = cap;
-    if (blocks >= 8) blocks &= ~7;
-    if (blocks < 1) blocks = 1;
+    const int blocks = nnconv_eg_blocks(n_nodes, cap);       // nnconv_eg_plan.h
     kern<<<(unsigned)blocks, WAVES * 64, eg_lds_bytes(n_types, WAVES), s>>>(h, tile_grp_ptr, reinterpret_cast<const int2 *>(grp), wimg,
                                                                             n_types, bias, n_nodes, act, out, bn_partial, h_max, root_max,
                                                                             stamp, sh);
@@ -481,6 +487,31 @@ int launch_nnconv_eg(const float *h, const int32_t *tile_grp_ptr, const int32_t 
 }  // namespace tgnn
 
 using namespace tgnn;
+
+extern "C" int tgnn_kernel_footprint(int32_t kernel, int32_t n_types, int32_t *out) {
+    TGNN_CHECK_ARG(kernel >= 0 && kernel < kLayerKernels && out && n_types >= 0, "kernel index / null pointer");
+    hipFuncAttributes attr{};
+    int waves = 0, dyn_lds = 0, rc = 0;
+    switch (kernel) {
+    case kLayerNnconvEg:
+        rc = nnconv_eg_func_attributes(&attr, &waves);
+        dyn_lds = (int)eg_lds_bytes(n_types, waves);
+        break;
+    case kLayerMerge: rc = merge_wide_func_attributes(&attr, &waves); break;
+    default: rc = gin32_func_attributes(kernel, &attr, &waves); break;
+    }
+    if (rc != 0) {
+        set_error("tgnn_kernel_footprint: hipFuncGetAttributes failed (%d)", rc);
+        return TGNN_ERR_LAUNCH;
+    }
+    out[0] = waves;                                          // waves of a block as the general schedule launches it
+    out[1] = (waves + kEgSimds - 1) / kEgSimds;              // ... of them on one SIMD
+    out[2] = kLayerFootprints[kernel].vgpr_cap;              // what __launch_bounds__ pins the kernel to (nnconv_eg_plan.h)
+    out[3] = attr.numRegs;                                   // what the runtime reports for the code object that is loaded
+    out[4] = (int32_t)attr.sharedSizeBytes + dyn_lds;        // LDS of a block, static + dynamic at n_types edge types
+    out[5] = attr.maxThreadsPerBlock;
+    return TGNN_OK;
+}
 
 extern "C" int tgnn_nnconv_mean_eg_fwd(const float *h, int64_t ldh, int64_t n_src_rows, const int32_t *tile_grp_ptr,
                                        const int32_t *grp, const float *wtab, int32_t n_types,

@@ -539,6 +539,11 @@ struct EgShardPack {
 int launch_nnconv_eg(const float *h, const int32_t *tile_grp_ptr, const int32_t *grp, const float *wimg, int32_t n_types, const float *bias, int64_t n_nodes, int32_t act, float *out,
                      double *bn_partial, int32_t *n_partials_host, hipStream_t s, const unsigned *h_max, const unsigned *root_max,
                      unsigned long long *stamp = nullptr, const EgShardPack *pack = nullptr, const float *sum_root_rows = nullptr);
+// hipFuncGetAttributes of a layer kernel of the general schedule and the waves of its block (tgnn_kernel_footprint, nnconv_eg.hip);
+// `which`: kLayerGinAggregate / kLayerGinMlp (nnconv_eg_plan.h)
+int nnconv_eg_func_attributes(hipFuncAttributes *attr, int *waves);
+int gin32_func_attributes(int which, hipFuncAttributes *attr, int *waves);
+int merge_wide_func_attributes(hipFuncAttributes *attr, int *waves);
 // (sum_root_rows given: the SUM form of the kernel -- edge sums instead of means, no bias / activation / BatchNorm partials, the
 //  root group's rows read from sum_root_rows [N][32]: the input gradient of the adjoint, nnconv_bwd_eg.hip)
 // largest |h[0 .. n_floats)| (n_floats % 4 == 0) as float bits, atomicMax into *max_bits; bn_merge.hip
