@@ -293,6 +293,53 @@ def test_error_bits_index_and_wedge_overflow():
         od.union_topology(torch.ones(17, dtype=torch.int32, device=DEV))
 
 
+# ------------------------------------------------------------------------------------------------ the longest way for a label
+CHAIN = 193                                                                 # one more than three waves of 64 lanes
+# tile index by position along the chain, the lowest index at position 0.  "descending": the indices fall by one per step
+# towards it, the slowest a permutation can (every tile's first label points one step on, and the walk to the root is as long
+# as the chain).  "against": past position 0 they RISE towards it, so every tile first joins the far end's tile 1 and the
+# label 0 comes one position per round, the most rounds a chain can take.
+CHAIN_ORDERS = {"descending": np.arange(CHAIN), "against": np.concatenate([[0], np.arange(CHAIN - 1, 0, -1)])}
+
+
+@pytest.mark.parametrize("order", sorted(CHAIN_ORDERS))
+def test_chain_of_squares_through_the_three_calls(order):
+    """193 unit squares end to end, all alive / the middle one dead / every second one dead, through union_topology,
+    union_contours and hole_deltas: the three kernels that label components must agree on a label that has the whole chain to
+    travel, and give the same bytes on a second call."""
+    from tilingnn_amd.tiling.region import contact_geometry, union_geometry
+    from tilingnn_amd.util.data_util import CompleteGraphOnDevice
+    index = CHAIN_ORDERS[order]
+    assert sorted(index.tolist()) == list(range(CHAIN)) and index[0] == 0
+    place = np.argsort(index)                                               # position of tile t
+    tiles = [_box(p, 0, p + 1, 1) for p in place.tolist()]
+    geo = union_geometry(tiles, np.zeros((2, 0), dtype=np.int64), CHAIN)
+    od = CompleteGraphOnDevice.__new__(CompleteGraphOnDevice)
+    od.device, od.n_tiles = torch.device(DEV), CHAIN
+    up = lambda a: torch.from_numpy(a if a.size else np.zeros(1, dtype=a.dtype)).to(DEV)
+    od._union = tuple(up(a) for a in geo)
+    od._topology = tuple(up(a) for a in contact_geometry(geo[0], geo[1])) + (math.cos(0.1234), math.sin(0.1234))
+    here = np.arange(CHAIN)
+    by_place = np.stack([np.ones(CHAIN, dtype=bool), here != CHAIN // 2, here % 2 == 0])
+    masks = np.zeros((3, CHAIN), dtype=np.int32)
+    masks[:, index] = by_place
+    assert masks.sum(axis=1).tolist() == [193, 192, 97]
+    alive = torch.from_numpy(masks).to(DEV)
+
+    def run():
+        topo = od.union_topology(alive)
+        rings = od.union_contours(alive)
+        delta, state = od.hole_deltas(alive)
+        return [t.cpu().numpy() for t in (topo, rings.mask, rings.ring, rings.ring_area, rings.pts_xy, rings.pts_src, delta, state)]
+    first, again = run(), run()
+    topo, ring_mask, delta, state = first[0], first[1], first[6], first[7]
+    assert topo.tolist() == [[1, 0, 0], [2, 0, 0], [97, 0, 0]]
+    assert ring_mask[:, 0].tolist() == [1, 2, 97] and (ring_mask[:, 3] == 0).all()
+    middle = int(index[CHAIN // 2])
+    assert masks[1, middle] == 0 and delta[1, middle].tolist() == [-1, 0] and state[1, middle] == 0
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(first, again))
+
+
 # ------------------------------------------------------------------------------------------------ BrickLayout
 def _solved_layout(fx, selection, seed):
     """A layout cut from the complete graph around `selection` (the selected tiles and a random half of the others), with

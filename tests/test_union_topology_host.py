@@ -1,7 +1,7 @@
 """Host side of the union topology (csrc/union_topology.hip): the loop-tracing oracle of tests/topology_oracle.py against counts
 worked out by hand and on the lattice fixtures, the contact relation against an all-pairs brute force, the sweep-direction
-picker, the kernel's per-vertex code (csrc/union_topology_point.h) run on the host under sanitizers, and the refusal to run
-without a GPU.  The GPU tests (tests/test_union_topology_gpu.py) lean on every one of these."""
+picker, the kernel's per-vertex code (csrc/union_topology_point.h) and the steps the union kernels share
+(csrc/union_components.h) run on the host under sanitizers, and the refusal to run without a GPU.  The GPU tests (tests/test_union_topology_gpu.py) lean on every one of these."""
 import gzip
 import math
 import os
@@ -177,26 +177,37 @@ def test_side_directions_too_close_are_refused():
 
 
 # ------------------------------------------------------------------------------------------------ the kernel's local term
-@pytest.fixture(scope="module")
-def point_program(tmp_path_factory):
-    """tests/host/union_topology_point_test.cpp: the header the kernel runs per vertex, built with the host compiler alone under
-    AddressSanitizer + UBSan (the sanitizers' runtime linked into the program itself)."""
+def _build_host_program(tmp_path_factory, name):
+    """tests/host/<name>.cpp built with the host compiler alone under AddressSanitizer + UBSan (the sanitizers' runtime linked
+    into the program itself)."""
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     assert cxx, "no host C++ compiler"
     clang = "clang" in subprocess.run([cxx, "--version"], capture_output=True, text=True).stdout
     static_rt = ["-static-libsan"] if clang else ["-static-libasan", "-static-libubsan"]
-    exe = str(tmp_path_factory.mktemp("topo_point") / "union_topology_point_test")
+    exe = str(tmp_path_factory.mktemp(name) / name)
     build = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
                             "-fno-sanitize-recover=undefined", *static_rt, "-I", os.path.join(repo, "tilingnn_amd", "csrc"),
-                            os.path.join(repo, "tests", "host", "union_topology_point_test.cpp"), "-o", exe],
+                            os.path.join(repo, "tests", "host", name + ".cpp"), "-o", exe],
                            capture_output=True, text=True)
     assert build.returncode == 0, build.stderr[-4000:]
     return exe
 
 
-def _host_topology(exe, tmp_path, tiles, masks):
-    """[(components, holes)] per mask: chi from the host program, components by a union-find over the contact rows."""
+@pytest.fixture(scope="module")
+def point_program(tmp_path_factory):
+    """tests/host/union_topology_point_test.cpp: the header the kernel runs per vertex."""
+    return _build_host_program(tmp_path_factory, "union_topology_point_test")
+
+
+@pytest.fixture(scope="module")
+def components_program(tmp_path_factory):
+    """tests/host/union_components_test.cpp: the collision-row test and the labelling step the union kernels share."""
+    return _build_host_program(tmp_path_factory, "union_components_test")
+
+
+def _run_on_case(exe, tmp_path, tiles, masks):
+    """Writes tiles, contact rows and masks to a file, runs the host program on it; (output words, masks, touch_ptr, touch_idx)."""
     from tilingnn_amd.tiling.region import UNION_TOL, contact_geometry, sweep_direction, union_geometry
     n = len(tiles)
     ring_xy, ring_ptr, _, _ = union_geometry(tiles, np.zeros((2, 0), dtype=np.int64), n)
@@ -211,24 +222,34 @@ def _host_topology(exe, tmp_path, tiles, masks):
             f.write(np.ascontiguousarray(a).tobytes())
     run = subprocess.run([exe, path], capture_output=True, text=True)
     assert run.returncode == 0, (run.stdout + run.stderr)[-4000:]
-    lines = run.stdout.split()
+    return run.stdout.split(), masks, touch_ptr, touch_idx
+
+
+def _components(m, touch_ptr, touch_idx):
+    """The components of mask m by a union-find over the contact rows."""
+    parent = list(range(m.shape[0]))
+
+    def find(a):
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        return a
+    for i in np.flatnonzero(m):
+        for j in touch_idx[touch_ptr[i]:touch_ptr[i + 1]]:
+            if m[j]:
+                parent[find(i)] = find(int(j))
+    return len({find(i) for i in np.flatnonzero(m)})
+
+
+def _host_topology(exe, tmp_path, tiles, masks):
+    """[(components, holes)] per mask: chi from the host program, components by a union-find over the contact rows."""
+    lines, masks, touch_ptr, touch_idx = _run_on_case(exe, tmp_path, tiles, masks)
     assert lines[-2:] == ["err", "0"], lines[-2:]
     chi = [int(v) for v in lines[:-2]]
     assert len(chi) == masks.shape[0]
     out = []
     for m, c in zip(masks, chi):
-        parent = list(range(n))
-
-        def find(a):
-            while parent[a] != a:
-                parent[a] = parent[parent[a]]
-                a = parent[a]
-            return a
-        for i in np.flatnonzero(m):
-            for j in touch_idx[touch_ptr[i]:touch_ptr[i + 1]]:
-                if m[j]:
-                    parent[find(i)] = find(int(j))
-        comps = len({find(i) for i in np.flatnonzero(m)})
+        comps = _components(m, touch_ptr, touch_idx)
         out.append((comps, comps - c))
     return out
 
@@ -247,6 +268,53 @@ def test_local_euler_terms_on_the_host_lattice(which, graphs, point_program, tmp
     holes = to.QUOTED[(which, "independent")][0] + to.QUOTED[(which, "thinned")][0]
     comps = to.QUOTED[(which, "independent")][1] + to.QUOTED[(which, "thinned")][1]
     assert _host_topology(point_program, tmp_path, rings, masks) == list(zip(comps, holes))
+
+
+# ------------------------------------------------------------------------------------------------ the kernels' shared steps
+def _host_labelling(exe, tmp_path, tiles, masks):
+    """Runs tests/host/union_components_test.cpp; checks the component count of every mask against the union-find and the number
+    of sweeps against the round cap of the kernels (n_tiles + 1).  Returns the sweep counts and the program's `collides` lines."""
+    lines, masks, touch_ptr, touch_idx = _run_on_case(exe, tmp_path, tiles, masks)
+    k, n = masks.shape
+    assert lines[2 * k:2 * k + 2] == ["err", "0"], lines[2 * k:2 * k + 2]
+    comps, sweeps = [int(v) for v in lines[0:2 * k:2]], [int(v) for v in lines[1:2 * k:2]]
+    assert comps == [_components(m, touch_ptr, touch_idx) for m in masks]
+    assert all(1 <= s <= n + 1 for s in sweeps), (max(sweeps), n)
+    rest = lines[2 * k + 2:]
+    assert len(rest) % 6 == 0 and set(rest[0::6]) == {"collides"}
+    return sweeps, [tuple(int(v) for v in rest[q + 1:q + 6]) for q in range(0, len(rest), 6)]
+
+
+def test_labelling_step_on_the_host_hand_sets(components_program, tmp_path):
+    for name, (tiles, want) in to.hand_sets().items():
+        n = len(tiles)
+        subsets = ((np.arange(2 ** n)[:, None] >> np.arange(n)[None, :]) & 1).astype(np.int32)
+        _host_labelling(components_program, tmp_path, tiles, subsets)
+        lines, _, _, _ = _run_on_case(components_program, tmp_path, tiles, [np.ones(n)])
+        assert int(lines[0]) == want[0], name                               # all tiles: the count worked out by hand
+
+
+@pytest.mark.parametrize("which", ["small", "ring9"])
+def test_labelling_step_on_the_host_lattice(which, graphs, components_program, tmp_path):
+    g = graphs[which]
+    rings, col = _rings(g), g.arrays.colli_edges
+    masks = [make(len(rings), col, seed) for make in (to.independent_set, to.thinned_set) for seed in to.SEEDS]
+    masks += [np.ones(len(rings)), np.zeros(len(rings))]                     # (labelling does not ask whether tiles overlap)
+    sweeps, _ = _host_labelling(components_program, tmp_path, rings, masks)
+    print(f"\nunion_components {which}: sweeps per mask {sweeps} (cap {len(rings) + 1})")
+    assert sweeps[-1] == 1 and max(sweeps) >= 2
+
+
+def test_collision_row_test_on_the_host(components_program, tmp_path):
+    """`collides` on the program's own four rows {1, 2^31 - 1}, {0, -1}, {2}, {2} with tile 1 dead: (row, first, stride, answer,
+    error word).  An entry out of range sets the index bit and is passed over; the row's own tile and a dead tile do not count;
+    with stride 2 a call sees every second entry only."""
+    tri = np.array([[0, 0], [1, 0], [0, 1]], dtype=float)
+    _, got = _host_labelling(components_program, tmp_path, [tri], [np.ones(1)])
+    assert got == [(0, 0, 1, 0, 1), (0, 0, 2, 0, 0), (0, 1, 2, 0, 1),
+                   (1, 0, 1, 1, 1), (1, 0, 2, 1, 0), (1, 1, 2, 0, 1),
+                   (2, 0, 1, 0, 0), (2, 0, 2, 0, 0), (2, 1, 2, 0, 0),
+                   (3, 0, 1, 1, 0), (3, 0, 2, 1, 0), (3, 1, 2, 0, 0)]
 
 
 # ------------------------------------------------------------------------------------------------ no GPU, no answer

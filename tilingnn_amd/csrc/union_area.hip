@@ -35,7 +35,7 @@
 // [slot][thread] (conflict free), 5 blocks per CU.  union_area_fold_kernel: one block per mask adds the alive tiles' three
 // partials in a fixed order (thread t takes tiles t, t + 256, ...; then a fixed LDS tree): the same bits on every run, no
 // floating-point atomics.  The two kernels follow each other on the stream; nothing returns to the host.
-#include "tgnn_common.h"
+#include "union_masks.h"
 
 namespace tgnn {
 
@@ -241,8 +241,6 @@ __global__ __launch_bounds__(kUaThreads) void union_area_fold_kernel(UnionArgs a
 
 using namespace tgnn;
 
-static constexpr int64_t kUaMaxGridY = 65535;
-
 extern "C" size_t tgnn_union_area_workspace_bytes(int64_t n_masks, int64_t n_tiles) {
     if (n_masks <= 0 || n_tiles <= 0 || n_masks > (1ll << 58) / n_tiles) return 0;
     return (size_t)3 * (size_t)n_masks * (size_t)n_tiles * sizeof(double);
@@ -252,8 +250,7 @@ extern "C" int tgnn_union_area(const double *ring_xy, const int32_t *ring_ptr, i
                                const int32_t *col_idx, const int32_t *alive, int64_t n_masks, double tol, double *area_out,
                                int32_t *err_flag, void *ws, size_t ws_bytes, tgnn_stream_t stream) {
     DeviceGuard guard__(stream);
-    TGNN_CHECK_ARG(n_tiles >= 0 && n_tiles < (1ll << 31) - 1 && n_masks >= 0, "shape");
-    TGNN_CHECK_ARG(tol >= 0.0, "tol");                       // (false for a NaN too)
+    if (int rc = check_mask_shape(__func__, n_tiles, n_masks, tol, 1.0, 0.0)) return rc;
     if (n_masks == 0) return TGNN_OK;
     TGNN_CHECK_ARG(area_out && err_flag, "null area_out / err_flag");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -261,22 +258,16 @@ extern "C" int tgnn_union_area(const double *ring_xy, const int32_t *ring_ptr, i
         TGNN_CHECK_HIP(hipMemsetAsync(area_out, 0, sizeof(double) * n_masks, s));
         return TGNN_OK;
     }
-    TGNN_CHECK_ARG(n_masks <= (1ll << 58) / n_tiles, "K * n_tiles overflows");
-    TGNN_CHECK_ARG(ring_xy && ring_ptr && col_ptr && alive, "null tile array");      // (col_idx may be NULL: no collision edge)
-    TGNN_CHECK_ARG(ws && ws_bytes >= tgnn_union_area_workspace_bytes(n_masks, n_tiles), "workspace too small");
-    TGNN_CHECK_ARG(reinterpret_cast<uintptr_t>(ws) % sizeof(double) == 0, "workspace alignment");
+    if (int rc = check_mask_arrays(__func__, n_masks, (1ll << 58) / n_tiles, ring_xy && ring_ptr && col_ptr && alive, ws, ws_bytes,
+                                   tgnn_union_area_workspace_bytes(n_masks, n_tiles), sizeof(double)))
+        return rc;
     UnionArgs a{reinterpret_cast<const double2 *>(ring_xy), ring_ptr, n_tiles, col_ptr, col_idx, alive, n_masks, tol,
                 static_cast<double *>(ws), area_out, err_flag};
     const unsigned gx = (unsigned)((n_tiles + kUaThreads - 1) / kUaThreads);
-    for (int64_t k0 = 0; k0 < n_masks; k0 += kUaMaxGridY) {
-        const unsigned gy = (unsigned)(n_masks - k0 < kUaMaxGridY ? n_masks - k0 : kUaMaxGridY);
+    for_mask_chunks(n_masks, kMaskGridY, [&](int64_t k0, unsigned gy) {
         union_area_tiles_kernel<<<dim3(gx, gy), kUaThreads, 0, s>>>(a, k0);
-    }
-    constexpr int64_t kMaxGridX = 1ll << 30;
-    for (int64_t k0 = 0; k0 < n_masks; k0 += kMaxGridX) {
-        const unsigned g = (unsigned)(n_masks - k0 < kMaxGridX ? n_masks - k0 : kMaxGridX);
-        union_area_fold_kernel<<<g, kUaThreads, 0, s>>>(a, k0);
-    }
+    });
+    for_mask_chunks(n_masks, kMaskGridX, [&](int64_t k0, unsigned g) { union_area_fold_kernel<<<g, kUaThreads, 0, s>>>(a, k0); });
     TGNN_CHECK_LAUNCH();
     return TGNN_OK;
 }

@@ -10,7 +10,7 @@
 //                                 time): the collision row (status 1 when two alive tiles collide), the number of boundary
 //                                 pieces of the tile (union_contour_piece.h: tile_pieces); an exclusive block scan in tile
 //                                 order gives every tile its first piece, so piece indices do not depend on scheduling; the
-//                                 component labels by the min-label propagation of union_topology_fold_kernel, in the workspace.
+//                                 component labels by label_components of union_masks.h, in the workspace.
 //   union_contour_offsets_kernel  one block: exclusive scan of the K piece counts (int64), where each mask's pieces live.
 //   union_contour_trace_kernel    one block per mask.  Fill (a thread per tile writes its pieces), link (a thread per piece
 //                                 writes its successor), a check that the successor relation is a permutation (in-degrees, integer
@@ -22,7 +22,7 @@
 //   union_contour_emit_kernel     one block per mask, one thread per ring: walks the ring from its leader (at most `pieces`
 //                                 steps), writes the surviving points, and sums the fp64 shoelace about the ring's first point in
 //                                 listed order: no floating-point atomics anywhere, the same bits on every call.
-#include "tgnn_common.h"
+#include "union_masks.h"
 #include "union_contour_piece.h"
 
 namespace tgnn {
@@ -32,10 +32,8 @@ constexpr int kLdsPieces = 3072;             // 4 arrays x 4 B x 3 072 = 48 KB o
 constexpr int kListTiles = 2048;             // tiles per chunk of the alive-tile lists (8 KB of LDS)
 constexpr int kPieceWords = 13;              // int32 words of workspace per piece
 
-struct ContourArgs {
-    topo::Tiles g;
-    const int32_t *col_ptr, *col_idx, *alive;
-    int64_t n_masks, cap_pieces, cap_rings, cap_points;
+struct ContourArgs : MaskSet {
+    int64_t cap_pieces, cap_rings, cap_points;
     // workspace
     int64_t *piece_off, *ring_off, *point_off;               // [K]
     int32_t *status, *m_pieces, *m_rings, *m_points;         // [K]
@@ -47,8 +45,8 @@ struct ContourArgs {
     double *ring_area, *pts_xy;
     int32_t *pts_src;
     int64_t *total_out;
-    int32_t *err_flag;
 };
+static_assert(contour::kErrIndex == topo::kErrIndex, "topo::collides reports into the contour error word");
 
 // Exclusive scan of a[0 .. n) in place, in index order, by the whole block; returns the total (uniform).  tmp: kUcThreads words.
 template <class T>
@@ -119,16 +117,7 @@ __global__ __launch_bounds__(kUcThreads) void union_contour_prep_kernel(ContourA
         for (int w = tid; w < n_list; w += kUcThreads) {
             const int64_t i = c0 + list[w];
             CountSink sink{0};
-            bool hit = false;
-            for (int cc = a.col_ptr[i]; cc < a.col_ptr[i + 1]; ++cc) {
-                const int64_t j = a.col_idx[cc];
-                if (j < 0 || j >= n) {
-                    err |= contour::kErrIndex;
-                    continue;
-                }
-                hit |= j != i && al[j] != 0;
-            }
-            if (hit) collide = 1;
+            if (topo::collides(a.col_ptr, a.col_idx, al, i, n, 0, 1, err)) collide = 1;
             else contour::tile_pieces(a.g, al, i, sp, err, sink);
             first[i] = sink.n;
         }
@@ -142,36 +131,9 @@ __global__ __launch_bounds__(kUcThreads) void union_contour_prep_kernel(ContourA
         a.status[k] = bad ? 1 : 0;
         a.m_pieces[k] = bad ? 0 : pieces;
     }
-    // component labels: union_topology_fold_kernel's loop on labels in the workspace; a round lowers a label or is the last
-    for (int64_t round = 0; round <= n; ++round) {
-        __syncthreads();
-        if (tid == 0) changed = 0;
-        __syncthreads();
-        bool any = false;
-        for (int64_t i = tid; i < n; i += kUcThreads) {
-            const int32_t old = lab[i];
-            if (old < 0) continue;
-            int32_t best = old;
-            for (int cc = a.g.touch_ptr[i]; cc < a.g.touch_ptr[i + 1]; ++cc) {
-                const int64_t j = a.g.touch_idx[cc];
-                if (j < 0 || j >= n) continue;               // (reported by tile_pieces)
-                const int32_t lj = lab[j];
-                best = lj >= 0 && lj < best ? lj : best;
-            }
-            for (;;) {                                       // pointer jumping: labels strictly decrease along it
-                const int32_t up = lab[best];
-                if (up >= best) break;
-                best = up;
-            }
-            if (best < old) {
-                lab[i] = best;
-                any = true;
-            }
-        }
-        if (any) changed = 1;
-        __syncthreads();
-        if (changed == 0) break;
-    }
+    // component labels, in the workspace (there is no LDS to spare for them here)
+    int ignored = 0;                                         // (a bad contact index is tile_pieces' to report, not the labelling's)
+    label_components<kUcThreads, false>(a.g, lab, nullptr, nullptr, &changed, ignored);
     if (err != 0) atomicOr(a.err_flag, err);
 }
 
@@ -394,8 +356,8 @@ extern "C" int tgnn_union_contour(const double *ring_xy, const int32_t *ring_ptr
                                   int32_t *mask_out, int32_t *ring_out, double *ring_area, double *pts_xy, int32_t *pts_src,
                                   int64_t *total_out, int32_t *err_flag, void *ws, size_t ws_bytes, tgnn_stream_t stream) {
     DeviceGuard guard__(stream);
-    TGNN_CHECK_ARG(n_tiles >= 0 && n_tiles < (1ll << 31) - 1 && n_masks >= 0 && n_masks < (1ll << 31) - 1, "shape");
-    TGNN_CHECK_ARG(tol >= 0.0, "tol");                       // (false for a NaN too)
+    TGNN_CHECK_ARG(n_masks < (1ll << 31) - 1, "shape");      // (a block per mask, no chunks)
+    if (int rc = check_mask_shape(__func__, n_tiles, n_masks, tol, 1.0, 0.0)) return rc;
     TGNN_CHECK_ARG(cap_rings >= 0 && cap_points >= 0 && cap_rings < (1ll << 31) && cap_points < (1ll << 31), "capacity");
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (n_masks == 0 || n_tiles == 0) {
@@ -409,12 +371,10 @@ extern "C" int tgnn_union_contour(const double *ring_xy, const int32_t *ring_ptr
     TGNN_CHECK_ARG(mask_out && total_out && err_flag, "null mask_out / total_out / err_flag");
     TGNN_CHECK_ARG((ring_out && ring_area) || cap_rings == 0, "null ring_out / ring_area");
     TGNN_CHECK_ARG((pts_xy && pts_src) || cap_points == 0, "null pts_xy / pts_src");
-    TGNN_CHECK_ARG(n_masks <= (1ll << 56) / (n_tiles + 4), "K * n_tiles overflows");
-    // (col_idx / touch_idx may be NULL: no collision edge / no contact)
-    TGNN_CHECK_ARG(ring_xy && ring_ptr && col_ptr && touch_ptr && alive, "null tile array");
-    const size_t fixed = align_up(contour_fixed_bytes(n_masks, n_tiles), 8);
-    TGNN_CHECK_ARG(ws && ws_bytes >= fixed, "workspace too small");
-    TGNN_CHECK_ARG(reinterpret_cast<uintptr_t>(ws) % sizeof(int64_t) == 0, "workspace alignment");
+    const size_t fixed = align_up(contour_fixed_bytes(n_masks, n_tiles), 8);     // (any value when K * n_tiles overflows: not used then)
+    if (int rc = check_mask_arrays(__func__, n_masks, (1ll << 56) / (n_tiles + 4), ring_xy && ring_ptr && col_ptr && touch_ptr && alive,
+                                   ws, ws_bytes, fixed, sizeof(int64_t)))
+        return rc;
     ContourArgs a{};
     a.g = {reinterpret_cast<const topo::Pt *>(ring_xy), ring_ptr, n_tiles, touch_ptr, touch_idx, tol, 1.0, 0.0};
     a.col_ptr = col_ptr;

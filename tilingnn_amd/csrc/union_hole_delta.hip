@@ -6,7 +6,7 @@
 // union_hole_delta_point.h has the derivation and the code per candidate, which a host program runs as well.
 //
 // Launch shape.
-//   union_hole_delta_label_kernel  ONE BLOCK per mask: the loop of union_topology_fold_kernel (min-label propagation over the
+//   union_hole_delta_label_kernel  ONE BLOCK per mask: label_components of union_masks.h (min-label propagation over the
 //                                  contact rows with pointer jumping, at most n_tiles + 1 rounds), the labels in LDS for graphs
 //                                  of up to 6 144 tiles and in the workspace beyond, written to the workspace at the end; and
 //                                  the mask's refusal word from the collision rows of its alive tiles.
@@ -23,7 +23,7 @@
 //                                  per candidate by integer atomics in LDS and written once.
 // Every word of both outputs and every workspace word that is read is written by the call itself: nothing is zeroed first, and
 // integer sums make every call give the same bytes.
-#include "tgnn_common.h"
+#include "union_masks.h"
 #include "union_hole_delta_point.h"
 
 namespace tgnn {
@@ -36,29 +36,16 @@ constexpr int kHdSub = 8;                    // threads that share one (candidat
 constexpr int kHdItems = 1024;               // (candidate, slot) pairs listed at a time: 4 KB of LDS (37 KB a block: 4 blocks a CU)
 constexpr int kHdLabelThreads = 256;
 
-struct HoleArgs {
-    topo::Tiles g;
-    const int32_t *col_ptr;                  // [n_tiles + 1]
-    const int32_t *col_idx;
-    const int32_t *alive;                    // [K][n_tiles]
-    int64_t n_masks;
+struct HoleArgs : MaskSet {
     int32_t *refused;                        // [K]            (workspace)
     int32_t *label;                          // [K][n_tiles]   (workspace)
     int32_t *delta;                          // [K][n_tiles][2]
     int32_t *state;                          // [K][n_tiles]
-    int32_t *err_flag;
-};
-
-struct HdArcs {
-    double (*lo_)[kHdThreads], (*hi_)[kHdThreads];
-    int tid;
-    __device__ __forceinline__ double &lo(int q) { return lo_[q][tid]; }
-    __device__ __forceinline__ double &hi(int q) { return hi_[q][tid]; }
 };
 
 // kInLds: the labels and the list of the mask's alive tiles live in LDS (2 n_tiles words of dynamic LDS), a round visits the
-// alive tiles only and the labels are copied to the workspace at the end; otherwise they live in the workspace throughout.
-// As in union_topology_fold_kernel only thread i % threads writes label i and labels only ever decrease.
+// alive tiles only and the labels are copied to the workspace at the end; otherwise they live in the workspace throughout
+// (union_masks.h: label_components runs the rounds).
 template <bool kInLds>
 __global__ __launch_bounds__(kHdLabelThreads) void union_hole_delta_label_kernel(HoleArgs a, int64_t mask0) {
     extern __shared__ int32_t label_lds[];
@@ -78,51 +65,9 @@ __global__ __launch_bounds__(kHdLabelThreads) void union_hole_delta_label_kernel
         lab[i] = alive ? i : -1;
         if (!alive) continue;
         if (kInLds) list[atomicAdd(&n_alive, 1)] = i;
-        bool hit = false;
-        for (int cc = a.col_ptr[i]; cc < a.col_ptr[i + 1]; ++cc) {
-            const int64_t j = a.col_idx[cc];
-            if (j < 0 || j >= n) {
-                err |= topo::kErrIndex;
-                continue;
-            }
-            hit |= j != i && al[j] != 0;
-        }
-        if (hit) collide = 1;
+        if (topo::collides(a.col_ptr, a.col_idx, al, i, n, 0, 1, err)) collide = 1;
     }
-    for (int64_t round = 0; round <= n; ++round) {           // a round lowers a label or is the last
-        __syncthreads();                                     // labels of the last round (or the initial ones) are in place
-        if (tid == 0) changed = 0;
-        __syncthreads();
-        const int items = kInLds ? n_alive : n;
-        bool any = false;
-        for (int w = tid; w < items; w += kHdLabelThreads) {
-            const int i = kInLds ? list[w] : w;
-            const int32_t old = lab[i];
-            if (old < 0) continue;
-            int32_t best = old;
-            for (int cc = a.g.touch_ptr[i]; cc < a.g.touch_ptr[i + 1]; ++cc) {
-                const int64_t j = a.g.touch_idx[cc];
-                if (j < 0 || j >= n) {
-                    err |= topo::kErrIndex;
-                    continue;
-                }
-                const int32_t lj = lab[j];
-                best = lj >= 0 && lj < best ? lj : best;
-            }
-            for (;;) {                                       // pointer jumping: labels strictly decrease along it
-                const int32_t up = lab[best];
-                if (up >= best) break;
-                best = up;
-            }
-            if (best < old) {
-                lab[i] = best;
-                any = true;
-            }
-        }
-        if (any) changed = 1;
-        __syncthreads();
-        if (changed == 0) break;                             // (uniform: read between two barriers)
-    }
+    label_components<kHdLabelThreads, kInLds>(a.g, lab, list, &n_alive, &changed, err);
     if (kInLds)
         for (int i = tid; i < n; i += kHdLabelThreads) out[i] = lab[i];
     if (tid == 0) a.refused[k] = collide;                    // (set before the barriers of the loop's first round)
@@ -149,14 +94,7 @@ __global__ __launch_bounds__(kHdThreads) void union_hole_delta_kernel(HoleArgs a
     const bool dead = t < n && !refused && al[t] == 0;
     if (dead) {
         bool hit = part == 0 && a.g.ring_ptr[t + 1] - a.g.ring_ptr[t] < 3;
-        for (int cc = a.col_ptr[t] + part; cc < a.col_ptr[t + 1]; cc += kHdParts) {
-            const int64_t j = a.col_idx[cc];
-            if (j < 0 || j >= n) {
-                err |= topo::kErrIndex;
-                continue;
-            }
-            hit |= j != t && al[j] != 0;
-        }
+        hit |= topo::collides(a.col_ptr, a.col_idx, al, t, n, part, kHdParts, err);
         if (hit) blocked[mine] = 1;
     }
     __syncthreads();
@@ -188,7 +126,7 @@ __global__ __launch_bounds__(kHdThreads) void union_hole_delta_kernel(HoleArgs a
     // per listed pair do the work.  An eighth of a row is alive: without the list seven lanes in eight would wait for the eighth.
     const int cands = n_list, slots = max_row + 1;
     const int step = cands > 0 ? kHdItems / cands : 1;       // cands <= kHdTiles: a chunk never overflows the list
-    HdArcs arcs{arc_lo, arc_hi, tid};
+    LdsArcs<kHdThreads> arcs{arc_lo, arc_hi, tid};
     for (int s0 = 0; cands > 0 && s0 < slots; s0 += step) {
         const int chunk = (slots - s0 < step ? slots - s0 : step) * cands;
         for (int w = tid; w < chunk; w += kHdThreads) {
@@ -230,9 +168,6 @@ __global__ __launch_bounds__(kHdThreads) void union_hole_delta_kernel(HoleArgs a
 
 using namespace tgnn;
 
-static constexpr int64_t kHdMaxGridY = 65535;
-static constexpr int64_t kHdLabelLdsTiles = 6144;            // 2 x 4 B x 6 144 = 48 KB of dynamic LDS at the most
-
 extern "C" size_t tgnn_union_hole_delta_workspace_bytes(int64_t n_masks, int64_t n_tiles) {
     if (n_masks <= 0 || n_tiles <= 0 || n_masks > (1ll << 58) / (n_tiles + 2)) return 0;
     return (size_t)n_masks * ((size_t)n_tiles + 1) * sizeof(int32_t);
@@ -244,33 +179,27 @@ extern "C" int tgnn_union_hole_delta(const double *ring_xy, const int32_t *ring_
                                      int32_t *delta_out, int32_t *state_out, int32_t *err_flag, void *ws, size_t ws_bytes,
                                      tgnn_stream_t stream) {
     DeviceGuard guard__(stream);
-    TGNN_CHECK_ARG(n_tiles >= 0 && n_tiles < (1ll << 31) - 1 && n_masks >= 0, "shape");
-    TGNN_CHECK_ARG(tol >= 0.0, "tol");                       // (false for a NaN too)
-    TGNN_CHECK_ARG(fabs(dir_x * dir_x + dir_y * dir_y - 1.0) <= 1e-9, "(dir_x, dir_y) is not a unit vector");
+    if (int rc = check_mask_shape(__func__, n_tiles, n_masks, tol, dir_x, dir_y)) return rc;
     if (n_masks == 0 || n_tiles == 0) return TGNN_OK;        // no output word
     TGNN_CHECK_ARG(delta_out && state_out && err_flag, "null delta_out / state_out / err_flag");
-    TGNN_CHECK_ARG(n_masks <= (1ll << 58) / (n_tiles + 2), "K * n_tiles overflows");
-    // (col_idx / touch_idx may be NULL: no collision edge / no contact)
-    TGNN_CHECK_ARG(ring_xy && ring_ptr && col_ptr && touch_ptr && alive, "null tile array");
-    TGNN_CHECK_ARG(ws && ws_bytes >= tgnn_union_hole_delta_workspace_bytes(n_masks, n_tiles), "workspace too small");
-    TGNN_CHECK_ARG(reinterpret_cast<uintptr_t>(ws) % sizeof(int32_t) == 0, "workspace alignment");
+    if (int rc = check_mask_arrays(__func__, n_masks, (1ll << 58) / (n_tiles + 2), ring_xy && ring_ptr && col_ptr && touch_ptr && alive,
+                                   ws, ws_bytes, tgnn_union_hole_delta_workspace_bytes(n_masks, n_tiles), sizeof(int32_t)))
+        return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     int32_t *words = static_cast<int32_t *>(ws);
-    HoleArgs a{{reinterpret_cast<const topo::Pt *>(ring_xy), ring_ptr, n_tiles, touch_ptr, touch_idx, tol, dir_x, dir_y},
-               col_ptr, col_idx, alive, n_masks, words, words + n_masks, delta_out, state_out, err_flag};
-    constexpr int64_t kMaxGridX = 1ll << 30;
-    for (int64_t k0 = 0; k0 < n_masks; k0 += kMaxGridX) {
-        const unsigned g = (unsigned)(n_masks - k0 < kMaxGridX ? n_masks - k0 : kMaxGridX);
-        if (n_tiles <= kHdLabelLdsTiles)
+    HoleArgs a{{{reinterpret_cast<const topo::Pt *>(ring_xy), ring_ptr, n_tiles, touch_ptr, touch_idx, tol, dir_x, dir_y},
+                col_ptr, col_idx, alive, n_masks, err_flag},
+               words, words + n_masks, delta_out, state_out};
+    for_mask_chunks(n_masks, kMaskGridX, [&](int64_t k0, unsigned g) {
+        if (n_tiles <= kLabelLdsTiles)
             union_hole_delta_label_kernel<true><<<g, kHdLabelThreads, 2 * sizeof(int32_t) * n_tiles, s>>>(a, k0);
         else
             union_hole_delta_label_kernel<false><<<g, kHdLabelThreads, 0, s>>>(a, k0);
-    }
+    });
     const unsigned gx = (unsigned)((n_tiles + kHdTiles - 1) / kHdTiles);
-    for (int64_t k0 = 0; k0 < n_masks; k0 += kHdMaxGridY) {
-        const unsigned gy = (unsigned)(n_masks - k0 < kHdMaxGridY ? n_masks - k0 : kHdMaxGridY);
+    for_mask_chunks(n_masks, kMaskGridY, [&](int64_t k0, unsigned gy) {
         union_hole_delta_kernel<<<dim3(gx, gy), kHdThreads, 0, s>>>(a, k0);
-    }
+    });
     TGNN_CHECK_LAUNCH();
     return TGNN_OK;
 }

@@ -20,35 +20,22 @@
 // tile would leave four lanes in five idle through the whole of the work; the points fill them.  Each thread adds its integer
 // terms to the mask's chi with one integer atomic: integer addition commutes, so every call gives the same bits.
 // union_topology_fold_kernel: ONE BLOCK per mask labels the components by min-label propagation over the contact rows filtered
-// by the mask, with pointer jumping, until a block-wide flag stays down (no grid barrier); labels live in LDS for graphs of up
-// to 6 144 tiles, in the caller's workspace beyond; components = alive tiles that kept their own index.  The memset of the K chi / status words and the two kernels
-// follow each other on the stream; nothing returns to the host.
-#include "tgnn_common.h"
-#include "union_topology_point.h"
+// by the mask, with pointer jumping, until a block-wide flag stays down (no grid barrier; union_masks.h: label_components, which
+// csrc/union_hole_delta.hip and csrc/union_contour.hip run too); labels live in LDS for graphs of up to 6 144 tiles, in the
+// caller's workspace beyond; components = alive tiles that kept their own index.  The memset of the K chi / status words and the
+// two kernels follow each other on the stream; nothing returns to the host.
+#include "union_masks.h"
 
 namespace tgnn {
 
 constexpr int kUtThreads = 128;
 constexpr int kUtFoldThreads = 256;
 
-struct TopoArgs {
-    topo::Tiles g;
-    const int32_t *col_ptr;                  // [n_tiles + 1]
-    const int32_t *col_idx;
-    const int32_t *alive;                    // [K][n_tiles]
-    int64_t n_masks;
+struct TopoArgs : MaskSet {
     int32_t *label;                          // [K][n_tiles]   (workspace)
     int32_t *chi;                            // [K]            (workspace, zeroed per call)
     int32_t *status;                         // [K]            (workspace, zeroed per call)
     int32_t *out;                            // [K][3]
-    int32_t *err_flag;
-};
-
-struct LdsArcs {
-    double (*lo_)[kUtThreads], (*hi_)[kUtThreads];
-    int tid;
-    __device__ __forceinline__ double &lo(int q) { return lo_[q][tid]; }
-    __device__ __forceinline__ double &hi(int q) { return hi_[q][tid]; }
 };
 
 __global__ __launch_bounds__(kUtThreads) void union_topology_chi_kernel(TopoArgs a, int64_t mask0) {
@@ -64,17 +51,8 @@ __global__ __launch_bounds__(kUtThreads) void union_topology_chi_kernel(TopoArgs
     int err = 0;
     // 1. one thread per tile: the collision rows, and the block's alive tiles into a list (in any order: the sum is of integers)
     if (i < a.g.n_tiles && al[i] != 0) {
-        bool collides = false;
-        for (int cc = a.col_ptr[i]; cc < a.col_ptr[i + 1]; ++cc) {
-            const int64_t j = a.col_idx[cc];
-            if (j < 0 || j >= a.g.n_tiles) {
-                err |= topo::kErrIndex;
-                continue;
-            }
-            collides |= j != i && al[j] != 0;
-        }
         const int n = a.g.ring_ptr[i + 1] - a.g.ring_ptr[i];
-        if (collides) {
+        if (topo::collides(a.col_ptr, a.col_idx, al, i, a.g.n_tiles, 0, 1, err)) {
             atomicOr(a.status + k, 1);
         } else if (n >= 3) {
             list[atomicAdd(&n_list, 1)] = tid;
@@ -84,7 +62,7 @@ __global__ __launch_bounds__(kUtThreads) void union_topology_chi_kernel(TopoArgs
     __syncthreads();
     // 2. one thread per (alive tile, vertex): the alive tiles are few, so the points, not the tiles, fill the lanes
     const int tiles = n_list, points = tiles * max_verts;
-    LdsArcs arcs{arc_lo, arc_hi, tid};
+    LdsArcs<kUtThreads> arcs{arc_lo, arc_hi, tid};
     int sum = 0;
     for (int w = tid; w < points; w += kUtThreads) {
         const int64_t t = (int64_t)blockIdx.x * kUtThreads + list[w % tiles];
@@ -96,9 +74,8 @@ __global__ __launch_bounds__(kUtThreads) void union_topology_chi_kernel(TopoArgs
 }
 
 // kInLds: the labels and the list of the mask's alive tiles live in LDS (2 n_tiles words of dynamic LDS) and a round visits the
-// alive tiles only; otherwise the labels live in the workspace and a round strides over all tiles.  A label is -1 for a dead
-// tile, else the index of an alive tile of the same component; labels only ever decrease, and only thread i % threads writes
-// label i, so a label read while its owner lowers it is merely one round old.
+// alive tiles only; otherwise the labels live in the workspace and a round strides over all tiles (union_masks.h:
+// label_components runs the rounds).  A label is -1 for a dead tile, else the index of an alive tile of the same component.
 template <bool kInLds>
 __global__ __launch_bounds__(kUtFoldThreads) void union_topology_fold_kernel(TopoArgs a, int64_t mask0) {
     extern __shared__ int32_t fold_lds[];
@@ -117,40 +94,7 @@ __global__ __launch_bounds__(kUtFoldThreads) void union_topology_fold_kernel(Top
         if (kInLds && alive) list[atomicAdd(&n_alive, 1)] = i;
     }
     int err = 0;
-    for (;;) {
-        __syncthreads();                                     // labels of the last round (or the initial ones) are in place
-        if (tid == 0) changed = 0;
-        __syncthreads();
-        const int items = kInLds ? n_alive : n;
-        bool any = false;
-        for (int w = tid; w < items; w += kUtFoldThreads) {
-            const int i = kInLds ? list[w] : w;
-            const int32_t old = lab[i];
-            if (old < 0) continue;
-            int32_t best = old;
-            for (int cc = a.g.touch_ptr[i]; cc < a.g.touch_ptr[i + 1]; ++cc) {
-                const int64_t j = a.g.touch_idx[cc];
-                if (j < 0 || j >= n) {
-                    err |= topo::kErrIndex;
-                    continue;
-                }
-                const int32_t lj = lab[j];
-                best = lj >= 0 && lj < best ? lj : best;
-            }
-            for (;;) {                                       // pointer jumping, to the current root
-                const int32_t up = lab[best];
-                if (up >= best) break;
-                best = up;
-            }
-            if (best < old) {
-                lab[i] = best;
-                any = true;
-            }
-        }
-        if (any) changed = 1;
-        __syncthreads();
-        if (changed == 0) break;                             // (uniform: read between two barriers)
-    }
+    label_components<kUtFoldThreads, kInLds>(a.g, lab, list, &n_alive, &changed, err);
     int mine = 0;
     for (int i = tid; i < n; i += kUtFoldThreads) mine += lab[i] == i ? 1 : 0;
     if (mine != 0) atomicAdd(&roots, mine);
@@ -168,9 +112,6 @@ __global__ __launch_bounds__(kUtFoldThreads) void union_topology_fold_kernel(Top
 
 using namespace tgnn;
 
-static constexpr int64_t kUtMaxGridY = 65535;
-static constexpr int64_t kUtFoldLdsTiles = 6144;             // 2 x 4 B x 6 144 = 48 KB of dynamic LDS at the most
-
 extern "C" size_t tgnn_union_topology_workspace_bytes(int64_t n_masks, int64_t n_tiles) {
     if (n_masks <= 0 || n_tiles <= 0 || n_masks > (1ll << 58) / (n_tiles + 2)) return 0;
     return (size_t)n_masks * ((size_t)n_tiles + 2) * sizeof(int32_t);
@@ -181,9 +122,7 @@ extern "C" int tgnn_union_topology(const double *ring_xy, const int32_t *ring_pt
                                    const int32_t *alive, int64_t n_masks, double tol, double dir_x, double dir_y, int32_t *out,
                                    int32_t *err_flag, void *ws, size_t ws_bytes, tgnn_stream_t stream) {
     DeviceGuard guard__(stream);
-    TGNN_CHECK_ARG(n_tiles >= 0 && n_tiles < (1ll << 31) - 1 && n_masks >= 0, "shape");
-    TGNN_CHECK_ARG(tol >= 0.0, "tol");                       // (false for a NaN too)
-    TGNN_CHECK_ARG(fabs(dir_x * dir_x + dir_y * dir_y - 1.0) <= 1e-9, "(dir_x, dir_y) is not a unit vector");
+    if (int rc = check_mask_shape(__func__, n_tiles, n_masks, tol, dir_x, dir_y)) return rc;
     if (n_masks == 0) return TGNN_OK;
     TGNN_CHECK_ARG(out && err_flag, "null out / err_flag");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -191,28 +130,24 @@ extern "C" int tgnn_union_topology(const double *ring_xy, const int32_t *ring_pt
         TGNN_CHECK_HIP(hipMemsetAsync(out, 0, sizeof(int32_t) * 3 * n_masks, s));
         return TGNN_OK;
     }
-    TGNN_CHECK_ARG(n_masks <= (1ll << 58) / (n_tiles + 2), "K * n_tiles overflows");
-    // (col_idx / touch_idx may be NULL: no collision edge / no contact)
-    TGNN_CHECK_ARG(ring_xy && ring_ptr && col_ptr && touch_ptr && alive, "null tile array");
-    TGNN_CHECK_ARG(ws && ws_bytes >= tgnn_union_topology_workspace_bytes(n_masks, n_tiles), "workspace too small");
-    TGNN_CHECK_ARG(reinterpret_cast<uintptr_t>(ws) % sizeof(int32_t) == 0, "workspace alignment");
+    if (int rc = check_mask_arrays(__func__, n_masks, (1ll << 58) / (n_tiles + 2), ring_xy && ring_ptr && col_ptr && touch_ptr && alive,
+                                   ws, ws_bytes, tgnn_union_topology_workspace_bytes(n_masks, n_tiles), sizeof(int32_t)))
+        return rc;
     int32_t *words = static_cast<int32_t *>(ws);
-    TopoArgs a{{reinterpret_cast<const topo::Pt *>(ring_xy), ring_ptr, n_tiles, touch_ptr, touch_idx, tol, dir_x, dir_y},
-               col_ptr, col_idx, alive, n_masks, words + 2 * n_masks, words, words + n_masks, out, err_flag};
+    TopoArgs a{{{reinterpret_cast<const topo::Pt *>(ring_xy), ring_ptr, n_tiles, touch_ptr, touch_idx, tol, dir_x, dir_y},
+                col_ptr, col_idx, alive, n_masks, err_flag},
+               words + 2 * n_masks, words, words + n_masks, out};
     TGNN_CHECK_HIP(hipMemsetAsync(words, 0, sizeof(int32_t) * 2 * n_masks, s));
     const unsigned gx = (unsigned)((n_tiles + kUtThreads - 1) / kUtThreads);
-    for (int64_t k0 = 0; k0 < n_masks; k0 += kUtMaxGridY) {
-        const unsigned gy = (unsigned)(n_masks - k0 < kUtMaxGridY ? n_masks - k0 : kUtMaxGridY);
+    for_mask_chunks(n_masks, kMaskGridY, [&](int64_t k0, unsigned gy) {
         union_topology_chi_kernel<<<dim3(gx, gy), kUtThreads, 0, s>>>(a, k0);
-    }
-    constexpr int64_t kMaxGridX = 1ll << 30;
-    for (int64_t k0 = 0; k0 < n_masks; k0 += kMaxGridX) {
-        const unsigned g = (unsigned)(n_masks - k0 < kMaxGridX ? n_masks - k0 : kMaxGridX);
-        if (n_tiles <= kUtFoldLdsTiles)
+    });
+    for_mask_chunks(n_masks, kMaskGridX, [&](int64_t k0, unsigned g) {
+        if (n_tiles <= kLabelLdsTiles)
             union_topology_fold_kernel<true><<<g, kUtFoldThreads, 2 * sizeof(int32_t) * n_tiles, s>>>(a, k0);
         else
             union_topology_fold_kernel<false><<<g, kUtFoldThreads, 0, s>>>(a, k0);
-    }
+    });
     TGNN_CHECK_LAUNCH();
     return TGNN_OK;
 }

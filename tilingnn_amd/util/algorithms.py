@@ -200,8 +200,8 @@ class HoleGuard:
         self.launches += 1
         words = self._host.numpy()
         if words[-1]:
-            raise _lib.TgnnError(f"tgnn_union_hole_delta: device error word {int(words[-1])} (1: collision or contact index out "
-                                 "of range, 2: more tiles meet in one point than the kernel's wedge list holds)")
+            from .data_util import _TOPOLOGY_ERROR_BITS, _raise_device_error
+            _raise_device_error("tgnn_union_hole_delta", int(words[-1]), _TOPOLOGY_ERROR_BITS)
         self.state = words[2 * n_tiles:3 * n_tiles][self.tiles]
         if (self.state == 3).any():
             raise ValueError("HoleGuard: two accepted tiles collide")

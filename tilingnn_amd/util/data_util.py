@@ -163,6 +163,36 @@ def create_brick_layout_from_super_set(graph: TileGraph, tiles_super_set):
 
 
 # ------------------------------------------------------------------------------------------ producer, device
+def _union_api():
+    """(torch, _lib, check, lib, ptr, UNION_TOL): what the union calls of CompleteGraphOnDevice need, imported on first use (this
+    module imports without torch and without the library)."""
+    import torch
+    from .. import _lib
+    from .._lib import check, lib, ptr
+    from ..tiling.region import UNION_TOL
+    return torch, _lib, check, lib, ptr, UNION_TOL
+
+
+# the bits of the device error words (include/tgnn.h: TGNN_UNION_ERR_*, TGNN_TOPO_ERR_*, TGNN_CONTOUR_ERR_*)
+_AREA_ERROR_BITS = {1: "collision index out of range",
+                    2: "a tile side is covered in more separate stretches than the kernel's interval list holds"}
+_TOPOLOGY_ERROR_BITS = {1: "collision or contact index out of range",            # (tgnn_union_hole_delta's too)
+                        2: "more tiles meet in one point than the kernel's wedge list holds"}
+_CONTOUR_ERROR_BITS = {1: "a collision or contact index out of range",
+                       2: "more boundary pieces leave one point than the kernel's wedge list holds",
+                       4: "more foreign vertices inside one tile side than the kernel's split list holds",
+                       8: "an output or the workspace is too small",
+                       16: "the boundary of a mask does not close: its tiles overlap"}
+
+
+def _raise_device_error(name, code, bits, only_set=False):
+    """TgnnError for the non-zero device error word `code` of entry point `name`, with the table of its bits (only_set: only
+    the bits that are set)."""
+    from .._lib import TgnnError
+    listed = [f"{b}: {t}" for b, t in bits.items() if code & b or not only_set]
+    raise TgnnError(f"{name}: device error word {code} (" + ("; " if only_set else ", ").join(listed) + ")")
+
+
 class CompleteGraphOnDevice:
     """The complete graph resident in HBM: node features of ALL tiles, both edge lists, the normalised adjacency
     features, each converted exactly as `to_torch_tensor` converts a layout (float64 -> .float(), int -> .long()).
@@ -183,7 +213,7 @@ class CompleteGraphOnDevice:
         self._alive = torch.zeros(self.n_tiles, dtype=torch.int32, device=self.device)
         self._graph = graph
         self._geometry = None
-        self._union = None
+        self._union = self._rings_host = None
         self._topology = None
 
     def layout(self, tiles_super_set):
@@ -263,26 +293,30 @@ class CompleteGraphOnDevice:
             g = self._graph
             geo = union_geometry([t.tile_poly.exterior for t in g.tiles], g.arrays.colli_edges, self.n_tiles)
             check_tolerance_gap(*geo)
+            self._rings_host = geo[:2]                           # (kept for _topology_geometry)
             self._union = tuple(torch.from_numpy(a if a.size else np.zeros(1, dtype=a.dtype)).to(self.device) for a in geo)
         return self._union
+
+    def _as_masks(self, alive):
+        """`alive` ([K, n_tiles] or [n_tiles], any integer or bool tensor) as a contiguous [K, n_tiles] int32 tensor on this
+        device."""
+        import torch
+        alive = torch.as_tensor(alive, device=self.device)
+        if alive.dim() == 1:
+            alive = alive[None, :]
+        if alive.dim() != 2 or alive.shape[1] != self.n_tiles:
+            raise ValueError(f"alive must be [K, {self.n_tiles}], got {tuple(alive.shape)}")
+        return (alive != 0).to(torch.int32).contiguous() if alive.dtype != torch.int32 else alive.contiguous()
 
     def union_areas(self, alive):
         """[K] float64 on the device: the area of the union of the tiles with alive[k, i] != 0 (`alive` [K, n_tiles] or
         [n_tiles], any integer or bool tensor on this device; what `tiles_in_regions` returns, or a solver's selection) -- the
         reference's `get_super_contour_poly().area` of that tile set.  csrc/union_area.hip; one device-to-host copy of the
         error word."""
-        import torch
-        from .. import _lib
-        from .._lib import check, lib, ptr
-        from ..tiling.region import UNION_TOL
-        alive = torch.as_tensor(alive, device=self.device)
-        if alive.dim() == 1:
-            alive = alive[None, :]
-        if alive.dim() != 2 or alive.shape[1] != self.n_tiles:
-            raise ValueError(f"alive must be [K, {self.n_tiles}], got {tuple(alive.shape)}")
-        alive = (alive != 0).to(torch.int32).contiguous() if alive.dtype != torch.int32 else alive.contiguous()
+        torch, _lib, check, lib, ptr, UNION_TOL = _union_api()
+        alive = self._as_masks(alive)
         k = int(alive.shape[0])
-        area = torch.empty(k, dtype=torch.float64, device=self.device)
+        area =torch.empty(k, dtype=torch.float64, device=self.device)
         if k:
             ring_xy, ring_ptr, col_ptr, col_idx = self._union_geometry()
             err = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -292,19 +326,18 @@ class CompleteGraphOnDevice:
                                       UNION_TOL, ptr(area), ptr(err), ptr(ws), ws_bytes, _lib.current_stream(self.device)))
             code = int(err.item())
             if code:
-                raise _lib.TgnnError(f"tgnn_union_area: device error word {code} (1: collision index out of range, 2: a tile "
-                                     "side is covered in more separate stretches than the kernel's interval list holds)")
+                _raise_device_error("tgnn_union_area", code, _AREA_ERROR_BITS)
         return area
 
     # -------------------------------------------------------------------------- the topology of a union of tiles
     def _topology_geometry(self):
         """The contact relation as CSR and the sweep direction of tgnn_union_topology (region.contact_geometry,
-        region.sweep_direction), made from the graph's rings and uploaded on first use."""
+        region.sweep_direction), made from the packed rings `_union_geometry` built on the host and uploaded on first use."""
         if self._topology is None:
             import torch
-            from ..tiling.region import contact_geometry, sweep_direction, union_geometry
-            g = self._graph
-            ring_xy, ring_ptr, _, _ = union_geometry([t.tile_poly.exterior for t in g.tiles], g.arrays.colli_edges, self.n_tiles)
+            from ..tiling.region import contact_geometry, sweep_direction
+            self._union_geometry()
+            ring_xy, ring_ptr = self._rings_host
             theta = sweep_direction(ring_xy, ring_ptr)
             touch = contact_geometry(ring_xy, ring_ptr)
             self._topology = tuple(torch.from_numpy(a if a.size else np.zeros(1, dtype=a.dtype)).to(self.device)
@@ -317,16 +350,8 @@ class CompleteGraphOnDevice:
         (tiles sharing a single point are connected) and the bounded components of its complement, what the reference's
         `detect_holes` looks for.  For selections that do not overlap: a mask with two colliding alive tiles gets
         {-1, -1, 1}.  csrc/union_topology.hip; one device-to-host copy of the error word."""
-        import torch
-        from .. import _lib
-        from .._lib import check, lib, ptr
-        from ..tiling.region import UNION_TOL
-        alive = torch.as_tensor(alive, device=self.device)
-        if alive.dim() == 1:
-            alive = alive[None, :]
-        if alive.dim() != 2 or alive.shape[1] != self.n_tiles:
-            raise ValueError(f"alive must be [K, {self.n_tiles}], got {tuple(alive.shape)}")
-        alive = (alive != 0).to(torch.int32).contiguous() if alive.dtype != torch.int32 else alive.contiguous()
+        torch, _lib, check, lib, ptr, UNION_TOL = _union_api()
+        alive = self._as_masks(alive)
         k = int(alive.shape[0])
         out = torch.empty(k, 3, dtype=torch.int32, device=self.device)
         if k:
@@ -340,8 +365,7 @@ class CompleteGraphOnDevice:
                                           ws_bytes, _lib.current_stream(self.device)))
             code = int(err.item())
             if code:
-                raise _lib.TgnnError(f"tgnn_union_topology: device error word {code} (1: collision or contact index out of "
-                                     "range, 2: more tiles meet in one point than the kernel's wedge list holds)")
+                _raise_device_error("tgnn_union_topology", code, _TOPOLOGY_ERROR_BITS)
         return out
 
     def hole_deltas(self, alive):
@@ -352,13 +376,7 @@ class CompleteGraphOnDevice:
         per tile (util/algorithms.py:150-152), for all tiles at once.  csrc/union_hole_delta.hip; one device-to-host copy of
         the error word."""
         import torch
-        from .. import _lib
-        alive = torch.as_tensor(alive, device=self.device)
-        if alive.dim() == 1:
-            alive = alive[None, :]
-        if alive.dim() != 2 or alive.shape[1] != self.n_tiles:
-            raise ValueError(f"alive must be [K, {self.n_tiles}], got {tuple(alive.shape)}")
-        alive = (alive != 0).to(torch.int32).contiguous() if alive.dtype != torch.int32 else alive.contiguous()
+        alive = self._as_masks(alive)
         k = int(alive.shape[0])
         delta = torch.empty(k, self.n_tiles, 2, dtype=torch.int32, device=self.device)
         state = torch.empty(k, self.n_tiles, dtype=torch.int32, device=self.device)
@@ -367,18 +385,14 @@ class CompleteGraphOnDevice:
             self.hole_deltas_into(alive, delta, state, err)
             code = int(err.item())
             if code:
-                raise _lib.TgnnError(f"tgnn_union_hole_delta: device error word {code} (1: collision or contact index out of "
-                                     "range, 2: more tiles meet in one point than the kernel's wedge list holds)")
+                _raise_device_error("tgnn_union_hole_delta", code, _TOPOLOGY_ERROR_BITS)
         return delta, state
 
     def hole_deltas_into(self, alive, delta, state, err):
         """The call of `hole_deltas` alone, queued on the current stream with nothing read back: `alive` [K, n_tiles] int32
         contiguous, `delta` / `state` / `err` int32 device buffers of 2 K n_tiles / K n_tiles / 1 words, `err` zeroed by the
         caller (util.algorithms.HoleGuard keeps the three in one buffer and reads it back in one copy)."""
-        import torch
-        from .. import _lib
-        from .._lib import check, lib, ptr
-        from ..tiling.region import UNION_TOL
+        torch, _lib, check, lib, ptr, UNION_TOL = _union_api()
         k = int(alive.shape[0])
         ring_xy, ring_ptr, col_ptr, col_idx = self._union_geometry()
         touch_ptr, touch_idx, dir_x, dir_y = self._topology_geometry()
@@ -396,16 +410,8 @@ class CompleteGraphOnDevice:
         `get_selected_tiles_union_polygon` of that selection.  For selections that do not overlap: a mask with two colliding
         alive tiles gets status 1 and no rings.  csrc/union_contour.hip; the outputs are sized by the bound of 2 points per
         vertex of an alive tile (one device reduction), one device-to-host copy brings back the error word and the totals."""
-        import torch
-        from .. import _lib
-        from .._lib import check, lib, ptr
-        from ..tiling.region import UNION_TOL
-        alive = torch.as_tensor(alive, device=self.device)
-        if alive.dim() == 1:
-            alive = alive[None, :]
-        if alive.dim() != 2 or alive.shape[1] != self.n_tiles:
-            raise ValueError(f"alive must be [K, {self.n_tiles}], got {tuple(alive.shape)}")
-        alive = (alive != 0).to(torch.int32).contiguous() if alive.dtype != torch.int32 else alive.contiguous()
+        torch, _lib, check, lib, ptr, UNION_TOL = _union_api()
+        alive = self._as_masks(alive)
         k = int(alive.shape[0])
         ring_xy, ring_ptr, col_ptr, col_idx = self._union_geometry()
         i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=self.device)
@@ -430,11 +436,7 @@ class CompleteGraphOnDevice:
         code, rings, points = (int(v) for v in word.cpu().tolist())
         code &= 0xFFFFFFFF
         if code:
-            names = {1: "a collision or contact index out of range", 2: "more boundary pieces leave one point than the kernel's "
-                     "wedge list holds", 4: "more foreign vertices inside one tile side than the kernel's split list holds",
-                     8: "an output or the workspace is too small", 16: "the boundary of a mask does not close: its tiles overlap"}
-            raise _lib.TgnnError(f"tgnn_union_contour: device error word {code} ("
-                                 + "; ".join(f"{b}: {t}" for b, t in names.items() if code & b) + ")")
+            _raise_device_error("tgnn_union_contour", code, _CONTOUR_ERROR_BITS, only_set=True)
         return UnionContours(ring_xy, ring_ptr, mask_out, ring_out[:rings], ring_area[:rings], pts_xy[:points], pts_src[:points])
 
     def layouts_in_regions(self, regions, with_area=False):
