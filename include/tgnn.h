@@ -1313,6 +1313,65 @@ int tgnn_union_hole_delta(const double *ring_xy, const int32_t *ring_ptr, int64_
                           int32_t *state_out /* [K][n_tiles] */, int32_t *err_flag, void *ws, size_t ws_bytes,
                           tgnn_stream_t stream);
 
+/* ---- one round of the hole-free greedy sweep for K layouts cut from ONE complete graph (csrc/hole_sweep.hip): the sequential
+ * acceptance sweep of the reference (util/algorithms.py:41-54) with its hole veto (:150-152) before the draw, one block per
+ * layout, a visited node's d holes computed when the walk reaches it (csrc/hole_sweep_step.h).  One call per greedy round, no
+ * host synchronisation, integer sums only, every output word of a layout that ran written by the call: the same bytes on every
+ * run.  Every array is device memory.
+ *   ring_xy, ring_ptr, touch_ptr, touch_idx, tol, (dir_x, dir_y): as for tgnn_union_hole_delta.  The complete graph's collision
+ *   rows are NOT an argument: an unlabelled node cannot collide with a selected node of its own layout, because the layout's
+ *   collision edges are the graph's restricted to it and every acceptance labels the node's collision neighbours.
+ *   Layout tables, constant over a solve: node_ptr [K + 1] (layout k owns the nodes node_ptr[k] .. node_ptr[k + 1] of N = n_nodes);
+ *   tile_of_node [N], each layout's inverse_index; nbr_ptr [N + 1], nbr_idx [n_nbr]: the collision neighbours of every node as
+ *   CSR, row = the node's place in [0, N), entries = LOCAL node numbers of the same layout, in edge order (nbr_idx may be NULL
+ *   when n_nbr is 0).
+ *   State, the caller's, carried from round to round: unlabelled [N] (!= 0: not yet labelled); tile_alive [K][n_tiles], the
+ *   layout's selected tiles; label [K][n_tiles], -1 for a dead tile, else the LOWEST alive tile of its component (closed union:
+ *   tiles that share a point are connected); chi_cache [K][n_tiles], TGNN_SWEEP_CHI_UNKNOWN or the change of the Euler
+ *   characteristic the tile would make under tile_alive, forgotten for the contact row of every accepted tile (a veto repeated
+ *   round after round is then answered from the labels alone).  A solve starts from all ones, all zeros, all -1 and all
+ *   TGNN_SWEEP_CHI_UNKNOWN.  Up to 6 144 tiles the labels are held in LDS during the walk and written back at its end; beyond,
+ *   they are read and written in place.
+ *   Per round: active [K] (0: the layout is skipped); visit_ptr [K + 1]; visit_node [V], LOCAL nodes in visiting order; thr [V]
+ *   fp64, the acceptance threshold of that position; u [V] fp64, layout k's uniforms from u[visit_ptr[k]] on, consumed in order.
+ *   Per position, in order: a node that is no longer unlabelled ends the walk; d holes of its tile (the value
+ *   tgnn_union_hole_delta gives for that tile on the layout's tile_alive: 0 for a tile that touches nothing alive or has fewer
+ *   than 3 vertices); d holes > 0: a veto, NO u is consumed; else the next u is consumed and thr > u accepts: the node leaves
+ *   unlabelled, its tile enters tile_alive, the labels are brought up to date, the node's unlabelled collision neighbours are
+ *   cleared.  After the walk: whether every still-unlabelled node of the layout is vetoed under the final selection.
+ *   stats_out [K][8] int32 = TGNN_SWEEP_STAT_*: positions reached, vetoes, u consumed, accepted, killed, all vetoed (1 also
+ *   when no node is left), 0, 0.  accepted_out [V]: the accepted local nodes in order from accepted_out[visit_ptr[k]];
+ *   killed_out [N]: the cleared neighbours, by acceptance then row order, from killed_out[node_ptr[k]] (the accepted nodes
+ *   themselves are not among them).  trace_out [V][2] = {TGNN_SWEEP_*, d holes} of every position of the visiting list.
+ *   err_out [K] gets the layout's TGNN_TOPO_ERR_* bits (0: none): a node, tile, contact or table entry outside its array,
+ *   or more than 16 tiles around a point counting the visited tile.  The walk ends where the error shows; the layout's other
+ *   outputs and its state are then not to be used.
+ *   A layout that is inactive or whose visiting list is empty: none of its words, output or state, is touched.
+ *   ws: tgnn_hole_sweep_workspace_bytes(K) = 4 K bytes, 4-byte aligned; its contents on entry do not matter.
+ *   K, n_tiles, n_nodes or n_visit == 0: nothing is queued. */
+#define TGNN_SWEEP_NOT_REACHED 0
+#define TGNN_SWEEP_BREAK 1
+#define TGNN_SWEEP_VETOED 2
+#define TGNN_SWEEP_REJECTED 3
+#define TGNN_SWEEP_ACCEPTED 4
+#define TGNN_SWEEP_STAT_VISITED 0
+#define TGNN_SWEEP_STAT_VETOES 1
+#define TGNN_SWEEP_STAT_DRAWS 2
+#define TGNN_SWEEP_STAT_ACCEPTED 3
+#define TGNN_SWEEP_STAT_KILLED 4
+#define TGNN_SWEEP_STAT_ALL_VETOED 5
+#define TGNN_SWEEP_STAT_WORDS 8
+#define TGNN_SWEEP_CHI_UNKNOWN (-2147483647 - 1)
+size_t tgnn_hole_sweep_workspace_bytes(int64_t n_layouts);
+int tgnn_hole_sweep_many(const double *ring_xy, const int32_t *ring_ptr, int64_t n_tiles, const int32_t *touch_ptr,
+                         const int32_t *touch_idx, double tol, double dir_x, double dir_y, int64_t n_layouts,
+                         const int32_t *node_ptr, int64_t n_nodes, const int32_t *tile_of_node, const int32_t *nbr_ptr,
+                         const int32_t *nbr_idx, int64_t n_nbr, int32_t *unlabelled, int32_t *tile_alive, int32_t *label,
+                         int32_t *chi_cache, const int32_t *active, const int32_t *visit_ptr, const int32_t *visit_node, const double *thr,
+                         const double *u, int64_t n_visit, int32_t *stats_out /* [K][8] */, int32_t *accepted_out /* [V] */,
+                         int32_t *killed_out /* [N] */, int32_t *trace_out /* [V][2] */, int32_t *err_out /* [K] */, void *ws,
+                         size_t ws_bytes, tgnn_stream_t stream);
+
 /* ---- the outline of the union of the alive tiles of K masks (csrc/union_contour.hip): what the reference's
  * BrickLayout.get_selected_tiles_union_polygon (tiling/brick_layout.py:223-227) returns for a solved layout.  One call for all K
  * masks, no host synchronisation, no floating-point atomics: the same bits in every output on every run.  For masks whose alive

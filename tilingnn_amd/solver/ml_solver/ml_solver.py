@@ -9,6 +9,7 @@
     solve(brick_layout)              ml_solver.py:64-73   (greedy assembly loop: tilingnn_amd/util/algorithms.py keeps the
                                                            layout on the GPU; `greedy_solver=` swaps in the reference's)
     solve_many(brick_layouts)        Tiling-Shape.py:60-64 (the crop loop: K device-greedy solves in one loop)
+    solve_many_hole_free(layouts)    the same crop loop with the hole veto of algorithms.py:150-152 in every solve
 The debug dumps stay with the reference.
 
 `brick_layout` is duck-typed exactly as the reference uses it: `.node_feature`,
@@ -62,6 +63,9 @@ class ML_Solver:
         # ... and, with union_forward, prepare their graphs by ONE library call and one read-back per round instead of one of each per
         # sub-layout (TilinGNN.forward_many(union=True, union_prep=True), csrc/graph_prep.hip); the same graphs either way
         self.union_prep = False
+        # solve_many: K hole-free solves -- solve_many_hole_free, the sequential sweep with the reference's hole veto for every layout
+        # (csrc/hole_sweep.hip) -- instead of the batched acceptance, which has no hole rule
+        self.check_holes_many = False
 
     @staticmethod
     def _no_edges(index) -> bool:
@@ -96,6 +100,42 @@ class ML_Solver:
                               col_e_idx=collide_edge_index, col_e_features=collide_edge_features)
         return predictions[:, self._best_prob_map(predictions, brick_layout)].detach().contiguous()
 
+    def predict_many(self, sub_layouts):
+        """`predict` for several device-resident layouts at once -> a list of numpy arrays, per layout the bits `predict` returns:
+        the forwards side by side (`network.forward_many`, honouring `union_forward` / `union_prep`, with the checks of
+        `forward_checked` once), the best-map pick of a network with several maps from ONE loss call as
+        `solve_many_by_device_greedy` makes it, and ONE read-back for all layouts.  A layout with one edge set left gets ones
+        without the network (ml_solver.py:31-32).  This is the seam `solve_many_hole_free` calls once per round
+        (tilingnn_amd.util.algorithms.solve_many_hole_free; each sub-layout carries `.origin_index` there)."""
+        from ...util import algorithms as alg
+        subs = list(sub_layouts)
+        out = [None] * len(subs)
+        need = [i for i, s in enumerate(subs) if not (self._no_edges(s.collide_edge_index) or self._no_edges(s.align_edge_index))]
+        for i, s in enumerate(subs):
+            if i not in need:
+                out[i] = np.ones(int(s.node_feature.shape[0]), dtype=np.float32)
+        if not need:
+            return out
+        views = [subs[i] for i in need]
+        if hasattr(self.network, "forward_many"):
+            preds = alg._forward_many_checked(self.network, views, 3, bool(self.union_forward), bool(self.union_prep))
+        else:
+            preds = [self.predict_on_device(v).reshape(-1, 1) for v in views]
+        best = {j: 0 for j in range(len(views))}
+        if preds[0].shape[1] > 1:
+            pk = alg.PackedLayouts(views, self.device)
+            best = alg._best_prob_maps_many(pk, list(range(len(views))), preds, None, None)
+        flat = torch.cat([p[:, best[j]].detach().reshape(-1) for j, p in enumerate(preds)])
+        host = torch.empty(flat.shape, dtype=flat.dtype, pin_memory=True)
+        host.copy_(flat, non_blocking=True)
+        torch.cuda.current_stream(flat.device).synchronize()
+        host, at = host.numpy(), 0
+        for j, i in enumerate(need):
+            n = int(preds[j].shape[0])
+            out[i] = host[at:at + n].copy()
+            at += n
+        return out
+
     def _best_prob_map(self, predictions, brick_layout):
         """get_best_prob_map (ml_solver.py:133-136): argsort of the per-map unsupervised loss.
         With one probability map -- the only configuration the reference ever constructs
@@ -122,19 +162,23 @@ class ML_Solver:
                                       adj_e_features=adj_edge_features, col_e_idx=collide_edge_index,
                                       col_e_features=collide_edge_features)
 
-    def solve(self, brick_layout, check_holes=False):
+    def solve(self, brick_layout, check_holes=False, device_sweep=False):
         """ml_solver.py:64-73.  Default loop: tilingnn_amd.util.algorithms.solve_by_probablistic_greedy (layout resident
         on the GPU; score = Losses.solution_score when the layout carries its complete graph and super-contour area, or
         `score_fn`, else None); `greedy_solver=` swaps in another one, e.g. the reference's own.
         check_holes: the reference's hole veto (algorithms.py:150-152) in that loop -- a tile that would enclose a gap is passed
         over, so the solution has no hole (`solve_by_probablistic_greedy(check_holes=True)`, csrc/union_hole_delta.hip).  Always
-        the sequential sweep, whatever `device_greedy_min_nodes` says: the batched acceptance has no hole rule."""
+        the sequential sweep, whatever `device_greedy_min_nodes` says: the batched acceptance has no hole rule.
+        device_sweep (with check_holes): that guarded sweep runs on the device, one launch and one read-back per round
+        (csrc/hole_sweep.hip); the same solution and the same RNG stream."""
+        if device_sweep and not check_holes:
+            raise ValueError("device_sweep is an option of check_holes=True")
         if self._greedy_solver is None:
             from ...util.algorithms import solve_by_device_greedy, solve_by_probablistic_greedy
             n_nodes = int(brick_layout.node_feature.shape[0])
             if check_holes:                                      # the sequential sweep only: tiles accepted at once can close a gap jointly
                 output_solution, score, predict_order = solve_by_probablistic_greedy(self, brick_layout, score_fn=self._score_fn,
-                                                                                     check_holes=True)
+                                                                                     check_holes=True, device_sweep=device_sweep)
             elif self.device_greedy_min_nodes is not None and n_nodes >= self.device_greedy_min_nodes:
                 # large layouts: the acceptance batched on the device (a documented substitute of the sequential sweep)
                 output_solution, score, predict_order = solve_by_device_greedy(self, brick_layout, seed=self.device_greedy_seed,
@@ -161,8 +205,12 @@ class ML_Solver:
         In train mode the BatchNorm running statistics are left untouched (see `TilinGNN.forward_many`).
         `self.union_forward = True`: every round's small sub-layouts are scored inside one persistent kernel launch
         (`TilinGNN.forward_many(union=True)`): the same results, fewer launches per round.  `self.union_prep = True` beside it: the
-        sub-layouts' graphs come from one library call and one read-back per round (`forward_many(..., union_prep=True)`)."""
+        sub-layouts' graphs come from one library call and one read-back per round (`forward_many(..., union_prep=True)`).
+        `self.check_holes_many = True` (an attribute like `union_forward`, default False): `solve_many_hole_free` instead -- K
+        HOLE-FREE solves, the sequential sweep with the reference's hole veto for every layout."""
         from ...util.algorithms import solve_many_by_device_greedy
+        if getattr(self, "check_holes_many", False):
+            return self.solve_many_hole_free(brick_layouts, seed=seed)
         brick_layouts = list(brick_layouts)
         if not brick_layouts:
             return []
@@ -175,6 +223,31 @@ class ML_Solver:
             output_layout.predict_order = order
             output_layout.predict = selection
             output_layout.predict_probs = probs.cpu().numpy() if probs is not None else self.predict(layout)
+            out.append((output_layout, score))
+        return out
+
+    def solve_many_hole_free(self, brick_layouts, seed=None):
+        """`solve(layout, check_holes=True)` for K layouts at once (tilingnn_amd.util.algorithms.solve_many_hole_free,
+        csrc/hole_sweep.hip): every layout is solved as it is solved alone after `np.random.seed(seed_k)` -- the sequential sweep
+        with the reference's hole veto, a block per layout, one `predict_many`, one sweep call and one read-back per round for all
+        of them -- so no solution has a hole.  `seed`: one per layout, or one number for all (default `device_greedy_seed`); the
+        global `np.random` stream is not touched.  The layouts must be cut from ONE complete graph and carry it with their
+        `inverse_index`.  Returns what `solve_many` returns.  What `solve_many` runs when `self.check_holes_many` is set."""
+        from ...util.algorithms import solve_many_hole_free
+        if self._greedy_solver is not None:
+            raise ValueError("check_holes is an option of the default greedy loop; hand it to the `greedy_solver` given instead")
+        brick_layouts = list(brick_layouts)
+        if not brick_layouts:
+            return []
+        seeds = self.device_greedy_seed if seed is None else seed
+        seeds = [int(s) for s in seeds] if np.ndim(seeds) else [int(seeds)] * len(brick_layouts)
+        results = solve_many_hole_free(self, brick_layouts, seeds, score_fn=self._score_fn)
+        out = []
+        for layout, (selection, score, order), probs in zip(brick_layouts, results, solve_many_hole_free.last_first_probs):
+            output_layout = deepcopy(layout)
+            output_layout.predict_order = order
+            output_layout.predict = selection
+            output_layout.predict_probs = probs if probs is not None else self.predict(layout)
             out.append((output_layout, score))
         return out
 

@@ -19,7 +19,9 @@ neither and scores `None` unless `score_fn(selection, origin_layout)` is given.
 
 `check_holes=True` adds the reference's hole veto (algorithms.py:150-152) to that sweep: `HoleGuard` keeps, per node, what adding
 its tile would do to the holes of the selection (csrc/union_hole_delta.hip) and the sweep passes over the tiles that would
-enclose a gap, before the draw.
+enclose a gap, before the draw.  `device_sweep=True` runs that guarded sweep on the device instead (`DeviceHoleSweep`,
+csrc/hole_sweep.hip): one launch and one read-back per ROUND, the same decisions and the same RNG stream; and
+`solve_many_hole_free` runs it for K layouts of one complete graph in one loop, one block per layout.
 
 `solve_many_by_device_greedy` runs K such device-greedy solves (the crops of one silhouette, Tiling-Shape.py:60-64) in one loop
 over `PackedLayouts`: one compaction, one read-back and one acceptance call per round for all of them (csrc/greedy_many.hip).
@@ -208,23 +210,184 @@ class HoleGuard:
         self.dholes = words[:2 * n_tiles].reshape(n_tiles, 2)[self.tiles, 1]
 
 
-def solve_by_probablistic_greedy(ml_solver, origin_layout, score_fn=None, on_round=None, check_holes=False):
+class DeviceHoleSweep:
+    """`HostSweep.round(ids, prob, guard)` with a `HoleGuard`, for K layouts cut from ONE complete graph, ON THE DEVICE
+    (csrc/hole_sweep.hip: tgnn_hole_sweep_many): per round ONE host-to-device copy (who is active, the visiting orders, the
+    thresholds, the uniforms), one call -- a block per layout walks its order and computes a node's d holes when it gets there --
+    and ONE device-to-host copy (counters, accepted and killed nodes, the trace).  The decisions are the host sweep's, one for one.
+    layouts: (n nodes, collide_edge_index as numpy, inverse_index) per layout; rngs: per layout what draws its uniforms,
+    `np.random` itself or a `RandomState`.  A round draws n_sub uniforms in one call and, once the walk has said how many it
+    consumed, rewinds the generator and draws exactly those: numpy's `uniform(size=n)` is n scalar draws bit for bit, so the
+    selection AND the generator's state afterwards are the host sweep's (tests/test_hole_sweep_host.py pins both).
+    State per layout as `HostSweep` keeps it (`sweeps[k]`: prob_saved, unlabelled, selection, order, round_cnt) and on the device
+    `unlabelled` [N] int32 (the alive mask the sub-layout compaction reads), `tile_alive`, `label`, `chi_cache` [K, n_tiles].
+    `vetoes`, `launches` [K]: per layout the vetoes counted and the rounds it was active in; `calls`: sweep calls queued;
+    `trace`: the last round's [V, 2] {code, d holes} with `visit_ptr`, `visit_node` beside it (numpy views of the staging
+    buffers, valid until the next round)."""
+
+    def __init__(self, complete_graph, layouts, rngs, device=None):
+        from .data_util import graph_on_device
+        self.on_device = od = graph_on_device(complete_graph, device)
+        dev, n_tiles = od.device, od.n_tiles
+        layouts = list(layouts)
+        self.k = K = len(layouts)
+        self.rngs = list(rngs)
+        if len(self.rngs) != K:
+            raise ValueError(f"rngs: one per layout ({K}), got {len(self.rngs)}")
+        self.sweeps = [HostSweep(int(n), col) for n, col, _ in layouts]
+        sizes = [sw.n for sw in self.sweeps]
+        self.node_ptr_h = np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)])
+        self.n = N = int(self.node_ptr_h[-1])
+        tiles = np.zeros(max(N, 1), dtype=np.int32)
+        nbr_ptr, nbr_idx = np.zeros(N + 1, dtype=np.int64), []
+        for k, ((n, _, inverse), sw) in enumerate(zip(layouts, self.sweeps)):
+            n0 = int(self.node_ptr_h[k])
+            tiles[n0:n0 + n] = np.fromiter((inverse[i] for i in range(n)), dtype=np.int64, count=n)
+            if n and (tiles[n0:n0 + n].min() < 0 or tiles[n0:n0 + n].max() >= n_tiles):
+                raise ValueError(f"layout {k}: inverse_index names a tile outside [0, {n_tiles})")
+            if sw.has_col:                                      # the rows HostSweep walks (edge order), local numbers
+                nbr_ptr[n0 + 1:n0 + n + 1] = nbr_ptr[n0] + sw.starts[1:]
+                nbr_idx.append(sw.nbr)
+            else:
+                nbr_ptr[n0 + 1:n0 + n + 1] = nbr_ptr[n0]
+        nbr_idx = np.concatenate(nbr_idx) if nbr_idx else np.zeros(0, dtype=np.int64)
+        self.n_nbr = int(nbr_idx.shape[0])
+        if max(N, self.n_nbr, n_tiles) >= 2 ** 31 - 1:
+            raise ValueError("DeviceHoleSweep: more than 2^31 nodes or collision entries")
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+        self.node_ptr, self.tile_of_node = up(self.node_ptr_h), up(tiles)
+        self.nbr_ptr, self.nbr_idx = up(nbr_ptr), up(nbr_idx if self.n_nbr else np.zeros(1))
+        i32 = torch.int32
+        self.unlabelled = torch.ones(max(N, 1), dtype=i32, device=dev)
+        self.tile_alive = torch.zeros(max(K, 1), n_tiles, dtype=i32, device=dev)
+        self.label = torch.full((max(K, 1), n_tiles), -1, dtype=i32, device=dev)
+        self.chi_cache = torch.full((max(K, 1), n_tiles), -2 ** 31, dtype=i32, device=dev)     # TGNN_SWEEP_CHI_UNKNOWN
+        # what a round sends: thr [N] f64 | u [N] f64 | visit_node [N] | visit_ptr [K + 1] | active [K]   (int32 words)
+        words_in = 5 * N + 2 * K + 2
+        self._in = torch.zeros(words_in, dtype=i32, device=dev)
+        self._in_h = torch.zeros(words_in, dtype=i32, pin_memory=True)
+        cut = lambda buf: (buf[:2 * N].view(torch.float64), buf[2 * N:4 * N].view(torch.float64), buf[4 * N:5 * N],
+                           buf[5 * N:5 * N + K + 1], buf[5 * N + K + 1:5 * N + 2 * K + 1])
+        self._in_parts = cut(self._in)
+        self._thr_h, self._u_h, self._visit_node_h, self._visit_ptr_h, self._active_h = (t.numpy() for t in cut(self._in_h))
+        # what a round brings back: stats [K][8] | err [K] | accepted [N] | killed [N] | trace [N][2]
+        words_out = 9 * K + 4 * N + 1
+        self._out = torch.zeros(words_out, dtype=i32, device=dev)
+        self._out_h = torch.zeros(words_out, dtype=i32, pin_memory=True)
+        cut = lambda buf: (buf[:8 * K], buf[8 * K:9 * K], buf[9 * K:9 * K + N], buf[9 * K + N:9 * K + 2 * N],
+                           buf[9 * K + 2 * N:9 * K + 4 * N])
+        self._out_parts = cut(self._out)
+        self._stats_h, self._err_h, self._accepted_h, self._killed_h, self._trace_h = (t.numpy() for t in cut(self._out_h))
+        self._ws = torch.empty(max(K, 1), dtype=i32, device=dev)
+        self.vetoes, self.launches = np.zeros(K, dtype=np.int64), np.zeros(K, dtype=np.int64)
+        self.calls = 0
+        self.trace = self.visit_ptr = self.visit_node = None
+
+    def active(self):
+        return [bool(sw.unlabelled.any()) for sw in self.sweeps]
+
+    def round(self, probs) -> list:
+        """One round of every layout with probs[k] not None: probs[k] = the network's probabilities of the nodes
+        `sweeps[k].ids()`.  Returns per layout the original numbers of the nodes labelled in this round (None where it did not
+        run).  A layout all of whose remaining nodes are vetoed afterwards is finished: its `unlabelled` is cleared on the host."""
+        K, N, od = self.k, self.n, self.on_device
+        ran, states, all_ids = [], {}, {}
+        v = 0
+        self._visit_ptr_h[0] = 0
+        for k, (sw, prob) in enumerate(zip(self.sweeps, probs)):
+            ids = sw.ids() if prob is not None else ()
+            self._active_h[k] = int(len(ids) > 0)
+            if len(ids):
+                prob = np.asarray(prob, dtype=np.float64).reshape(-1)
+                per_node = np.power(np.power(sw.prob_saved[ids], sw.round_cnt - 1) * prob, 1 / sw.round_cnt)     # (HostSweep.round)
+                sw.prob_saved[ids] = per_node
+                order = np.argsort(-per_node)
+                n_sub = order.shape[0]
+                self._visit_node_h[v:v + n_sub] = ids[order]
+                self._thr_h[v:v + n_sub] = np.exp((per_node[order] - 1) * 1.0)
+                states[k] = self.rngs[k].get_state()
+                self._u_h[v:v + n_sub] = self.rngs[k].uniform(size=n_sub)
+                all_ids[k] = ids
+                ran.append(k)
+                v += n_sub
+            elif prob is not None:
+                sw.round_cnt += 1                               # (a round over no node: HostSweep.round counts it)
+            self._visit_ptr_h[k + 1] = v
+        out = [None if p is None else [] for p in probs]
+        if not ran:
+            return out
+        dev = od.device
+        self._in.copy_(self._in_h, non_blocking=True)
+        thr, u, visit_node, visit_ptr, active = self._in_parts
+        stats, err, accepted, killed, trace = self._out_parts
+        od.hole_sweep_into(K, self.node_ptr, N, self.tile_of_node, self.nbr_ptr, self.nbr_idx, self.n_nbr, self.unlabelled,
+                           self.tile_alive, self.label, self.chi_cache, active, visit_ptr, visit_node, thr, u, v, stats, accepted, killed, trace,
+                           err, self._ws)
+        self._out_h.copy_(self._out, non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()
+        self.calls += 1
+        self.trace, self.visit_ptr, self.visit_node = self._trace_h.reshape(-1, 2), self._visit_ptr_h, self._visit_node_h
+        for k in ran:
+            sw, rng = self.sweeps[k], self.rngs[k]
+            if self._err_h[k]:
+                from .data_util import _TOPOLOGY_ERROR_BITS, _raise_device_error
+                _raise_device_error(f"tgnn_hole_sweep_many (layout {k})", int(self._err_h[k]), _TOPOLOGY_ERROR_BITS)
+            _, vetoes, draws, n_acc, n_killed, all_vetoed = (int(w) for w in self._stats_h[8 * k:8 * k + 6])
+            rng.set_state(states[k])                            # the stream moves by what the walk consumed, no more
+            rng.uniform(size=draws)
+            v0, n0 = int(self._visit_ptr_h[k]), int(self.node_ptr_h[k])
+            acc = self._accepted_h[v0:v0 + n_acc].astype(np.int64)
+            gone = self._killed_h[n0:n0 + n_killed].astype(np.int64)
+            sw.unlabelled[acc] = False
+            sw.unlabelled[gone] = False
+            sw.selection[acc] = 1
+            sw.order.extend(int(i) for i in acc)
+            sw.round_cnt += 1
+            self.vetoes[k] += vetoes
+            self.launches[k] += 1
+            out[k] = [int(i) for i in acc] + [int(i) for i in gone]
+            if all_vetoed:                                      # nothing can change any more (solve_by_probablistic_greedy)
+                sw.unlabelled[:] = False
+        return out
+
+
+def solve_by_probablistic_greedy(ml_solver, origin_layout, score_fn=None, on_round=None, check_holes=False, device_sweep=False):
     """algorithms.py:18-62.  `origin_layout`: BrickLayout-like numpy arrays (uploaded once) or a DeviceLayout.
     check_holes: the reference's hole veto (:150-152) in this sweep, through a `HoleGuard` (kept as
     `solve_by_probablistic_greedy.last_guard`): a tile that would enclose a gap is passed over, so the selection never has a
     hole; the layout must carry its `complete_graph` and `inverse_index`.  A round after which every unlabelled node is vetoed
     ends the loop with those nodes unselected: nothing can change any more.  Like the reference's, the veto cannot close a
-    tiling around a hole the target region itself has."""
+    tiling around a hole the target region itself has.
+    device_sweep (with check_holes): the same loop with the guarded sweep on the device -- `DeviceHoleSweep` with K = 1 and
+    numpy's GLOBAL stream in place of `HostSweep` + `HoleGuard`: one launch and one read-back per round instead of one per
+    accepted tile; the same selection, order, round count, vetoes and generator state afterwards.  `.last_guard` is then the
+    `DeviceHoleSweep` (`vetoes[0]`, `launches[0]`)."""
+    if device_sweep and not check_holes:
+        raise ValueError("device_sweep runs the guarded sweep of check_holes=True on the device; without check_holes there is "
+                         "nothing for it to run")
     if check_holes and getattr(origin_layout, "complete_graph", None) is None:
         raise ValueError("check_holes needs the layout's complete graph (tile rings) and inverse_index: a BrickLayout, not a "
                          "bare DeviceLayout")
     device = ml_solver.device
     origin = origin_layout if isinstance(origin_layout, DeviceLayout) else DeviceLayout.upload(origin_layout, device)
     n = int(origin.node_feature.shape[0])
-    sweep = HostSweep(n, origin.collide_edge_index.cpu().numpy())
+    col_host = origin.collide_edge_index.cpu().numpy()
+    sweep = HostSweep(n, col_host)
     builder = SubLayoutBuilder(origin)
     alive_dev = torch.ones(n, dtype=torch.int32, device=origin.node_feature.device)
     guard = None
+    if device_sweep:
+        dsw = DeviceHoleSweep(origin_layout.complete_graph, [(n, col_host, origin_layout.inverse_index)], [np.random],
+                              origin.node_feature.device)
+        solve_by_probablistic_greedy.last_guard = dsw
+        sweep = dsw.sweeps[0]
+        while sweep.unlabelled.any():
+            temp_layout = builder.build(dsw.unlabelled)         # (the sweep's own mask on the device: nothing to upload)
+            if on_round is not None:
+                on_round(temp_layout)
+            dsw.round([ml_solver.predict(temp_layout)])
+        score = create_score(sweep.selection, origin_layout, score_fn, device)
+        return sweep.selection, score, sweep.order
     if check_holes:
         guard = HoleGuard(origin_layout.complete_graph, origin_layout.inverse_index, n, origin.node_feature.device)
         solve_by_probablistic_greedy.last_guard = guard
@@ -666,3 +829,109 @@ def create_score(selection, origin_layout, score_fn=None, device=None):
         return None
     from ..solver.ml_solver.losses import Losses
     return Losses.solution_score(selection, origin_layout, device=device)
+
+
+def solve_many_hole_free(ml_solver, layouts, seeds, score_fn=None, max_rounds=100000):
+    """K hole-free solves -- `solve_by_probablistic_greedy(ml_solver, layouts[k], check_holes=True)` after
+    `np.random.seed(seeds[k])` -- in ONE loop, for layouts cut from ONE complete graph: per round one compaction call for all
+    layouts (`tgnn_sublayout_compact_many`) with its read-back of the sub-layouts' sizes, ONE `ml_solver.predict_many` over the
+    active layouts' sub-layouts, ONE sweep call (`DeviceHoleSweep.round`, csrc/hole_sweep.hip: a block per layout) and its one
+    read-back, whatever K.  Parallel across layouts, SEQUENTIAL within one -- the only shape in which the reference's veto is
+    defined -- so result k is bit for bit the solo solve's: selection, predict_order, round count, vetoes.  Layout k draws from
+    `np.random.RandomState(seeds[k])`, the stream `np.random.seed(seeds[k])` gives the global generator; numpy's global stream
+    is not touched.  A layout without nodes returns what the single-layout loop returns for it.
+    Every sub-layout handed to `predict_many` carries `.origin_index`, its layout's place in `layouts`.
+    Returns a list of K (selection, score, predict_order); `.last_rounds`, `.last_vetoes` [K], `.last_sweep_calls` (sweep calls
+    queued = the rounds of the longest solve), `.last_first_probs` (the first round's probabilities per layout, numpy),
+    `.last_guard` (the `DeviceHoleSweep`)."""
+    layouts = list(layouts)
+    K = len(layouts)
+    fn = solve_many_hole_free
+    fn.last_rounds, fn.last_vetoes, fn.last_sweep_calls, fn.last_first_probs, fn.last_guard = [], [], 0, [], None
+    if K == 0:
+        return []
+    seeds = [int(s) for s in seeds]
+    if len(seeds) != K:
+        raise ValueError(f"seeds: one per layout ({K}), got {len(seeds)}")
+    for k, lay in enumerate(layouts):
+        if getattr(lay, "complete_graph", None) is None or getattr(lay, "inverse_index", None) is None:
+            raise ValueError(f"layout {k}: a hole-free solve needs the layout's complete_graph (tile rings) and inverse_index: a "
+                             "BrickLayout, not a bare DeviceLayout")
+        if lay.complete_graph is not layouts[0].complete_graph:
+            raise ValueError(f"layout {k} is cut from another complete graph than layout 0: one call solves layouts of ONE graph")
+    device = ml_solver.device
+    sizes = [int(np.asarray(lay.node_feature).shape[0]) for lay in layouts]
+    empty = {}
+    for k in range(K):
+        if sizes[k] == 0:                                       # what the single-layout loop makes of it (it draws nothing)
+            keep = np.random.get_state()
+            empty[k] = solve_by_probablistic_greedy(ml_solver, layouts[k], score_fn=score_fn, check_holes=True)
+            np.random.set_state(keep)
+    pk = PackedLayouts(layouts, device)
+    dev = pk.device
+    cols = [np.asarray(lay.collide_edge_index).reshape(2, -1) for lay in layouts]
+    dsw = DeviceHoleSweep(layouts[0].complete_graph, [(sizes[k], cols[k], layouts[k].inverse_index) for k in range(K)],
+                          [np.random.RandomState(s) for s in seeds], dev)
+    fn.last_guard = dsw
+    n_tot, ea_tot, ec_tot = pk.n, pk.ea, pk.ec
+    i64, i32 = torch.int64, torch.int32
+    x_out = torch.empty(max(n_tot, 1), pk.fx, dtype=torch.float32, device=dev)
+    inverse = torch.empty(max(n_tot, 1), dtype=i64, device=dev)
+    adj_out = torch.empty(2 * max(ea_tot, 1), dtype=i64, device=dev)
+    attr_out = torch.empty(max(ea_tot, 1), pk.fe, dtype=torch.float32, device=dev)
+    col_out = torch.empty(2 * max(ec_tot, 1), dtype=i64, device=dev)
+    tail = torch.zeros(4 * K, dtype=i64, device=dev)            # counts [K][3] | error words [K] int32
+    counts, err = tail[:3 * K], tail[3 * K:].view(i32)[:K]
+    tail_h = torch.empty(4 * K, dtype=i64, pin_memory=True)
+    act_words = torch.zeros(K, dtype=i32, device=dev)
+    cws_bytes = int(lib.tgnn_sublayout_compact_many_workspace_bytes(K, n_tot, ea_tot, ec_tot))
+    cws = torch.empty(cws_bytes, dtype=torch.uint8, device=dev)
+    first_probs = [None] * K
+    rounds = [0] * K
+    sent = None
+    rnd = 0
+    while True:
+        active = dsw.active()
+        if not any(active):
+            break
+        rnd += 1
+        if rnd > max_rounds:
+            raise RuntimeError(f"solve_many_hole_free: layouts {[k for k in range(K) if active[k]]} still have unlabelled nodes "
+                               f"after {max_rounds} rounds")
+        if active != sent:                                      # (only when a layout has finished)
+            act_words.copy_(torch.tensor([int(a) for a in active], dtype=i32), non_blocking=False)
+            sent = active
+        check(lib.tgnn_sublayout_compact_many(K, ptr(act_words), ptr(pk.node_ptr), ptr(pk.adj_ptr), ptr(pk.col_ptr), n_tot, ea_tot, ec_tot,
+                                              ptr(dsw.unlabelled), ptr(pk.x), pk.fx, ptr(pk.adj), ptr(pk.attr), pk.fe, ptr(pk.col),
+                                              ptr(x_out), ptr(inverse), ptr(adj_out), ptr(attr_out), ptr(col_out), ptr(counts), ptr(err),
+                                              ptr(cws), cws_bytes, _lib.current_stream(dev)))
+        tail_h.copy_(tail, non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()
+        host = tail_h.numpy()
+        bad = [k for k in range(K) if host[3 * K:].view(np.int32)[k]]
+        if bad:
+            raise IndexError(f"edge index out of range in layout {bad[0]} of {K}")
+        cnt = host[:3 * K].reshape(K, 3)
+        members, subs = [k for k in range(K) if active[k]], []
+        for k in members:
+            n2, ea2, ec2 = (int(v) for v in cnt[k])
+            sub = pk.view(k, x_out, adj_out, attr_out, col_out, n2, ea2, ec2, inverse)
+            sub.origin_index = k
+            subs.append(sub)
+            rounds[k] = rnd
+        probs = [None] * K
+        for k, p in zip(members, ml_solver.predict_many(subs)):
+            probs[k] = p
+            if rnd == 1:
+                first_probs[k] = np.array(p, copy=True)
+        dsw.round(probs)
+    results = []
+    for k in range(K):
+        if k in empty:
+            results.append(empty[k])
+            continue
+        sw = dsw.sweeps[k]
+        results.append((sw.selection, create_score(sw.selection, layouts[k], score_fn, device), sw.order))
+    fn.last_rounds, fn.last_vetoes, fn.last_sweep_calls = rounds, [int(v) for v in dsw.vetoes], dsw.calls
+    fn.last_first_probs = first_probs
+    return results

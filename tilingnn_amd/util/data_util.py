@@ -402,6 +402,26 @@ class CompleteGraphOnDevice:
                                         ptr(touch_idx), ptr(alive), k, UNION_TOL, dir_x, dir_y, ptr(delta), ptr(state),
                                         ptr(err), ptr(ws), ws_bytes, _lib.current_stream(self.device)))
 
+    def hole_sweep_into(self, k, node_ptr, n_nodes, tile_of_node, nbr_ptr, nbr_idx, n_nbr, unlabelled, tile_alive, label, chi_cache,
+                        active, visit_ptr, visit_node, thr, u, n_visit, stats, accepted, killed, trace, err, ws=None):
+        """One round of the hole-free greedy sweep of K layouts of this graph, queued on the current stream with nothing read
+        back: the raw call of `tgnn_hole_sweep_many` (include/tgnn.h has the argument contract; csrc/hole_sweep.hip).  Every
+        argument but the counts is a contiguous tensor on this device: int32, `thr` / `u` float64; `ws` int32 of at least K
+        words (made here when None).  `util.algorithms.DeviceHoleSweep` keeps the state, the staging buffers and the RNG."""
+        torch, _lib, check, lib, ptr, UNION_TOL = _union_api()
+        ring_xy, ring_ptr, _, _ = self._union_geometry()
+        touch_ptr, touch_idx, dir_x, dir_y = self._topology_geometry()
+        ws_bytes = int(lib.tgnn_hole_sweep_workspace_bytes(k))
+        if ws is None:
+            ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib.tgnn_hole_sweep_many(ptr(ring_xy), ptr(ring_ptr), self.n_tiles, ptr(touch_ptr), ptr(touch_idx), UNION_TOL,
+                                           dir_x, dir_y, k, ptr(node_ptr), n_nodes, ptr(tile_of_node), ptr(nbr_ptr), ptr(nbr_idx),
+                                           n_nbr, ptr(unlabelled), ptr(tile_alive), ptr(label), ptr(chi_cache), ptr(active), ptr(visit_ptr),
+                                           ptr(visit_node), ptr(thr), ptr(u), n_visit, ptr(stats), ptr(accepted), ptr(killed),
+                                           ptr(trace), ptr(err), ptr(ws), 4 * int(ws.numel()),
+                                           _lib.current_stream(self.device)))
+
     # -------------------------------------------------------------------------- the outline of a union of tiles
     def union_contours(self, alive):
         """`UnionContours` of the K masks `alive` ([K, n_tiles] or [n_tiles], any integer or bool tensor on this device): the
