@@ -1,9 +1,13 @@
 """Host-side checks of the batched unsupervised loss (no GPU): the two entries are exported, declared and bound with one
-argument list; the grouping of a split; the per-layout block count; the tests' own fp64 restatement of "K losses"
+argument list; the grouping of a split; the per-layout block count; the sums, block count and layout views that the single and
+the K-layout kernels share (csrc/loss_sums.h, many_desc.h) walked on the host under sanitizers; the tests' own fp64 restatement of "K losses"
 (tests/loss_many_oracle.py) against the oracle on the reference's golden cases; the new keyword of the training loops; bad
 arguments rejected before anything is queued."""
 import ctypes as C
 import inspect
+import os
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -51,6 +55,28 @@ def test_block_count_per_layout():
             assert lmo.loss_blocks(*sizes) == blocks, (sizes, blocks)
     for items in (2049, 300000, 10 ** 7):
         assert lmo.loss_blocks(5, items, 9) == min(max(-(-items // 1024), 1), 512)
+
+
+def test_shared_sums_walked_on_the_host_under_sanitizers(tmp_path):
+    """tests/host/loss_sums_test.cpp over csrc/loss_sums.h and many_desc.h -- what the single-layout and the K-layout kernels both
+    call -- built with the host compiler alone under AddressSanitizer + UBSan (the runtime linked into the program itself):
+    the block count at its boundaries in each position, the final formula, and 4 000 random packed sets with broken tables."""
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    clang = "clang" in subprocess.run([cxx, "--version"], capture_output=True, text=True).stdout
+    static_rt = ["-static-libsan"] if clang else ["-static-libasan", "-static-libubsan"]
+    exe = str(tmp_path / "loss_sums_test")
+    build = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                            "-fno-sanitize-recover=undefined", *static_rt, "-I", os.path.join(repo, "tilingnn_amd", "csrc"),
+                            os.path.join(repo, "tests", "host", "loss_sums_test.cpp"), "-o", exe], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr[-4000:]
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0, (run.stdout + run.stderr)[-4000:]
+    words = run.stdout.split()
+    assert words[0] == "ok:" and words[2:4] == ["layouts", "walked,"], run.stdout
+    walked, rejected, maps_bad, score_bad = int(words[1]), int(words[4]), int(words[11]), int(words[14])
+    assert walked > 5000 and rejected > 100 and maps_bad > 100 and score_bad > 20, run.stdout
 
 
 @pytest.mark.parametrize("name", LOSS_CASES)

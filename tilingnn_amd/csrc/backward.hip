@@ -22,6 +22,7 @@
 // All column sums run in fp64 over fixed trees (per-block partials, then one pass over the partial rows), like the
 // forward's BatchNorm statistics; the only atomics are the loss scatter's (fp64: the order shows up at 1e-16).
 #include "tgnn_common.h"
+#include "loss_sums.h"
 
 namespace tgnn {
 
@@ -519,7 +520,6 @@ __global__ void degree_kernel(const int32_t *__restrict__ rowptr, int64_t n, flo
 }
 
 // ------------------------------------------------------------------------------------------------ loss backward
-constexpr float kLossEpsB = 1e-7f;          // losses.py:10
 struct LossCoef {
     double a, b, c;                        // the three factors of the product (losses.py:104-106)
 };
@@ -546,7 +546,7 @@ __global__ __launch_bounds__(256) void loss_bwd_edges_kernel(const float *__rest
         if (i < 0 || i >= n || j < 0 || j >= n) continue;       // (the forward reports these: NaN loss -> IndexError)
         const float pi = p[i * ldp], pj = p[j * ldp];
         const float pp = pi * pj;
-        if (pp >= kLossEpsB && pp <= 1.0f - kLossEpsB) {         // torch.clamp passes the gradient inside [min, max]
+        if (pp >= kLossEps && pp <= 1.0f - kLossEps) {         // torch.clamp passes the gradient inside [min, max]
             const double g = -coef_c / (double)(1.0f - pp);
             atomicAdd(acc + i, g * (double)pj);
             atomicAdd(acc + j, g * (double)pi);
@@ -557,7 +557,7 @@ __global__ __launch_bounds__(256) void loss_bwd_edges_kernel(const float *__rest
         if (i < 0 || i >= n || j < 0 || j >= n) continue;
         const float pi = p[i * ldp], pj = p[j * ldp];
         const float pp = pi * pj * len[e * ldl];
-        if (pp >= kLossEpsB) {                                  // d log(pi pj len) / d pi = 1 / pi
+        if (pp >= kLossEps) {                                  // d log(pi pj len) / d pi = 1 / pi
             atomicAdd(acc + i, coef_l / (double)pi);
             atomicAdd(acc + j, coef_l / (double)pj);
         }
@@ -573,7 +573,7 @@ __global__ void loss_bwd_final_kernel(const double *__restrict__ acc, const floa
     // l_area = log(max(m, eps)), m = mean(area p): d l_area / d p_v = area_v / (n m) while m >= eps
     const double m = exp(terms[0]);
     double g = acc[v];
-    if (m > (double)kLossEpsB * (1.0 + 1e-9)) g += -(double)wa * k.b * k.c * (double)area[v * lda] / ((double)n * m);
+    if (m > (double)kLossEps * (1.0 + 1e-9)) g += -(double)wa * k.b * k.c * (double)area[v * lda] / ((double)n * m);
     dp[v * ld_dp] = (float)(g * (double)(grad_out ? grad_out[0] : 1.0f));
 }
 

@@ -18,45 +18,31 @@
 // guarantees.  A round labels a constant fraction of the remaining nodes: O(log N) rounds instead of O(sqrt N)..O(N).
 // Four small launches per round, everything stays on the device; the caller reads back one count.
 #include "tgnn_common.h"
+#include "greedy_rule.h"
 
 namespace tgnn {
 
 constexpr int kGrThreads = 256;
 
-// splitmix64 of (seed, round, node) -> uniform double in [0, 1)
-__device__ __forceinline__ double greedy_uniform(unsigned long long seed, unsigned round, unsigned long long node) {
-    unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (node + 1ull) + 0xD1B54A32D192ED03ull * (unsigned long long)(round + 1u);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (double)(z >> 11) * (1.0 / 9007199254740992.0);
-}
-
-// p_v of the round (algorithms.py:33-34), saved for the next one; flags cleared
+// p_v of the round, saved for the next one; flags cleared
 __global__ void greedy_mean_kernel(const float *__restrict__ prob, int64_t ldp, const int64_t *__restrict__ inverse, int64_t n_sub,
                                    int round, double *__restrict__ saved, double *__restrict__ p, int *__restrict__ flags) {
     for (int64_t i = (int64_t)blockIdx.x * kGrThreads + threadIdx.x; i < n_sub; i += (int64_t)gridDim.x * kGrThreads) {
         const int64_t o = inverse ? inverse[i] : i;
-        const double v = pow(pow(saved[o], (double)(round - 1)) * (double)prob[i * ldp], 1.0 / (double)round);
+        const double v = greedy_mean(saved[o], (double)prob[i * ldp], round);
         saved[o] = v;
         p[i] = v;
-        flags[i] = 0;                                             // bit 0: beaten by a neighbour, bit 1: accepted
+        flags[i] = 0;
     }
 }
-// a directed collision edge (u, v) of the sub-layout: u is beaten when v comes first in the visiting order
+// a directed collision edge (u, v) of the sub-layout: the later of the two in the visiting order is beaten (greedy_beaten_end)
 __global__ void greedy_beaten_kernel(const int64_t *__restrict__ col, int64_t ec, int64_t n_sub, const double *__restrict__ p,
                                      int *__restrict__ flags, int *__restrict__ err) {
     for (int64_t e = (int64_t)blockIdx.x * kGrThreads + threadIdx.x; e < ec; e += (int64_t)gridDim.x * kGrThreads) {
         const int64_t u = col[e], v = col[ec + e];
         if (u < 0 || u >= n_sub || v < 0 || v >= n_sub) { *err = 1; continue; }
         if (u == v) continue;                                     // (GINConv drops self loops; so does the collision test)
-        const double pu = p[u], pv = p[v];
-        // the later of the two in the visiting order is beaten -- marked from EITHER direction of the pair, so that a collision
-        // stored one way only still keeps the two apart WITHIN THIS ROUND.  Labelling follows the stored direction only
-        // (greedy_label_kernel), so the final selection is collision free only when both directions are stored, as the
-        // reference stores them (tile_graph.py:206-207)
-        if (pv > pu || (pv == pu && v < u)) flags[u] = 1;         // (every writer stores the same word)
-        else flags[v] = 1;
+        flags[greedy_beaten_end(u, v, p[u], p[v])] = kGreedyBeaten;   // (every writer stores the same word)
     }
 }
 __global__ void greedy_accept_kernel(const int64_t *__restrict__ inverse, int64_t n_sub, const double *__restrict__ p, int round,
@@ -64,10 +50,10 @@ __global__ void greedy_accept_kernel(const int64_t *__restrict__ inverse, int64_
                                      int *__restrict__ selected, long long *__restrict__ count) {
     int mine = 0;
     for (int64_t i = (int64_t)blockIdx.x * kGrThreads + threadIdx.x; i < n_sub; i += (int64_t)gridDim.x * kGrThreads) {
-        if (flags[i] & 1) continue;
+        if (flags[i] & kGreedyBeaten) continue;
         const int64_t o = inverse ? inverse[i] : i;
-        if (exp((p[i] - 1.0) * 1.0) > greedy_uniform(seed, (unsigned)round, (unsigned long long)o)) {   // (algorithms.py:51)
-            flags[i] = 2;
+        if (greedy_accepts(p[i], seed, round, o)) {
+            flags[i] = kGreedyAccepted;
             alive[o] = 0;
             selected[o] = round;
             ++mine;
@@ -83,88 +69,18 @@ __global__ void greedy_label_kernel(const int64_t *__restrict__ col, int64_t ec,
     for (int64_t e = (int64_t)blockIdx.x * kGrThreads + threadIdx.x; e < ec; e += (int64_t)gridDim.x * kGrThreads) {
         const int64_t u = col[e], v = col[ec + e];
         if (u < 0 || u >= n_sub || v < 0 || v >= n_sub) continue;
-        if (flags[u] & 2) alive[inverse ? inverse[v] : v] = 0;
+        if (flags[u] & kGreedyAccepted) alive[inverse ? inverse[v] : v] = 0;
     }
 }
 
-// [r6] The END of a solve as ONE launch: a sub-layout without adjacency edges (or without collision edges) gets probability 1 for
-// every node from ML_Solver.predict without the network (ml_solver.py:31-32), and so does every sub-layout of it -- the remaining
-// rounds are the four kernels above with prob = 1 on ever smaller sub-layouts.  One block runs them all on the sub-layout it is
-// given: nodes that have left (alive == 0) and the edges at them are skipped instead of compacted away; the geometric mean, the
-// visiting order (ties by node number: compaction keeps the order), the draws (keyed by seed, round and ORIGINAL node number) and
-// the round numbers are those of the round-by-round path, hence the same selection, order and round count.
-constexpr int kFinThreads = 1024;
-constexpr int kFinMaxNodes = 4096;
+// [r6] the END of a solve as ONE launch: greedy_finish_block on the sub-layout as it is given
 __global__ __launch_bounds__(kFinThreads) void greedy_finish_kernel(const int64_t *__restrict__ inverse, int n_sub,
                                                                     const int64_t *__restrict__ col, int64_t ec, int first_round,
                                                                     int max_rounds, unsigned long long seed, double *__restrict__ saved,
                                                                     int *__restrict__ alive, int *__restrict__ selected,
                                                                     long long *__restrict__ count, int *__restrict__ err,
-                                                                    int *__restrict__ out) {   // out[0] rounds run, out[1] nodes left
-    __shared__ double p[kFinMaxNodes];
-    __shared__ __attribute__((aligned(16))) unsigned char flags[kFinMaxNodes];   // bit 0 beaten, bit 1 accepted, bit 2 gone, bit 3 leaving
-    __shared__ int left, accepted;
-    const int tid = threadIdx.x;
-    for (int i = tid; i < n_sub; i += kFinThreads) flags[i] = alive[inverse ? inverse[i] : i] ? 0 : 4;
-    __syncthreads();
-    int round = first_round, rounds_run = 0;
-    for (;; ++round) {
-        if (tid == 0) { left = 0; accepted = 0; }
-        __syncthreads();
-        int mine = 0;
-        for (int i = tid; i < n_sub; i += kFinThreads) {
-            if (flags[i] & 4) continue;
-            ++mine;
-            const int64_t o = inverse ? inverse[i] : i;
-            const double v = pow(pow(saved[o], (double)(round - 1)) * 1.0, 1.0 / (double)round);     // (greedy_mean_kernel, prob = 1)
-            saved[o] = v;
-            p[i] = v;
-            flags[i] = 0;
-        }
-        if (mine) atomicAdd(&left, mine);
-        __syncthreads();
-        if (left == 0 || rounds_run >= max_rounds) break;    // (uniform)
-        ++rounds_run;
-        for (int64_t e = tid; e < ec; e += kFinThreads) {      // greedy_beaten_kernel
-            const int64_t u = col[e], v = col[ec + e];
-            if (u < 0 || u >= n_sub || v < 0 || v >= n_sub) { *err = 1; continue; }
-            if (u == v || ((flags[u] | flags[v]) & 4)) continue;
-            const double pu = p[u], pv = p[v];
-            if (pv > pu || (pv == pu && v < u)) atomicOr(reinterpret_cast<unsigned *>(flags) + (u >> 2), 1u << (8 * (u & 3)));
-            else atomicOr(reinterpret_cast<unsigned *>(flags) + (v >> 2), 1u << (8 * (v & 3)));
-        }
-        __syncthreads();
-        int acc = 0;
-        for (int i = tid; i < n_sub; i += kFinThreads) {       // greedy_accept_kernel
-            if (flags[i] & 5) continue;
-            const int64_t o = inverse ? inverse[i] : i;
-            if (exp((p[i] - 1.0) * 1.0) > greedy_uniform(seed, (unsigned)round, (unsigned long long)o)) {
-                flags[i] |= 2;
-                alive[o] = 0;
-                selected[o] = round;
-                ++acc;
-            }
-        }
-        if (acc) atomicAdd(&accepted, acc);
-        __syncthreads();
-        for (int64_t e = tid; e < ec; e += kFinThreads) {      // greedy_label_kernel
-            const int64_t u = col[e], v = col[ec + e];
-            if (u < 0 || u >= n_sub || v < 0 || v >= n_sub) continue;
-            if ((flags[u] & 2) && !(flags[v] & 4)) {
-                alive[inverse ? inverse[v] : v] = 0;
-                atomicOr(reinterpret_cast<unsigned *>(flags) + (v >> 2), 8u << (8 * (v & 3)));   // bit 3: leaves behind this round
-            }
-        }
-        __syncthreads();
-        for (int i = tid; i < n_sub; i += kFinThreads)
-            if (flags[i] & (2 | 8)) flags[i] = 4;
-        if (tid == 0 && accepted) atomicAdd(reinterpret_cast<unsigned long long *>(count), (unsigned long long)accepted);
-        __syncthreads();
-    }
-    if (tid == 0) {
-        out[0] = rounds_run;
-        out[1] = left;
-    }
+                                                                    int *__restrict__ out) {
+    greedy_finish_block<false>(inverse, n_sub, n_sub, col, ec, first_round, max_rounds, seed, saved, alive, selected, count, err, out);
 }
 
 }  // namespace tgnn
@@ -174,7 +90,7 @@ using namespace tgnn;
 extern "C" int64_t tgnn_greedy_finish_max_nodes(void) { return kFinMaxNodes; }
 
 /* The remaining rounds of a greedy solve on a sub-layout whose nodes all get probability 1 (no adjacency edge or no collision edge
- * left: ml_solver.py:31-32) as one launch; see greedy_finish_kernel.  n_sub <= tgnn_greedy_finish_max_nodes().  out [2] (device):
+ * left: ml_solver.py:31-32) as one launch; see greedy_finish_block (greedy_rule.h).  n_sub <= tgnn_greedy_finish_max_nodes().  out [2] (device):
  * rounds run (first_round, first_round + 1, ...), nodes still unlabelled (0 unless max_rounds ran out). */
 extern "C" int tgnn_greedy_finish(const int64_t *inverse, int64_t n_sub, const int64_t *col_edge_index, int64_t n_col_edges,
                                   int32_t first_round, int32_t max_rounds, uint64_t seed, double *prob_saved, int32_t *alive,

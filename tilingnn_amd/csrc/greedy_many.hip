@@ -18,67 +18,17 @@
 // offset tables or from the sub-layout counts; thread 0 bisects, the block reads the answer from LDS).  The host only knows the
 // totals, so the grid is an upper bound (total / kChunk + K) and surplus blocks leave at once.
 //
-// EQUALITY.  Per layout every entry computes exactly what its single-layout counterpart computes: compaction keeps ascending
-// order (block scans, chunk bases from a per-layout scan), the acceptance uses the same expressions (pow / exp in fp64, the
-// same counter-based draw keyed by (seed_k, round, local original node)), the score sums run over the same fixed tree (same
-// number of blocks per layout, same strides, same reduction).  The only atomics add integers (n_selected) or store one value.
-// Every offset and index read from the device is range-checked: a bad one sets the layout's error word and is skipped.
+// EQUALITY.  Per layout every entry computes exactly what its single-layout counterpart computes, because both call the same
+// code: the acceptance rule and the finishing block of greedy_rule.h (mean, visiting order, test, draw keyed by (seed_k, round,
+// local original node)), the block count, per-thread sums, reductions and final formula of loss_sums.h (same number of blocks
+// per layout, same strides, same fixed tree).  Compaction keeps ascending order (block scans, chunk bases from a per-layout
+// scan).  The only atomics add integers (n_selected) or store one value.  Every offset and index read from the device is
+// range-checked (many_desc.h): a bad one sets the layout's error word and is skipped.
 #include "tgnn_common.h"
+#include "greedy_rule.h"
+#include "loss_sums.h"
 
 namespace tgnn {
-
-constexpr int kMnThreads = 256;
-constexpr int kMnSub = 4;                                   // sub-chunks of kMnThreads items per block
-constexpr int kChunk = kMnThreads * kMnSub;
-
-struct ManyDesc {
-    int K;
-    const int64_t *ptr[3];                                  // node / adjacency / collision offset tables [K + 1] (NULL: set unused)
-    int64_t total[3];                                       // sizes of the packed arrays (host-known)
-    const int32_t *active;                                  // [K] or NULL = every layout takes part
-    const int64_t *counts;                                  // [K][3] sub-layout sizes, or NULL = the layouts' full sizes
-};
-
-// full size of set `s` of layout k, 0 (and bad = true) when the offset table is not 0 <= ptr[k] <= ptr[k + 1] <= total
-__host__ __device__ __forceinline__ int64_t many_full_size(const ManyDesc &d, int s, int k, bool &bad) {
-    const int64_t a = d.ptr[s][k], b = d.ptr[s][k + 1];
-    if (a < 0 || b < a || b > d.total[s] || b - a >= (1ll << 31) - 1) { bad = true; return 0; }
-    return b - a;
-}
-// the size this call works on: 0 for an inactive layout; the sub-layout count (checked against the full size) when counts are given
-__host__ __device__ __forceinline__ int64_t many_size(const ManyDesc &d, int s, int k, bool &bad) {
-    if (d.active && d.active[k] == 0) return 0;
-    const int64_t full = many_full_size(d, s, k, bad);
-    if (!d.counts) return full;
-    const int64_t c = d.counts[(int64_t)k * 3 + s];
-    if (c < 0 || c > full) { bad = true; return 0; }
-    return c;
-}
-
-// ---- the unsupervised loss of K layouts (loss.hip per layout): what a layout contributes, where its arrays start.  Host and
-// device: scratch/loss_many_host_check.cpp walks these on random offset tables under AddressSanitizer.
-struct LossManyView {
-    int64_t n, ec, ea;                                      // sizes this call works on (the sub-layout's with counts)
-    int64_t np, ap, cp;                                     // first node / adjacency edge / collision edge in the packed arrays
-};
-// false: nothing to compute -- inactive or without nodes (bad stays false), or an offset / count out of range (bad = true).
-// Every offset is checked against the packed sizes before it is returned.
-__host__ __device__ __forceinline__ bool loss_many_view(const ManyDesc &d, int k, LossManyView &v, bool &bad) {
-    bad = false;
-    v.n = many_size(d, 0, k, bad);
-    v.ea = many_size(d, 1, k, bad);
-    v.ec = many_size(d, 2, k, bad);
-    if (bad || v.n == 0) return false;
-    v.np = d.ptr[0][k]; v.ap = d.ptr[1][k]; v.cp = d.ptr[2][k];
-    return true;
-}
-// loss.hip: loss_blocks(n, ec, ea)
-__host__ __device__ __forceinline__ int loss_many_blocks(int64_t n, int64_t ec, int64_t ea) {
-    int64_t work = n > ec ? n : ec;
-    if (ea > work) work = ea;
-    int64_t b = (work + kChunk - 1) / kChunk;
-    return (int)(b < 1 ? 1 : (b > 512 ? 512 : b));
-}
 
 // exclusive scan of one int per thread over the block (kMnThreads = 4 wavefronts); sh: >= 4 ints of LDS
 __device__ __forceinline__ int block_excl_scan(int v, int *sh, int &total) {
@@ -99,8 +49,8 @@ __device__ __forceinline__ int block_excl_scan(int v, int *sh, int &total) {
 }
 
 // start[s * (K + 1) + k] = number of blocks of set s in front of layout k (start[..K] = all of them).  mode 0: chunks of kChunk
-// items; mode 1 (set 0 only): the block count of the score sums, loss.hip: loss_blocks(n, 0, ea); mode 2 (set 0 only): the block
-// count of the unsupervised loss, loss_blocks(n, ec, ea) over the sizes this call works on (0 for a layout without nodes).
+// items; mode 1 (set 0 only): the block count of the score sums, loss_blocks(n, 0, ea); mode 2 (set 0 only): the block count
+// of the unsupervised loss, loss_blocks(n, ec, ea) over the sizes this call works on (0 for a layout without nodes).
 __global__ __launch_bounds__(kMnThreads) void many_plan_kernel(ManyDesc d, int n_sets, int mode, int *__restrict__ start,
                                                                int *__restrict__ err) {
     __shared__ int sh[4];
@@ -116,11 +66,10 @@ __global__ __launch_bounds__(kMnThreads) void many_plan_kernel(ManyDesc d, int n
                     blocks = (int)((many_size(d, s, k, bad) + kChunk - 1) / kChunk);
                 } else if (mode == 2) {
                     LossManyView v;
-                    blocks = loss_many_view(d, k, v, bad) ? loss_many_blocks(v.n, v.ec, v.ea) : 0;
+                    blocks = loss_many_view(d, k, v, bad) ? loss_blocks(v.n, v.ec, v.ea) : 0;
                 } else if (!(d.active && d.active[k] == 0)) {
                     const int64_t n = many_full_size(d, 0, k, bad), ea = many_full_size(d, 1, k, bad);
-                    int64_t b = ((n > ea ? n : ea) + kChunk - 1) / kChunk;
-                    blocks = bad ? 0 : (int)(b < 1 ? 1 : (b > 512 ? 512 : b));
+                    blocks = bad ? 0 : loss_blocks(n, 0, ea);
                 }
                 if (bad) err[k] = 1;
             }
@@ -268,15 +217,6 @@ __global__ __launch_bounds__(kMnThreads) void compact_scatter_kernel(ManyDesc d,
 }
 
 // ------------------------------------------------------------------------------------------ acceptance (greedy.hip, per layout)
-// splitmix64 of (seed, round, node) -> uniform double in [0, 1): greedy.hip's greedy_uniform
-__device__ __forceinline__ double many_uniform(unsigned long long seed, unsigned round, unsigned long long node) {
-    unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (node + 1ull) + 0xD1B54A32D192ED03ull * (unsigned long long)(round + 1u);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (double)(z >> 11) * (1.0 / 9007199254740992.0);
-}
-
 struct RoundArgs {
     const float *const *prob;                               // [K] device pointers (NULL entry: probability 1 for every node)
     int64_t ldp;
@@ -313,19 +253,19 @@ __global__ __launch_bounds__(kMnThreads) void round_step_kernel(ManyDesc d, Roun
             const int64_t o = inverse[i];
             if (o < 0 || o >= n_k) {                          // never accepted
                 a.err[k] = 1;
-                if (step == 0) { p[i] = 0.0; flags[i] = 1; }
+                if (step == 0) { p[i] = 0.0; flags[i] = kGreedyBeaten; }
                 continue;
             }
             if (step == 0) {
                 const double pr = prob ? (double)prob[i * a.ldp] : (double)1.0f;
-                const double v = pow(pow(a.saved[np + o], (double)(a.round - 1)) * pr, 1.0 / (double)a.round);
+                const double v = greedy_mean(a.saved[np + o], pr, a.round);
                 a.saved[np + o] = v;
                 p[i] = v;
-                flags[i] = 0;                                 // bit 0: beaten by a neighbour, bit 1: accepted
+                flags[i] = 0;
             } else {
-                if (flags[i] & 1) continue;
-                if (exp((p[i] - 1.0) * 1.0) > many_uniform(seed, (unsigned)a.round, (unsigned long long)o)) {
-                    flags[i] = 2;
+                if (flags[i] & kGreedyBeaten) continue;
+                if (greedy_accepts(p[i], seed, a.round, o)) {
+                    flags[i] = kGreedyAccepted;
                     a.alive[np + o] = 0;
                     a.selected[np + o] = a.round;
                     ++mine;
@@ -349,19 +289,15 @@ __global__ __launch_bounds__(kMnThreads) void round_step_kernel(ManyDesc d, Roun
         if (u < 0 || u >= n_sub || v < 0 || v >= n_sub) { a.err[k] = 1; continue; }
         if (step == 1) {
             if (u == v) continue;
-            const double pu = p[u], pv = p[v];
-            if (pv > pu || (pv == pu && v < u)) flags[u] = 1;  // (every writer stores the same word)
-            else flags[v] = 1;
-        } else if (flags[u] & 2) {
+            flags[greedy_beaten_end(u, v, p[u], p[v])] = kGreedyBeaten;   // (every writer stores the same word)
+        } else if (flags[u] & kGreedyAccepted) {
             const int64_t o = inverse[v];
             if (o >= 0 && o < n_k) a.alive[np + o] = 0;
         }
     }
 }
 
-// greedy.hip's greedy_finish_kernel, one block per layout whose finish word is set
-constexpr int kFinThreads = 1024;
-constexpr int kFinMaxNodes = 4096;                          // == tgnn_greedy_finish_max_nodes()
+// greedy_finish_block on layout k's own arrays, one block per layout whose finish word is set
 __global__ __launch_bounds__(kFinThreads) void finish_many_kernel(ManyDesc d, const int32_t *__restrict__ finish,
                                                                   const int64_t *__restrict__ inverse_all,
                                                                   const int64_t *__restrict__ col_all, int first_round, int max_rounds,
@@ -369,96 +305,21 @@ __global__ __launch_bounds__(kFinThreads) void finish_many_kernel(ManyDesc d, co
                                                                   double *__restrict__ saved_all, int *__restrict__ alive_all,
                                                                   int *__restrict__ selected_all, long long *__restrict__ count_all,
                                                                   int *__restrict__ err_all, int *__restrict__ out_all) {
-    __shared__ double p[kFinMaxNodes];
-    __shared__ __attribute__((aligned(16))) unsigned char flags[kFinMaxNodes];   // bit 0 beaten, bit 1 accepted, bit 2 gone, bit 3 leaving
-    __shared__ int left, accepted, bad_inverse;
-    const int k = blockIdx.x, tid = threadIdx.x;
+    const int k = blockIdx.x;
     if (finish[k] == 0) return;
     int *out = out_all + 2 * k, *err = err_all + k;
     bool bad = false;
     const int64_t n64 = many_size(d, 0, k, bad), n_k = many_full_size(d, 0, k, bad), ec = many_size(d, 2, k, bad);
     if (bad || n64 > kFinMaxNodes) {                          // (uniform over the block)
-        if (tid == 0) { *err = 1; out[0] = 0; out[1] = (int)(n64 > 0x7fffffff ? 0x7fffffff : n64); }
+        if (threadIdx.x == 0) { *err = 1; out[0] = 0; out[1] = (int)(n64 > 0x7fffffff ? 0x7fffffff : n64); }
         return;
     }
-    const int n_sub = (int)n64;
     const int64_t np = d.ptr[0][k];
-    const int64_t *inverse = inverse_all + np, *col = col_all + 2 * d.ptr[2][k];
-    double *saved = saved_all + np;
-    int *alive = alive_all + np, *selected = selected_all + np;
-    long long *count = count_all + k;
-    const unsigned long long seed = seeds[k];
-    if (tid == 0) bad_inverse = 0;
-    __syncthreads();
-    for (int i = tid; i < n_sub; i += kFinThreads) {
-        const int64_t o = inverse[i];
-        if (o < 0 || o >= n_k) { bad_inverse = 1; flags[i] = 4; continue; }
-        flags[i] = alive[o] ? 0 : 4;
-    }
-    __syncthreads();
-    if (bad_inverse && tid == 0) *err = 1;
-    int round = first_round, rounds_run = 0;
-    for (;; ++round) {
-        if (tid == 0) { left = 0; accepted = 0; }
-        __syncthreads();
-        int mine = 0;
-        for (int i = tid; i < n_sub; i += kFinThreads) {
-            if (flags[i] & 4) continue;
-            ++mine;
-            const int64_t o = inverse[i];
-            const double v = pow(pow(saved[o], (double)(round - 1)) * 1.0, 1.0 / (double)round);     // (greedy_mean_kernel, prob = 1)
-            saved[o] = v;
-            p[i] = v;
-            flags[i] = 0;
-        }
-        if (mine) atomicAdd(&left, mine);
-        __syncthreads();
-        if (left == 0 || rounds_run >= max_rounds) break;    // (uniform)
-        ++rounds_run;
-        for (int64_t e = tid; e < ec; e += kFinThreads) {      // greedy_beaten_kernel
-            const int64_t u = col[e], v = col[ec + e];
-            if (u < 0 || u >= n_sub || v < 0 || v >= n_sub) { *err = 1; continue; }
-            if (u == v || ((flags[u] | flags[v]) & 4)) continue;
-            const double pu = p[u], pv = p[v];
-            if (pv > pu || (pv == pu && v < u)) atomicOr(reinterpret_cast<unsigned *>(flags) + (u >> 2), 1u << (8 * (u & 3)));
-            else atomicOr(reinterpret_cast<unsigned *>(flags) + (v >> 2), 1u << (8 * (v & 3)));
-        }
-        __syncthreads();
-        int acc = 0;
-        for (int i = tid; i < n_sub; i += kFinThreads) {       // greedy_accept_kernel
-            if (flags[i] & 5) continue;
-            const int64_t o = inverse[i];
-            if (exp((p[i] - 1.0) * 1.0) > many_uniform(seed, (unsigned)round, (unsigned long long)o)) {
-                flags[i] |= 2;
-                alive[o] = 0;
-                selected[o] = round;
-                ++acc;
-            }
-        }
-        if (acc) atomicAdd(&accepted, acc);
-        __syncthreads();
-        for (int64_t e = tid; e < ec; e += kFinThreads) {      // greedy_label_kernel
-            const int64_t u = col[e], v = col[ec + e];
-            if (u < 0 || u >= n_sub || v < 0 || v >= n_sub) continue;
-            if ((flags[u] & 2) && !(flags[v] & 4)) {
-                alive[inverse[v]] = 0;
-                atomicOr(reinterpret_cast<unsigned *>(flags) + (v >> 2), 8u << (8 * (v & 3)));   // bit 3: leaves behind this round
-            }
-        }
-        __syncthreads();
-        for (int i = tid; i < n_sub; i += kFinThreads)
-            if (flags[i] & (2 | 8)) flags[i] = 4;
-        if (tid == 0 && accepted) atomicAdd(reinterpret_cast<unsigned long long *>(count), (unsigned long long)accepted);
-        __syncthreads();
-    }
-    if (tid == 0) {
-        out[0] = rounds_run;
-        out[1] = left;
-    }
+    greedy_finish_block<true>(inverse_all + np, (int)n64, n_k, col_all + 2 * d.ptr[2][k], ec, first_round, max_rounds, seeds[k],
+                              saved_all + np, alive_all + np, selected_all + np, count_all + k, err, out);
 }
 
 // ------------------------------------------------------------------------------------------ score sums (loss.hip, per layout)
-constexpr int kScoreMaxBlocks = 512;
 __global__ __launch_bounds__(kMnThreads) void score_many_partial_kernel(ManyDesc d, const int *__restrict__ start,
                                                                         const float *__restrict__ predict_all,
                                                                         const float *__restrict__ area_all, int64_t lda,
@@ -472,31 +333,11 @@ __global__ __launch_bounds__(kMnThreads) void score_many_partial_kernel(ManyDesc
     bool bad = false;
     const int64_t n = many_full_size(d, 0, k, bad), ea = many_full_size(d, 1, k, bad);
     const int64_t np = d.ptr[0][k], ap = d.ptr[1][k];
-    const float *predict = predict_all + np, *area = area_all + np * lda, *perim = perim_all + np;
-    const int64_t *adj = adj_all + 2 * ap;
-    const float *len = len_all + ap * ldl;
     double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-    const int64_t stride = (int64_t)nb * kMnThreads, t0 = (int64_t)bl * kMnThreads + threadIdx.x;
-    for (int64_t v = t0; v < n; v += stride) {
-        const float p = predict[v];
-        s0 += (double)(p * area[v * lda]);
-        if (p == 1.0f) s2 += (double)perim[v];
-    }
-    for (int64_t e = t0; e < ea; e += stride) {
-        const int64_t i = adj[e], j = adj[ea + e];
-        if (i < 0 || i >= n || j < 0 || j >= n) { bad = true; continue; }
-        s1 += (double)(predict[i] * predict[j] * len[e * ldl]);
-    }
+    score_accumulate(n, ea, predict_all + np, area_all + np * lda, lda, perim_all + np, adj_all + 2 * ap, len_all + ap * ldl, ldl,
+                     (int64_t)bl * kMnThreads + threadIdx.x, (int64_t)nb * kMnThreads, s0, s1, s2, bad);
     if (bad) err[k] = 1;
-    __shared__ double red[3][kMnThreads];
-    red[0][threadIdx.x] = s0; red[1][threadIdx.x] = s1; red[2][threadIdx.x] = s2;
-    __syncthreads();
-    for (int s = kMnThreads / 2; s >= 1; s >>= 1) {
-        if ((int)threadIdx.x < s)
-            for (int c = 0; c < 3; ++c) red[c][threadIdx.x] += red[c][threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x < 3) partial_all[((int64_t)k * kScoreMaxBlocks + bl) * 3 + threadIdx.x] = red[threadIdx.x][0];
+    loss_block_reduce(s0, s1, s2, partial_all + ((int64_t)k * kLossMaxBlocks + bl) * 3);
 }
 
 __global__ __launch_bounds__(64) void score_many_final_kernel(int K, const int32_t *__restrict__ active, const int *__restrict__ start,
@@ -504,21 +345,12 @@ __global__ __launch_bounds__(64) void score_many_final_kernel(int K, const int32
                                                               double *__restrict__ sums) {
     const int k = blockIdx.x, lane = threadIdx.x;
     if (active && active[k] == 0) return;
-    const int n_blocks = start[k + 1] - start[k];
-    const double *partial = partial_all + (int64_t)k * kScoreMaxBlocks * 3;
-    double s[3] = {0.0, 0.0, 0.0};
-    for (int b = lane; b < n_blocks; b += 64)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) s[c] += partial[(int64_t)b * 3 + c];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int t = 32; t >= 1; t >>= 1) s[c] += __shfl_xor(s[c], t, 64);
-    if (lane < 3) sums[(int64_t)k * 3 + lane] = err[k] ? __longlong_as_double(0x7ff8000000000000ll) : s[lane];
+    double s[3];
+    loss_fold_rows(partial_all + (int64_t)k * kLossMaxBlocks * 3, start[k + 1] - start[k], s);
+    if (lane < 3) sums[(int64_t)k * 3 + lane] = err[k] ? loss_nan() : s[lane];
 }
 
 // ------------------------------------------------------------------------------------------ unsupervised loss (loss.hip, per layout)
-constexpr float kLossManyEps = 1e-7f;                       // loss.hip: kLossEps
 struct LossManyArgs {
     const float *const *probs;                              // [K] device pointers: layout k's [n_k, ldp]
     int64_t ldp;
@@ -533,60 +365,27 @@ struct LossManyArgs {
     double *losses, *terms;
     int32_t *err;
     const int *start;                                       // workspace
-    double *partial;                                        // [K][n_maps][512][3]
+    double *partial;                                        // [K][n_maps][kLossMaxBlocks][3]
 };
 
-// what thread t0 of a grid of `stride` threads adds up: loss_partial_kernel's three loops on one layout's arrays (p: the map's
-// column, area / col / adj / len: the layout's own blocks).  An edge end outside [0, n) is skipped and reported.
-__host__ __device__ __forceinline__ void loss_many_accumulate(const LossManyView &v, const float *p, int64_t ldp, const float *area,
-                                                              int64_t lda, const int64_t *col, const int64_t *adj, const float *len,
-                                                              int64_t ldl, int64_t t0, int64_t stride, double &s_area, double &s_feas,
-                                                              double &s_align, bool &bad) {
-    const int64_t n = v.n, ec = v.ec, ea = v.ea;
-    for (int64_t i = t0; i < n; i += stride) s_area += (double)(area[i * lda] * p[i * ldp]);
-    for (int64_t e = t0; e < ec; e += stride) {
-        const int64_t i = col[e], j = col[ec + e];
-        if (i < 0 || i >= n || j < 0 || j >= n) { bad = true; continue; }
-        float pp = p[i * ldp] * p[j * ldp];
-        pp = fminf(fmaxf(pp, kLossManyEps), 1.0f - kLossManyEps);
-        s_feas += (double)logf(1.0f - pp);
-    }
-    for (int64_t e = t0; e < ea; e += stride) {
-        const int64_t i = adj[e], j = adj[ea + e];
-        if (i < 0 || i >= n || j < 0 || j >= n) { bad = true; continue; }
-        float pp = p[i * ldp] * p[j * ldp] * len[e * ldl];
-        pp = fmaxf(pp, kLossManyEps);
-        s_align += (double)(logf(pp) / 2.302585092994046f);
-    }
-}
-
-// grid = (upper bound of blocks over all layouts, maps); partial[((k * n_maps + m) * 512 + block of the layout) * 3 + {0,1,2}]
+// grid = (upper bound of blocks over all layouts, maps); partial[((k * n_maps + m) * kLossMaxBlocks + block of the layout) * 3 + {0,1,2}]
 __global__ __launch_bounds__(kMnThreads) void loss_many_partial_kernel(ManyDesc d, LossManyArgs a) {
     int k, bl;
     if (!many_find(a.start, d.K, blockIdx.x, k, bl)) return;
     const int nb = a.start[k + 1] - a.start[k], m = blockIdx.y;
     LossManyView v;
     bool bad;
-    if (!loss_many_view(d, k, v, bad) || bl >= kScoreMaxBlocks) return;      // (the plan gives such a layout no block)
+    if (!loss_many_view(d, k, v, bad) || bl >= kLossMaxBlocks) return;      // (the plan gives such a layout no block)
     const float *p = a.probs[k];
     if (!p) {                                               // (uniform over the block)
         if (threadIdx.x == 0) a.err[k] = 1;
         return;
     }
     double s_area = 0.0, s_feas = 0.0, s_align = 0.0;
-    loss_many_accumulate(v, p + m, a.ldp, a.area + v.np * a.lda, a.lda, a.col + 2 * v.cp, a.adj + 2 * v.ap, a.len + v.ap * a.ldl, a.ldl,
-                         (int64_t)bl * kMnThreads + threadIdx.x, (int64_t)nb * kMnThreads, s_area, s_feas, s_align, bad);
+    loss_accumulate(v.n, v.ec, v.ea, p + m, a.ldp, a.area + v.np * a.lda, a.lda, a.col + 2 * v.cp, a.adj + 2 * v.ap, a.len + v.ap * a.ldl,
+                    a.ldl, (int64_t)bl * kMnThreads + threadIdx.x, (int64_t)nb * kMnThreads, s_area, s_feas, s_align, bad);
     if (bad) a.err[k] = 1;
-    __shared__ double red[3][kMnThreads];
-    red[0][threadIdx.x] = s_area; red[1][threadIdx.x] = s_feas; red[2][threadIdx.x] = s_align;
-    __syncthreads();
-    for (int s = kMnThreads / 2; s >= 1; s >>= 1) {
-        if ((int)threadIdx.x < s)
-            for (int c = 0; c < 3; ++c) red[c][threadIdx.x] += red[c][threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x < 3)
-        a.partial[(((int64_t)k * a.n_maps + m) * kScoreMaxBlocks + bl) * 3 + threadIdx.x] = red[threadIdx.x][0];
+    loss_block_reduce(s_area, s_feas, s_align, a.partial + (((int64_t)k * a.n_maps + m) * kLossMaxBlocks + bl) * 3);
 }
 
 // one wavefront per (layout, map): loss_final_kernel on the layout's partial rows
@@ -598,7 +397,7 @@ __global__ __launch_bounds__(64) void loss_many_final_kernel(ManyDesc d, LossMan
     if (!live && !bad) return;                              // inactive or without nodes: the caller's rows stay
     const int64_t row = (int64_t)k * a.n_maps + m;
     if (bad || a.err[k]) {                                  // NaN = "offset, count or edge index out of range"
-        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        const double nan = loss_nan();
         if (lane == 0) {
             if (bad) a.err[k] = 1;
             a.losses[row] = nan;
@@ -606,22 +405,12 @@ __global__ __launch_bounds__(64) void loss_many_final_kernel(ManyDesc d, LossMan
         }
         return;
     }
-    const int n_blocks = a.start[k + 1] - a.start[k];
-    const double *partial = a.partial + row * kScoreMaxBlocks * 3;
-    double s[3] = {0.0, 0.0, 0.0};
-    for (int b = lane; b < n_blocks; b += 64)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) s[c] += partial[(int64_t)b * 3 + c];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int t = 32; t >= 1; t >>= 1) s[c] += __shfl_xor(s[c], t, 64);
+    double s[3];
+    loss_fold_rows(a.partial + row * kLossMaxBlocks * 3, a.start[k + 1] - a.start[k], s);
     if (lane == 0) {
-        const double t0 = log(fmax(s[0] / (double)v.n, (double)kLossManyEps));
-        const double t1 = v.ec > 0 ? s[1] / (double)v.ec : 0.0;
-        const double t2 = v.ea > 0 ? s[2] / (double)v.ea : 0.0;
-        if (a.terms) { a.terms[row * 3] = t0; a.terms[row * 3 + 1] = t1; a.terms[row * 3 + 2] = t2; }
-        a.losses[row] = (1.0 - (double)a.wa * t0) * (1.0 - (double)a.wc * t1) * (1.0 - (double)a.wl * t2);
+        double t[3];
+        a.losses[row] = loss_from_sums(s, v.n, v.ec, v.ea, a.wc, a.wl, a.wa, t);
+        if (a.terms) { a.terms[row * 3] = t[0]; a.terms[row * 3 + 1] = t[1]; a.terms[row * 3 + 2] = t[2]; }
     }
 }
 
@@ -753,7 +542,7 @@ extern "C" int tgnn_greedy_finish_many(int32_t n_layouts, const int32_t *finish,
 
 extern "C" size_t tgnn_solution_score_sums_many_workspace_bytes(int32_t n_layouts) {
     const size_t k = n_layouts > 0 ? (size_t)n_layouts : 1;
-    return align_up((k + 1) * sizeof(int), 256) + align_up(k * kScoreMaxBlocks * 3 * sizeof(double), 256) +
+    return align_up((k + 1) * sizeof(int), 256) + align_up(k * kLossMaxBlocks * 3 * sizeof(double), 256) +
            align_up(k * sizeof(int), 256) + 256;
 }
 
@@ -777,12 +566,12 @@ extern "C" int tgnn_solution_score_sums_many(int32_t n_layouts, const int32_t *a
     const int K = n_layouts;
     Carver cv(ws, ws_bytes);
     int *start = cv.take<int>((size_t)K + 1);
-    double *partial = cv.take<double>((size_t)K * kScoreMaxBlocks * 3);
+    double *partial = cv.take<double>((size_t)K * kLossMaxBlocks * 3);
     int *err = cv.take<int>((size_t)K);
     TGNN_CHECK_HIP(hipMemsetAsync(err, 0, (size_t)K * sizeof(int), s));
     ManyDesc d{K, {node_ptr, adj_ptr, nullptr}, {total_nodes, total_adj_edges, 0}, active, nullptr};
     many_plan_kernel<<<1, kMnThreads, 0, s>>>(d, 1, 1, start, err);
-    // blocks of layout k: clamp(ceil(max(n, ea) / kChunk), 1, 512) <= (n + ea) / kChunk + 1
+    // blocks of layout k: loss_blocks(n, 0, ea) <= (n + ea) / kChunk + 1
     const int ub = many_blocks_ub(total_nodes + total_adj_edges, K);
     score_many_partial_kernel<<<ub, kMnThreads, 0, s>>>(d, start, predict, area_ratio, ld_area, perimeter, adj_edge_index, adj_edge_len,
                                                         ld_len, partial, err);
@@ -793,7 +582,7 @@ extern "C" int tgnn_solution_score_sums_many(int32_t n_layouts, const int32_t *a
 
 extern "C" size_t tgnn_unsupervised_loss_many_workspace_bytes(int32_t n_layouts, int32_t n_maps) {
     const size_t k = n_layouts > 0 ? (size_t)n_layouts : 1, m = n_maps > 0 ? (size_t)n_maps : 1;
-    return align_up((k + 1) * sizeof(int), 256) + align_up(k * m * kScoreMaxBlocks * 3 * sizeof(double), 256) + 256;
+    return align_up((k + 1) * sizeof(int), 256) + align_up(k * m * kLossMaxBlocks * 3 * sizeof(double), 256) + 256;
 }
 
 extern "C" int tgnn_unsupervised_loss_many(int32_t n_layouts, const int32_t *active, const int64_t *node_ptr, const int64_t *adj_ptr,
@@ -821,13 +610,13 @@ extern "C" int tgnn_unsupervised_loss_many(int32_t n_layouts, const int32_t *act
     const int K = n_layouts;
     Carver cv(ws, ws_bytes);
     int *start = cv.take<int>((size_t)K + 1);
-    double *partial = cv.take<double>((size_t)K * n_maps * kScoreMaxBlocks * 3);
+    double *partial = cv.take<double>((size_t)K * n_maps * kLossMaxBlocks * 3);
     TGNN_CHECK_HIP(hipMemsetAsync(err, 0, (size_t)K * sizeof(int32_t), s));
     ManyDesc d{K, {node_ptr, adj_ptr, col_ptr}, {total_nodes, total_adj_edges, total_col_edges}, active, counts};
     LossManyArgs a{probs, ld_probs, n_maps, area_ratio, ld_area, adj_edge_index, adj_edge_len, ld_len, col_edge_index,
                    collision_weight, align_length_weight, avg_area_weight, losses, terms, err, start, partial};
     many_plan_kernel<<<1, kMnThreads, 0, s>>>(d, 1, 2, start, err);
-    // blocks of layout k: clamp(ceil(max(n, ec, ea) / kChunk), 1, 512) <= (n + ec + ea) / kChunk + 1
+    // blocks of layout k: loss_blocks(n, ec, ea) <= (n + ec + ea) / kChunk + 1
     const int ub = many_blocks_ub(total_nodes + total_adj_edges + total_col_edges, K);
     loss_many_partial_kernel<<<dim3(ub, n_maps), kMnThreads, 0, s>>>(d, a);
     loss_many_final_kernel<<<dim3(K, n_maps), 64, 0, s>>>(d, a);
