@@ -1372,6 +1372,58 @@ int tgnn_hole_sweep_many(const double *ring_xy, const int32_t *ring_ptr, int64_t
                          int32_t *killed_out /* [N] */, int32_t *trace_out /* [V][2] */, int32_t *err_out /* [K] */, void *ws,
                          size_t ws_bytes, tgnn_stream_t stream);
 
+/* ---- one step of the tree search: the sweeps of K branches of ONE layout cut from one complete graph (csrc/tree_sweep.hip): the
+ * reference's solve_by_treesearch (util/algorithms.py:138-157) with its hole veto (:150-152), one block per branch, each branch a
+ * sequential walk over its own sampled order from its own copy of a queued state (csrc/tree_sweep_step.h has the per-visit rule).
+ * One call per step of the search, no host synchronisation, integer sums only, every output word of a branch that ran written by
+ * the call: the same bytes on every run.  Every array is device memory.
+ *   ring_xy, ring_ptr, touch_ptr, touch_idx, tol, (dir_x, dir_y): as for tgnn_hole_sweep_many.  With check_holes == 0 the four
+ *   pointers may ALL be NULL: then no tile state is kept (tile_of_node, tile_alive, label, chi_cache are not looked at and may be
+ *   NULL).  With check_holes == 0 and the geometry given the tile state is kept all the same, and no ring is read.
+ *   Constant over a search: tile_of_node [n_nodes], the layout's inverse_index; nbr_ptr [n_nodes + 1], nbr_idx [n_nbr]: the
+ *   collision neighbours of every node as CSR in edge order (nbr_idx may be NULL when n_nbr is 0).
+ *   The state pool, the caller's, n_slots slots: unlabelled [S][n_nodes]; tile_alive, label, chi_cache [S][n_tiles], per slot
+ *   with the conventions of tgnn_hole_sweep_many.  A search starts from a slot of all ones, all zeros, all -1 and all
+ *   TGNN_SWEEP_CHI_UNKNOWN.
+ *   Per call: parent_slot [K], slot [K]: branch k walks on slot[k], which the call first makes a copy of parent_slot[k]'s four
+ *   rows.  THE SLOT CONTRACT: the child slots of a call are pairwise distinct; a child may be its own parent's slot only when no
+ *   other branch of the call names that parent; every other child slot differs from every parent slot of the call.  The call
+ *   checks ranges only: a slot outside [0, n_slots) sets TGNN_TOPO_ERR_INDEX for its branch, which then touches no slot.  A
+ *   parent that is not reused is not written.
+ *   visit_ptr [K + 1]; visit_node [V], the layout's nodes in the branch's sampled order; p [V] fp64, prob_m of that position;
+ *   u [V] fp64, branch k's uniforms from u[visit_ptr[k]] on, consumed in order.
+ *   Per position, in order: a node that is no longer unlabelled consumes the next u: u < p passes over it (SKIPPED), else the
+ *   walk ends (BREAK); with check_holes, a node whose tile has d holes > 0 under the slot's tile_alive is passed over, NO u
+ *   (VETOED); every other node is accepted, NO u: it leaves unlabelled, its tile enters tile_alive, the labels are brought up to
+ *   date and the node's unlabelled collision neighbours are cleared.  TGNN_SWEEP_REJECTED does not occur.
+ *   stats_out [K][8] int32 = TGNN_TREE_STAT_*: positions reached, vetoes, u consumed, accepted, killed, skipped, 0, 0.
+ *   accepted_out [V], killed_out [V]: from [visit_ptr[k]] on, the accepted nodes in order and the cleared neighbours by acceptance
+ *   then row order, each filled up with -1 to the list's length; both together never exceed it (a table that would make them is
+ *   reported).  trace_out [V][2] = {TGNN_SWEEP_*, d holes} of every position ({NOT_REACHED, 0} behind the walk's end).
+ *   err_out [K] gets the branch's TGNN_TOPO_ERR_* bits (0: none): a slot, node, tile, contact or collision entry outside its
+ *   array, or more than 16 tiles around a point counting the visited tile.  The branch ends where the error shows, nothing is
+ *   read or written out of range; its other outputs and its slot are then not to be used.
+ *   ws: tgnn_tree_sweep_workspace_bytes(K) = 4 K bytes, 4-byte aligned; its contents on entry do not matter.
+ *   K, n_nodes or n_visit == 0: nothing is queued. */
+#define TGNN_SWEEP_SKIPPED 5
+#define TGNN_TREE_STAT_VISITED 0
+#define TGNN_TREE_STAT_VETOES 1
+#define TGNN_TREE_STAT_DRAWS 2
+#define TGNN_TREE_STAT_ACCEPTED 3
+#define TGNN_TREE_STAT_KILLED 4
+#define TGNN_TREE_STAT_SKIPPED 5
+#define TGNN_TREE_STAT_WORDS 8
+size_t tgnn_tree_sweep_workspace_bytes(int64_t n_branches);
+int tgnn_tree_sweep_many(const double *ring_xy, const int32_t *ring_ptr, int64_t n_tiles, const int32_t *touch_ptr,
+                         const int32_t *touch_idx, double tol, double dir_x, double dir_y, int64_t n_nodes,
+                         const int32_t *tile_of_node, const int32_t *nbr_ptr, const int32_t *nbr_idx, int64_t n_nbr,
+                         int64_t n_slots, int32_t *unlabelled, int32_t *tile_alive, int32_t *label, int32_t *chi_cache,
+                         int64_t n_branches, const int32_t *parent_slot, const int32_t *slot, const int32_t *visit_ptr,
+                         const int32_t *visit_node, const double *p, const double *u, int64_t n_visit, int32_t check_holes,
+                         int32_t *stats_out /* [K][8] */, int32_t *accepted_out /* [V] */, int32_t *killed_out /* [V] */,
+                         int32_t *trace_out /* [V][2] */, int32_t *err_out /* [K] */, void *ws, size_t ws_bytes,
+                         tgnn_stream_t stream);
+
 /* ---- the outline of the union of the alive tiles of K masks (csrc/union_contour.hip): what the reference's
  * BrickLayout.get_selected_tiles_union_polygon (tiling/brick_layout.py:223-227) returns for a solved layout.  One call for all K
  * masks, no host synchronisation, no floating-point atomics: the same bits in every output on every run.  For masks whose alive

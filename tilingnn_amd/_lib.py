@@ -170,6 +170,9 @@ def _load() -> C.CDLL:
         "tgnn_hole_sweep_workspace_bytes": (sz, [i64]),
         "tgnn_hole_sweep_many": (C.c_int, [p, p, i64, p, p, C.c_double, C.c_double, C.c_double, i64, p, i64, p, p, p, i64, p, p, p, p,
                                            p, p, p, p, p, i64, p, p, p, p, p, p, sz, p]),
+        "tgnn_tree_sweep_workspace_bytes": (sz, [i64]),
+        "tgnn_tree_sweep_many": (C.c_int, [p, p, i64, p, p, C.c_double, C.c_double, C.c_double, i64, p, p, p, i64, i64, p, p, p, p,
+                                           i64, p, p, p, p, p, p, i64, i32, p, p, p, p, p, p, sz, p]),
         "tgnn_union_contour_workspace_bytes": (sz, [i64, i64, i64]),
         "tgnn_union_contour": (C.c_int, [p, p, i64, p, p, p, p, p, i64, C.c_double, i64, i64, p, p, p, p, p, p, p, p, sz, p]),
         "tgnn_batch_union": (C.c_int, [p] * 10 + [i32, i32, i32, p, p, i32, p, p, p, p, p]),
@@ -338,6 +341,7 @@ EXPORTED_SYMBOLS = (
     "tgnn_tiles_in_region", "tgnn_region_edge_counts", "tgnn_union_area_workspace_bytes", "tgnn_union_area", "tgnn_batch_union",
     "tgnn_union_topology_workspace_bytes", "tgnn_union_topology", "tgnn_union_contour_workspace_bytes", "tgnn_union_contour",
     "tgnn_union_hole_delta_workspace_bytes", "tgnn_union_hole_delta", "tgnn_hole_sweep_workspace_bytes", "tgnn_hole_sweep_many",
+    "tgnn_tree_sweep_workspace_bytes", "tgnn_tree_sweep_many",
     "tgnn_transpose", "tgnn_swap_leading", "tgnn_gin_aggregate", "tgnn_sigmoid_bwd", "tgnn_add_into", "tgnn_reduce_workspace_bytes", "tgnn_colsum",
     "tgnn_bn_bwd_reduce", "tgnn_bn_bwd_apply", "tgnn_merge_bwd_reduce", "tgnn_wgrad_workspace_bytes", "tgnn_wgrad", "tgnn_wgrad_slots",
     "tgnn_sigmoid_mlp_bwd_workspace_bytes", "tgnn_sigmoid_mlp_bwd",

@@ -10,6 +10,7 @@
                                                            layout on the GPU; `greedy_solver=` swaps in the reference's)
     solve_many(brick_layouts)        Tiling-Shape.py:60-64 (the crop loop: K device-greedy solves in one loop)
     solve_many_hole_free(layouts)    the same crop loop with the hole veto of algorithms.py:150-152 in every solve
+    solve_tree(brick_layout)         algorithms.py:66-181  (the tree search; `predict_top_maps` scores its popped states)
 The debug dumps stay with the reference.
 
 `brick_layout` is duck-typed exactly as the reference uses it: `.node_feature`,
@@ -136,6 +137,49 @@ class ML_Solver:
             at += n
         return out
 
+    def predict_top_maps(self, sub_layouts, top_k):
+        """What the tree search asks per popped state (tilingnn_amd.util.algorithms.solve_by_treesearch; the repair of the
+        reference's 4-argument get_best_prob_map, algorithms.py:105): for several device-resident layouts at once, per layout a
+        numpy float32 [n, min(top_k, M)] array -- the probabilities of its min(top_k, M) best maps, best first, "best" being
+        `np.argsort` of the per-map unsupervised loss.  The forwards side by side as in `predict_many` (honouring
+        `union_forward` / `union_prep`, the checks of `forward_checked` once), the ranking of every layout from ONE
+        `tgnn_unsupervised_loss_many` call, ONE read-back of the probabilities.  A layout with one edge set left gets ones
+        without the network (ml_solver.py:31-32).  Column 0 is bit for bit what `predict` returns."""
+        from ...util import algorithms as alg
+        if top_k < 1:
+            raise ValueError("predict_top_maps: top_k is at least 1")
+        subs = list(sub_layouts)
+        out = [None] * len(subs)
+        need = [i for i, s in enumerate(subs) if not (self._no_edges(s.collide_edge_index) or self._no_edges(s.align_edge_index))]
+        for i, s in enumerate(subs):
+            if i not in need:
+                out[i] = np.ones((int(s.node_feature.shape[0]), min(int(top_k), int(self.num_prob_maps))), dtype=np.float32)
+        if not need:
+            return out
+        views = [subs[i] for i in need]
+        if hasattr(self.network, "forward_many"):
+            preds = alg._forward_many_checked(self.network, views, 3, bool(self.union_forward), bool(self.union_prep))
+        else:
+            run = getattr(self.network, "forward_checked", None) or self.network
+            preds = [run(x=v.node_feature, adj_e_index=v.align_edge_index, adj_e_features=v.align_edge_features,
+                         col_e_idx=v.collide_edge_index, col_e_features=v.collide_edge_features)[0] for v in views]
+        n_maps = int(preds[0].shape[1])
+        keep = min(int(top_k), n_maps)
+        ranks = {j: np.arange(1) for j in range(len(views))}
+        if n_maps > 1:
+            ranks = alg._prob_map_ranks_many(alg.PackedLayouts(views, self.device), list(range(len(views))), preds)
+        picks = [torch.from_numpy(np.ascontiguousarray(ranks[j][:keep])).to(preds[j].device) for j in range(len(views))] if n_maps > 1 else None
+        flat = torch.cat([(p if picks is None else p[:, picks[j]]).detach().reshape(-1) for j, p in enumerate(preds)])
+        host = torch.empty(flat.shape, dtype=flat.dtype, pin_memory=True)
+        host.copy_(flat, non_blocking=True)
+        torch.cuda.current_stream(flat.device).synchronize()
+        host, at = host.numpy(), 0
+        for j, i in enumerate(need):
+            n = int(preds[j].shape[0])
+            out[i] = host[at:at + n * keep].reshape(n, keep).copy()
+            at += n * keep
+        return out
+
     def _best_prob_map(self, predictions, brick_layout):
         """get_best_prob_map (ml_solver.py:133-136): argsort of the per-map unsupervised loss.
         With one probability map -- the only configuration the reference ever constructs
@@ -248,6 +292,25 @@ class ML_Solver:
             output_layout.predict_order = order
             output_layout.predict = selection
             output_layout.predict_probs = probs if probs is not None else self.predict(layout)
+            out.append((output_layout, score))
+        return out
+
+    def solve_tree(self, brick_layout, **options):
+        """The tree search of the reference (util/algorithms.py:66-181) on one layout:
+        tilingnn_amd.util.algorithms.solve_by_treesearch(self, brick_layout, **options) -- top_k, check_holes, max_predictions,
+        time_limit, beam, roots, seed, literal -- with the branch sweeps on the device (csrc/tree_sweep.hip).  Returns a list of
+        (output_layout, score), one per distinct finished tiling, best first; `predict`, `predict_order` and `predict_probs` as
+        `solve` sets them.  `last_predict_cnt`: the states the search scored."""
+        from ...util.algorithms import solve_by_treesearch
+        options.setdefault("score_fn", self._score_fn)
+        results, self.last_predict_cnt = solve_by_treesearch(self, brick_layout, **options)
+        probs = self.predict(brick_layout) if results else None
+        out = []
+        for selection, score, order in results:
+            output_layout = deepcopy(brick_layout)
+            output_layout.predict_order = order
+            output_layout.predict = selection
+            output_layout.predict_probs = probs
             out.append((output_layout, score))
         return out
 

@@ -25,6 +25,10 @@ csrc/hole_sweep.hip): one launch and one read-back per ROUND, the same decisions
 
 `solve_many_by_device_greedy` runs K such device-greedy solves (the crops of one silhouette, Tiling-Shape.py:60-64) in one loop
 over `PackedLayouts`: one compaction, one read-back and one acceptance call per round for all of them (csrc/greedy_many.hip).
+
+`solve_by_treesearch` is the reference's tree search (algorithms.py:66-181), the consumer the hole veto was written for: a queue
+of partial selections, one branch per top probability map of a popped state, every distinct finished tiling returned; the
+branches of a step are swept side by side on the device (`DeviceTreeSweep`, csrc/tree_sweep.hip: a block per branch).
 """
 import ctypes as C
 
@@ -754,6 +758,21 @@ def _best_prob_maps_many(pk, members, outs, buffers, counts):
     return {k: int(np.argsort(results[k][2])[0]) for k in members}
 
 
+def _prob_map_ranks_many(pk, members, outs):
+    """The whole ranking `_best_prob_maps_many` takes the head of: per layout `np.argsort` of its per-map unsupervised losses
+    (float32, as `ML_Solver.get_unsupervised_losses_from_layout` gives them), from ONE `tgnn_unsupervised_loss_many` call and one
+    read-back.  -> {layout: map indices, best first}.  What `ML_Solver.predict_top_maps` hands the tree search."""
+    from ..solver.ml_solver.losses import Losses
+    probs, live = [None] * pk.k, [False] * pk.k
+    for k, out in zip(members, outs):
+        probs[k], live[k] = out, True
+    m = int(outs[0].shape[1])
+    buf, losses, terms, err = Losses.many_outputs(pk.k, m, pk.device)
+    Losses.unsupervised_losses_many(probs, pk, buffers=None, counts=None, active=live, out=(losses, terms, err))
+    results = Losses.results_many(*Losses.read_back_many(buf, pk.k, m), present=live)
+    return {k: np.argsort(results[k][2]) for k in members}
+
+
 def _scores_many(pk, selections, originals, score_fn, device):
     """`create_score` for K selections: `score_fn` when given; `Losses.solution_score` -- its three sums for all layouts in one
     `tgnn_solution_score_sums_many` call, over the single-layout call's summation tree -- for the layouts that carry their
@@ -935,3 +954,335 @@ def solve_many_hole_free(ml_solver, layouts, seeds, score_fn=None, max_rounds=10
     fn.last_rounds, fn.last_vetoes, fn.last_sweep_calls = rounds, [int(v) for v in dsw.vetoes], dsw.calls
     fn.last_first_probs = first_probs
     return results
+
+
+# ------------------------------------------------------------------------------------------------ the tree search
+TREE_EPS = 1e-7                                                 # (the reference's EPS, algorithms.py:16)
+TREE_ALPHA = 100.0                                              # (get_nodes_order_array, :228)
+
+
+def _tree_sampling_probabilities(prob_m):
+    """get_nodes_order_array (:228-231): softmax(100 prob_m) clipped to [1e-7, 1 - 1e-7] and normalised -- with the builtin `sum`
+    the reference uses, whose order of additions is not numpy's."""
+    x = prob_m * TREE_ALPHA
+    x = x - np.max(x)
+    exp_x = np.exp(x)
+    sampling_prob = np.clip(exp_x / np.sum(exp_x), a_min=1e-7, a_max=1 - 1e-7)
+    return sampling_prob / sum(sampling_prob)
+
+
+class DeviceTreeSweep:
+    """The branch sweeps of `solve_by_treesearch` ON THE DEVICE (csrc/tree_sweep.hip: tgnn_tree_sweep_many), a sibling of
+    `DeviceHoleSweep`: K branches of ONE layout per call, a block per branch, each on its own slot of a state pool.  Per call ONE
+    host-to-device copy (slots, visiting orders, prob_m, uniforms), one library call -- the fork of every parent slot into its
+    child slots and the walks -- and ONE device-to-host copy (counters, accepted and killed nodes, the trace).
+    The pool: `unlabelled` [S, n] int32 (a slot's row is the alive mask the sub-layout compaction reads) and, with the
+    geometry, `tile_alive`, `label`, `chi_cache` [S, n_tiles] as `DeviceHoleSweep` keeps them per layout.  `new_slot()` hands out
+    a free slot (the pool doubles when none is left: every row is copied, no state is dropped), `release(slot)` takes one back,
+    `reset(slot)` makes it the empty selection.
+    `sweep(branches)`: branches = (parent slot, child slot, nodes in visiting order, prob_m by position, rng) each.  The slot
+    contract of include/tgnn.h is checked here, on the host tables, before anything is copied.  The RNG hand-over is
+    `DeviceHoleSweep`'s, per branch: the generator's state is kept, n_sub uniforms are drawn in one call, and once the walk has
+    said how many it consumed the generator is rewound and draws exactly those (tests/test_tree_search_host.py pins that this is
+    n scalar draws).  Returns per branch (stats row [8], accepted nodes, killed nodes) as numpy copies.
+    geometry: keep the tile state (needed by check_holes; default: only with check_holes).  `calls`, `branches`, `vetoes` count
+    the sweep calls queued, the branches swept and the vetoes met; `trace`, `visit_ptr`, `visit_node` are the last call's (views
+    of the staging buffers, valid until the next call)."""
+
+    def __init__(self, complete_graph, n, collide_edge_index, inverse_index, check_holes, device=None, slots=8, geometry=None):
+        self.check_holes = bool(check_holes)
+        self.geometry = self.check_holes if geometry is None else bool(geometry)
+        if self.check_holes and not self.geometry:
+            raise ValueError("DeviceTreeSweep: check_holes needs the geometry")
+        self.n = n = int(n)
+        host = HostSweep(n, collide_edge_index)                 # (the collision rows in edge order)
+        self.has_col = host.has_col
+        self.starts = host.starts if host.has_col else np.zeros(n + 1, dtype=np.int64)
+        self.nbr = host.nbr if host.has_col else np.zeros(0, dtype=np.int64)
+        self.n_nbr = int(self.nbr.shape[0])
+        self.on_device, self.n_tiles, tiles = None, 0, None
+        if self.geometry:
+            from .data_util import graph_on_device
+            self.on_device = graph_on_device(complete_graph, device)
+            device, self.n_tiles = self.on_device.device, self.on_device.n_tiles
+            tiles = np.fromiter((inverse_index[i] for i in range(n)), dtype=np.int64, count=n)
+            if n and (tiles.min() < 0 or tiles.max() >= self.n_tiles):
+                raise ValueError(f"inverse_index names a tile outside [0, {self.n_tiles})")
+        self.device = dev = torch.device(device)
+        if max(n, self.n_nbr, self.n_tiles) >= 2 ** 31 - 1:
+            raise ValueError("DeviceTreeSweep: more than 2^31 nodes or collision entries")
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+        self.tile_of_node = up(tiles) if tiles is not None else None
+        self.nbr_ptr, self.nbr_idx = up(self.starts), up(self.nbr if self.n_nbr else np.zeros(1))
+        self.n_slots = 0
+        self.unlabelled = self.tile_alive = self.label = self.chi_cache = None
+        self._free = []
+        self._grow(max(int(slots), 1))
+        self._cap_k = self._cap_v = 0
+        self.calls = self.branches = self.vetoes = 0
+        self.trace = self.visit_ptr = self.visit_node = None
+
+    # ---------------------------------------------------------------- the pool
+    def _grow(self, n_slots):
+        dev, i32, old = self.device, torch.int32, self.n_slots
+        rows = [(self.unlabelled, max(self.n, 1), 1)]
+        if self.geometry:
+            rows += [(self.tile_alive, self.n_tiles, 0), (self.label, self.n_tiles, -1), (self.chi_cache, self.n_tiles, -2 ** 31)]
+        grown = []
+        for had, width, fill in rows:
+            t = torch.full((n_slots, width), fill, dtype=i32, device=dev)
+            if had is not None:
+                t[:old].copy_(had)
+            grown.append(t)
+        self.unlabelled = grown[0]
+        if self.geometry:
+            self.tile_alive, self.label, self.chi_cache = grown[1:]
+        self._free.extend(range(n_slots - 1, old - 1, -1))      # (popped from the end: the lowest free slot first)
+        self.n_slots = n_slots
+
+    def new_slot(self) -> int:
+        if not self._free:
+            self._grow(2 * self.n_slots)
+        return self._free.pop()
+
+    def release(self, slot):
+        self._free.append(int(slot))
+
+    def reset(self, slot):
+        """Slot `slot` becomes the empty selection (a root of a search)."""
+        self.unlabelled[slot].fill_(1)
+        if self.geometry:
+            self.tile_alive[slot].zero_()
+            self.label[slot].fill_(-1)
+            self.chi_cache[slot].fill_(-2 ** 31)                # TGNN_SWEEP_CHI_UNKNOWN
+
+    @staticmethod
+    def check_slots(parents, children, n_slots):
+        """The slot contract of tgnn_tree_sweep_many on the host tables."""
+        parents, children = [int(s) for s in parents], [int(s) for s in children]
+        for s in parents + children:
+            if not 0 <= s < n_slots:
+                raise ValueError(f"DeviceTreeSweep: slot {s} outside the pool of {n_slots}")
+        if len(set(children)) != len(children):
+            raise ValueError("DeviceTreeSweep: two branches of a call share a child slot")
+        for k, (par, child) in enumerate(zip(parents, children)):
+            if child == par:
+                if parents.count(par) != 1:
+                    raise ValueError(f"DeviceTreeSweep: branch {k} reuses its parent's slot {par}, which another branch forks as well")
+            elif child in parents:
+                raise ValueError(f"DeviceTreeSweep: the child slot {child} of branch {k} is a parent slot of the call")
+
+    # ---------------------------------------------------------------- the staging buffers
+    def _stage(self, k, v):
+        if k <= self._cap_k and v <= self._cap_v:
+            return
+        K, V = max(k, 2 * self._cap_k), max(v, 2 * self._cap_v)
+        self._cap_k, self._cap_v = K, V
+        i32, dev = torch.int32, self.device
+        # what a call sends: p [V] f64 | u [V] f64 | visit_node [V] | visit_ptr [K + 1] | parent [K] | slot [K]   (int32 words)
+        words_in = 5 * V + 3 * K + 2
+        self._in = torch.zeros(words_in, dtype=i32, device=dev)
+        self._in_h = torch.zeros(words_in, dtype=i32, pin_memory=True)
+        cut = lambda buf: (buf[:2 * V].view(torch.float64), buf[2 * V:4 * V].view(torch.float64), buf[4 * V:5 * V],
+                           buf[5 * V:5 * V + K + 1], buf[5 * V + K + 1:5 * V + 2 * K + 1], buf[5 * V + 2 * K + 1:5 * V + 3 * K + 1])
+        self._in_parts = cut(self._in)
+        self._p_h, self._u_h, self._visit_node_h, self._visit_ptr_h, self._parent_h, self._slot_h = (t.numpy() for t in cut(self._in_h))
+        # what a call brings back: stats [K][8] | err [K] | accepted [V] | killed [V] | trace [V][2]
+        words_out = 9 * K + 4 * V + 1
+        self._out = torch.zeros(words_out, dtype=i32, device=dev)
+        self._out_h = torch.zeros(words_out, dtype=i32, pin_memory=True)
+        cut = lambda buf: (buf[:8 * K], buf[8 * K:9 * K], buf[9 * K:9 * K + V], buf[9 * K + V:9 * K + 2 * V],
+                           buf[9 * K + 2 * V:9 * K + 4 * V])
+        self._out_parts = cut(self._out)
+        self._stats_h, self._err_h, self._accepted_h, self._killed_h, self._trace_h = (t.numpy() for t in cut(self._out_h))
+        self._ws = torch.empty(K, dtype=i32, device=dev)
+
+    def sweep(self, branches) -> list:
+        from .data_util import _TOPOLOGY_ERROR_BITS, _raise_device_error, tree_sweep_call
+        branches = list(branches)
+        K = len(branches)
+        if K == 0:
+            return []
+        self.check_slots([b[0] for b in branches], [b[1] for b in branches], self.n_slots)
+        self._stage(K, sum(len(b[2]) for b in branches))
+        states, v = [], 0
+        self._visit_ptr_h[0] = 0
+        for k, (parent, child, nodes, prob_m, rng) in enumerate(branches):
+            n_sub = len(nodes)
+            self._parent_h[k], self._slot_h[k] = parent, child
+            self._visit_node_h[v:v + n_sub] = nodes
+            self._p_h[v:v + n_sub] = prob_m
+            states.append(rng.get_state())
+            self._u_h[v:v + n_sub] = rng.uniform(size=n_sub)
+            v += n_sub
+            self._visit_ptr_h[k + 1] = v
+        if v == 0:
+            return [(np.zeros(8, dtype=np.int32), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64))] * K
+        dev = self.device
+        self._in.copy_(self._in_h, non_blocking=True)
+        p, u, visit_node, visit_ptr, parent, slot = self._in_parts
+        stats, err, accepted, killed, trace = self._out_parts
+        args = (self.n, self.tile_of_node, self.nbr_ptr, self.nbr_idx, self.n_nbr, self.n_slots, self.unlabelled, self.tile_alive,
+                self.label, self.chi_cache, K, parent, slot, visit_ptr, visit_node, p, u, v, self.check_holes, stats, accepted, killed,
+                trace, err, self._ws)
+        if self.geometry:
+            self.on_device.tree_sweep_into(*args)
+        else:
+            tree_sweep_call(dev, None, *args)
+        self._out_h.copy_(self._out, non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()
+        self.calls += 1
+        self.branches += K
+        self.trace, self.visit_ptr, self.visit_node = self._trace_h.reshape(-1, 2), self._visit_ptr_h, self._visit_node_h
+        out = []
+        for k, (_, _, nodes, _, rng) in enumerate(branches):
+            if self._err_h[k]:
+                _raise_device_error(f"tgnn_tree_sweep_many (branch {k})", int(self._err_h[k]), _TOPOLOGY_ERROR_BITS)
+            row = self._stats_h[8 * k:8 * k + 8].copy()
+            rng.set_state(states[k])                            # the stream moves by what the walk consumed, no more
+            rng.uniform(size=int(row[2]))
+            v0 = int(self._visit_ptr_h[k])
+            out.append((row, self._accepted_h[v0:v0 + int(row[3])].astype(np.int64), self._killed_h[v0:v0 + int(row[4])].astype(np.int64)))
+            self.vetoes += int(row[1])
+        return out
+
+
+class _TreeState:
+    """A queued partial selection of `solve_by_treesearch`: its slot of the device pool and what the host keeps beside it."""
+
+    def __init__(self, slot, n):
+        self.slot = slot
+        self.saved = np.ones(n)                                 # SelectionSolution.unlabelled_nodes (:285): 1.0, kept as the reference has it
+        self.unlabelled = np.ones(n, dtype=bool)
+        self.order = []
+        self.depth = 0
+
+    def fork(self, slot):
+        child = _TreeState.__new__(_TreeState)
+        child.slot, child.saved, child.unlabelled, child.order, child.depth = slot, self.saved.copy(), self.unlabelled.copy(), list(self.order), self.depth
+        return child
+
+
+def solve_by_treesearch(ml_solver, origin_layout, is_random_network=False, time_limit=None, top_k=4, check_holes=False,
+                        max_predictions=None, beam=8, roots=1, seed=0, literal=False, score_fn=None):
+    """The reference's tree search (algorithms.py:66-181) with the branch sweeps on the device (`DeviceTreeSweep`,
+    csrc/tree_sweep.hip): a queue of partial selections; a popped state is scored once (`ml_solver.predict_top_maps`: the
+    probabilities of its min(top_k, M) best maps, best first) and expanded into one branch per map -- the saved
+    log-probabilities are updated (:111-125), a visiting order is sampled (get_nodes_order_array, :223-234) and the branch is
+    swept (:138-157): an already labelled node is passed over with probability prob_m and ends the walk otherwise, with
+    check_holes a tile that would enclose a gap is passed over (:150-152), every other node is accepted.  A branch that still has
+    unlabelled nodes and accepted something goes back on the queue; every other one is finished and recorded once per distinct
+    selection.  Returns (results, predict_cnt): results = [(selection, score, predict_order)] sorted by score, best first, with a
+    stable sort (left in the order found when the layout cannot be scored), predict_cnt = the states popped.
+    Two repairs of the reference's dead calls: the solver hands back the top maps itself, and `is_random_network` must be False.
+    The default is the BATCHED search: `roots` empty selections; per step min(beam, len(queue)) states are popped one at a time
+    with `random.Random(seed)`; a state's exponent is 1 / its own number of predictions; branch number s (step, pop order, map
+    rank) draws its order and its uniforms from `np.random.RandomState([seed, s])`; per step ONE `predict_top_maps` call, ONE
+    sweep call for all branches and one read-back; neither global generator is touched.
+    literal=True (beam = roots = 1) follows the reference decision for decision: pops from the `random` module, the exponent
+    1 / predict_cnt of the global count, `np.random.choice` and the draws from numpy's global stream, the branches of a state
+    swept one after another (a sweep call each: branch m + 1's choice follows branch m's draws in the stream).
+    Stops when the queue is empty, after `max_predictions` pops or after `time_limit` seconds; one of the two must be given.
+    check_holes needs the layout's `complete_graph` and `inverse_index`.  There is no host sweep to fall back to.
+    `.last_sweep` is the `DeviceTreeSweep` (`calls`, `branches`, `vetoes`), `.last_steps` the number of steps."""
+    import random as _random
+    import time as _time
+    if is_random_network:
+        raise ValueError("solve_by_treesearch: is_random_network must be False (the reference's random-network predict does not exist)")
+    if max_predictions is None and time_limit is None:
+        raise ValueError("solve_by_treesearch: give max_predictions or time_limit; the queue need not run empty")
+    if literal and (beam != 1 or roots != 1):
+        raise ValueError("solve_by_treesearch: literal=True is the reference's search: beam == 1 and roots == 1")
+    if beam < 1 or roots < 1 or top_k < 1:
+        raise ValueError("solve_by_treesearch: beam, roots and top_k are at least 1")
+    if check_holes and (getattr(origin_layout, "complete_graph", None) is None or getattr(origin_layout, "inverse_index", None) is None):
+        raise ValueError("check_holes needs the layout's complete graph (tile rings) and inverse_index: a BrickLayout, not a "
+                         "bare DeviceLayout")
+    device = ml_solver.device
+    origin = origin_layout if isinstance(origin_layout, DeviceLayout) else DeviceLayout.upload(origin_layout, device)
+    dev = origin.node_feature.device
+    n = int(origin.node_feature.shape[0])
+    if n == 0:
+        raise ValueError("solve_by_treesearch: a layout without nodes")
+    col_host = origin.collide_edge_index.cpu().numpy()
+    dsw = DeviceTreeSweep(getattr(origin_layout, "complete_graph", None), n, col_host, getattr(origin_layout, "inverse_index", None),
+                          check_holes, dev, slots=max(8, roots + beam * top_k))
+    fn = solve_by_treesearch
+    fn.last_sweep, fn.last_steps = dsw, 0
+    builders = []
+    pop_rng = _random if literal else _random.Random(seed)
+    queue = []
+    for _ in range(roots):
+        queue.append(_TreeState(dsw.new_slot(), n))             # (a fresh pool: every slot is the empty selection)
+    results, seen = [], set()
+    predict_cnt = n_branches = 0
+    start = _time.time()
+
+    def running():
+        return (len(queue) > 0 and (max_predictions is None or predict_cnt < max_predictions)
+                and (time_limit is None or _time.time() - start < time_limit))
+
+    def finish(state, stats, acc, gone):
+        state.unlabelled[acc] = False
+        state.unlabelled[gone] = False
+        state.order.extend(int(i) for i in acc)
+        if state.unlabelled.any() and len(acc) > 0:             # (:166)
+            queue.append(state)
+            return
+        dsw.release(state.slot)
+        selection = np.zeros(n)
+        selection[state.order] = 1
+        key = selection.tobytes()                               # (:172: one entry per distinct selection)
+        if key not in seen:
+            seen.add(key)
+            results.append((selection, create_score(selection, origin_layout, score_fn, device), state.order))
+
+    while running():
+        popped = []
+        for _ in range(min(beam, len(queue))):
+            if not running():
+                break
+            state = queue.pop(pop_rng.randint(0, len(queue) - 1))     # (:89-90)
+            predict_cnt += 1
+            state.depth += 1
+            popped.append((state, predict_cnt))
+        fn.last_steps += 1
+        while len(builders) < len(popped):
+            builders.append(SubLayoutBuilder(origin))
+        subs = []
+        for builder, (state, cnt) in zip(builders, popped):
+            sub = builder.build(dsw.unlabelled[state.slot])     # (the slot's own row on the device: nothing to upload)
+            sub.predict_index, sub.origin_index = cnt, 0
+            subs.append(sub)
+        maps = ml_solver.predict_top_maps(subs, top_k)
+        pending, children, parents = [], [], []
+        for (state, cnt), prob in zip(popped, maps):
+            ids = np.flatnonzero(state.unlabelled)
+            prob = np.asarray(prob)
+            prob = prob.reshape(len(ids), -1)
+            n_maps = prob.shape[1]
+            for m in range(n_maps):
+                log_prob_network = np.log(np.clip(prob[:, m], TREE_EPS, 1.0))                       # (:111; float32 stays float32)
+                log_prob_m = state.saved[ids] + log_prob_network                                   # (:112)
+                prob_m = np.exp(log_prob_m / (predict_cnt if literal else state.depth))             # (:113)
+                child = state.fork(state.slot if n_maps == 1 else dsw.new_slot())
+                child.saved[ids] = log_prob_m
+                rng = np.random if literal else np.random.RandomState([seed, n_branches])
+                n_branches += 1
+                order = rng.choice(len(ids), len(ids), replace=False, p=_tree_sampling_probabilities(prob_m))     # (:232)
+                branch = (state.slot, child.slot, ids[order], prob_m[order], rng)
+                if literal:
+                    finish(child, *dsw.sweep([branch])[0])
+                else:
+                    pending.append(branch)
+                    children.append(child)
+            if n_maps != 1:
+                parents.append(state.slot)
+        if not literal:
+            for child, res in zip(children, dsw.sweep(pending)):
+                finish(child, *res)
+        for slot in parents:                                    # (forked into fresh slots: the parent's own is free again)
+            dsw.release(slot)
+    if results and all(r[1] is not None for r in results):
+        results = sorted(results, key=lambda tup: tup[1], reverse=True)                             # (:180)
+    return results, predict_cnt

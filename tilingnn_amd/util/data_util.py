@@ -422,6 +422,26 @@ class CompleteGraphOnDevice:
                                            ptr(trace), ptr(err), ptr(ws), 4 * int(ws.numel()),
                                            _lib.current_stream(self.device)))
 
+    def tree_sweep_into(self, n_nodes, tile_of_node, nbr_ptr, nbr_idx, n_nbr, n_slots, unlabelled, tile_alive, label, chi_cache, k,
+                        parent_slot, slot, visit_ptr, visit_node, p, u, n_visit, check_holes, stats, accepted, killed, trace, err,
+                        ws=None, geometry=True):
+        """One step of the tree search -- the sweeps of K branches of one layout of this graph, each on its own slot of the
+        caller's state pool -- queued on the current stream with nothing read back: the raw call of `tgnn_tree_sweep_many`
+        (include/tgnn.h has the argument contract and the slot contract; csrc/tree_sweep.hip).  Every argument but the counts is
+        a contiguous tensor on this device: int32, `p` / `u` float64; `ws` int32 of at least K words (made here when None).
+        geometry=False (check_holes == 0 only): the graph's rings and contact rows are not handed over and no tile state is
+        kept -- `tile_of_node` and the three tile rows may be None.  `util.algorithms.DeviceTreeSweep` keeps the pool, the
+        staging buffers and the RNGs."""
+        torch, _lib, check, lib, ptr, UNION_TOL = _union_api()
+        geo = None
+        if geometry:
+            ring_xy, ring_ptr, _, _ = self._union_geometry()
+            touch_ptr, touch_idx, dir_x, dir_y = self._topology_geometry()
+            geo = (ptr(ring_xy), ptr(ring_ptr), self.n_tiles, ptr(touch_ptr), ptr(touch_idx), UNION_TOL, dir_x, dir_y)
+        tree_sweep_call(self.device, geo, n_nodes, tile_of_node, nbr_ptr, nbr_idx, n_nbr, n_slots, unlabelled, tile_alive, label,
+                        chi_cache, k, parent_slot, slot, visit_ptr, visit_node, p, u, n_visit, check_holes, stats, accepted, killed,
+                        trace, err, ws)
+
     # -------------------------------------------------------------------------- the outline of a union of tiles
     def union_contours(self, alive):
         """`UnionContours` of the K masks `alive` ([K, n_tiles] or [n_tiles], any integer or bool tensor on this device): the
@@ -530,3 +550,22 @@ def graph_on_device(graph: TileGraph, device=None) -> CompleteGraphOnDevice:
 
 def layout_on_device(graph_on_device: CompleteGraphOnDevice, tiles_super_set):
     return graph_on_device.layout(tiles_super_set)
+
+
+def tree_sweep_call(device, geo, n_nodes, tile_of_node, nbr_ptr, nbr_idx, n_nbr, n_slots, unlabelled, tile_alive, label, chi_cache, k,
+                    parent_slot, slot, visit_ptr, visit_node, p, u, n_visit, check_holes, stats, accepted, killed, trace, err, ws=None):
+    """`tgnn_tree_sweep_many` on `device`'s current stream.  geo: the eight leading arguments (a graph's rings and contact rows:
+    `CompleteGraphOnDevice.tree_sweep_into`), or None for a layout that carries no complete graph -- check_holes == 0 only, no
+    tile state."""
+    torch, _lib, check, lib, ptr, UNION_TOL = _union_api()
+    opt = lambda t: None if t is None else ptr(t)
+    if geo is None:
+        geo = (None, None, 0, None, None, UNION_TOL, 1.0, 0.0)
+    ws_bytes = int(lib.tgnn_tree_sweep_workspace_bytes(k))
+    if ws is None:
+        ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        check(lib.tgnn_tree_sweep_many(*geo, n_nodes, opt(tile_of_node), ptr(nbr_ptr), ptr(nbr_idx), n_nbr, n_slots, ptr(unlabelled),
+                                       opt(tile_alive), opt(label), opt(chi_cache), k, ptr(parent_slot), ptr(slot), ptr(visit_ptr),
+                                       ptr(visit_node), ptr(p), ptr(u), n_visit, int(bool(check_holes)), ptr(stats), ptr(accepted),
+                                       ptr(killed), ptr(trace), ptr(err), ptr(ws), 4 * int(ws.numel()), _lib.current_stream(device)))
