@@ -1344,8 +1344,9 @@ int tgnn_union_hole_delta(const double *ring_xy, const int32_t *ring_ptr, int64_
  *   killed_out [N]: the cleared neighbours, by acceptance then row order, from killed_out[node_ptr[k]] (the accepted nodes
  *   themselves are not among them).  trace_out [V][2] = {TGNN_SWEEP_*, d holes} of every position of the visiting list.
  *   err_out [K] gets the layout's TGNN_TOPO_ERR_* bits (0: none): a node, tile, contact or table entry outside its array,
- *   or more than 16 tiles around a point counting the visited tile.  The walk ends where the error shows; the layout's other
- *   outputs and its state are then not to be used.
+ *   or more than 16 tiles around a point counting the visited tile.  The walk ends where the error shows -- a collision row
+ *   outside [0, n_nbr] is met BEFORE its node's acceptance, as in tgnn_tree_sweep_many --; the layout's other outputs and its
+ *   state are then not to be used.
  *   A layout that is inactive or whose visiting list is empty: none of its words, output or state, is touched.
  *   ws: tgnn_hole_sweep_workspace_bytes(K) = 4 K bytes, 4-byte aligned; its contents on entry do not matter.
  *   K, n_tiles, n_nodes or n_visit == 0: nothing is queued. */

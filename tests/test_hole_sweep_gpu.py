@@ -355,6 +355,18 @@ def test_error_bits_index_and_wedge_overflow():
     run = Harness(good, [(np.arange(9), np.array([[0], [8]]))])
     run.nbr_idx[0] = 77
     assert run.call([[0]], [[1.0]], [[0.0]])["err"][0] == 1
+    # a collision row that ends behind the array, and one that ends before it begins: met BEFORE the acceptance
+    # (csrc/hole_sweep_block.h: block_accept) -- the node stays unlabelled, its tile dead, and the lists end where they did
+    col = np.array([[2, 8, 8], [6, 0, 6]])                                  # node 2 labels 6; node 8, whose row is the last, 0 and 6
+    for end in (3 + 1, 0):
+        run = Harness(good, [(np.arange(9), col)])
+        assert run.nbr_ptr.tolist() == [0, 0, 0, 1, 1, 1, 1, 1, 1, 3]
+        run.nbr_ptr[9] = end
+        out = run.call([[2, 8, 1, 3]], [[1.0] * 4], [[0.0] * 4])
+        assert out["err"][0] == 1
+        assert out["accepted"].tolist() == [2, -7, -7, -7] and out["killed"].tolist() == [6] + [-7] * 8
+        unl, alive, _, _ = run.state()
+        assert unl.tolist() == [1, 1, 0, 1, 1, 1, 0, 1, 1] and alive[0].tolist() == [0, 0, 1, 0, 0, 0, 0, 0, 0]
 
 
 # ------------------------------------------------------------------------------------------------ refusals

@@ -8,9 +8,6 @@ pre-drawn uniforms."""
 import itertools
 import math
 import os
-import shutil
-import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,61 +16,21 @@ from tests import hole_delta_cases as hc
 from tests import hole_guard_restatement as hg
 from tests import topology_oracle as to
 from tests.golden_util import GOLDEN
+from tests.sweep_host_cases import NBR, SETS, build_step_program, run_program
 
-SETS = ("frame with a plus inside", "plus among four squares", "3x3 full")
-# what an acceptance labels besides the node (a layout's collision rows; the sets themselves have none): symmetric, and one
-# entry twice
-NBR = {5: {0: [2, 2], 2: [0]}, 9: {0: [8, 8], 8: [0], 2: [6], 6: [2]}}
 THR = (1.0, 0.5, 0.75, 1.0, 0.25, 1.0, 0.5, 1.0, 0.875)
 
 
 @pytest.fixture(scope="module")
 def step_program(tmp_path_factory):
-    """tests/host/hole_sweep_step_test.cpp, built with the host compiler alone under AddressSanitizer + UBSan (the sanitizers'
-    runtime linked into the program itself), the way tests/test_union_hole_delta_host.py builds its program."""
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    clang = "clang" in subprocess.run([cxx, "--version"], capture_output=True, text=True).stdout
-    static_rt = ["-static-libsan"] if clang else ["-static-libasan", "-static-libubsan"]
-    exe = str(tmp_path_factory.mktemp("hole_sweep") / "hole_sweep_step_test")
-    build = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                            "-fno-sanitize-recover=undefined", *static_rt, "-I", os.path.join(repo, "tilingnn_amd", "csrc"),
-                            os.path.join(repo, "tests", "host", "hole_sweep_step_test.cpp"), "-o", exe],
-                           capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr[-4000:]
-    return exe
-
-
-def _nbr_csr(n):
-    rows = NBR[n]
-    ptr = np.zeros(n + 1, dtype=np.int32)
-    for i in range(n):
-        ptr[i + 1] = ptr[i] + len(rows.get(i, ()))
-    idx = np.array([v for i in range(n) for v in rows.get(i, ())], dtype=np.int32)
-    return ptr, idx
+    return build_step_program(tmp_path_factory, "hole_sweep_step_test")
 
 
 def _run(exe, tmp_path, tiles, want, orders):
-    from tilingnn_amd.tiling.region import UNION_TOL, contact_geometry, sweep_direction, union_geometry
-    n = len(tiles)
-    ring_xy, ring_ptr, _, _ = union_geometry(tiles, np.zeros((2, 0), dtype=np.int64), n)
-    touch_ptr, touch_idx = contact_geometry(ring_xy, ring_ptr)
-    theta = sweep_direction(ring_xy, ring_ptr)
-    nbr_ptr, nbr_idx = _nbr_csr(n)
-    path, out = str(tmp_path / "case.bin"), str(tmp_path / "out.bin")
-    with open(path, "wb") as f:
-        f.write(struct.pack("<5q3d", n, ring_xy.shape[0], touch_idx.shape[0], nbr_idx.shape[0], orders.shape[0], UNION_TOL,
-                            math.cos(theta), math.sin(theta)))
-        for a in (ring_xy, ring_ptr, touch_ptr, touch_idx, nbr_ptr, nbr_idx, want.astype(np.int32), np.array(THR[:n]),
-                  orders.astype(np.uint8)):
-            f.write(np.ascontiguousarray(a).tobytes())
-    run = subprocess.run([exe, path, out], capture_output=True, text=True)
-    assert run.returncode == 0, (run.stdout + run.stderr)[-4000:]
-    tail = run.stdout.strip().split()
-    assert tail[0::2] == ["orders", "visits", "evaluated", "mismatches", "err", "hits"] and tail[7] == "0" and tail[9] == "0", run.stdout
+    tail, out = run_program(exe, tmp_path, tiles, want, orders, THR)
+    assert tail[0::2] == ["orders", "visits", "evaluated", "mismatches", "err", "hits"] and tail[7] == "0" and tail[9] == "0", tail
     assert int(tail[1]) == orders.shape[0]
-    return np.fromfile(out, dtype=np.int32).reshape(-1, 6), int(tail[3]), int(tail[5]), int(tail[11])
+    return out.reshape(-1, 6), int(tail[3]), int(tail[5]), int(tail[11])
 
 
 def _walk_from_the_table(n, want, orders):

@@ -6,6 +6,7 @@ against ONE tgnn_union_hole_delta call over the prefix masks.  Then the fork, th
 and workspaces against nine solo calls), graphs either side of the LDS limit, the sweep without geometry, a labelled first
 position, the error bits and the refusals.  Every comparison is exact integer equality.  The per-visit rule itself runs on the
 host under sanitizers in tests/test_tree_search_host.py."""
+import functools
 import math
 import os
 
@@ -14,6 +15,7 @@ import pytest
 import torch
 
 from tests import hole_delta_cases as hc
+from tests import topology_oracle as to
 from tests import tree_search_restatement as ts
 from tests.golden_util import GOLDEN
 from tests.test_tree_search_host import CONFIGS, restated
@@ -43,7 +45,8 @@ def _made_up_graph(tiles):
 class Harness:
     """A pool of `n_slots` states of ONE layout and one call per step, straight from arrays.  tile_of: the tile of every node;
     col: collision edges [2, E].  Outputs and the workspace are filled with the byte `fill` before every call: what is read must
-    be written.  geometry=False: no tile state (check_holes == 0)."""
+    be written; `guards_intact`: the two words of it behind the accepted and behind the killed list were still that byte after
+    the last call.  geometry=False: no tile state (check_holes == 0)."""
 
     def __init__(self, od, tile_of, col, n_slots, geometry=True):
         self.od, self.s, self.n, self.geometry = od, n_slots, len(tile_of), geometry
@@ -76,7 +79,7 @@ class Harness:
         v = int(visit_ptr[-1])
         cat = lambda parts, dt: torch.from_numpy(np.concatenate([np.asarray(x, dtype=dt) for x in parts] + [np.zeros(1, dtype=dt)])).to(DEV)
         dirty = lambda count: torch.full((4 * max(count, 1),), fill, dtype=torch.uint8, device=DEV).view(torch.int32)
-        out = {"stats": dirty(8 * k), "err": dirty(k), "accepted": dirty(v), "killed": dirty(v), "trace": dirty(2 * v)}
+        out = {"stats": dirty(8 * k), "err": dirty(k), "accepted": dirty(v + 2), "killed": dirty(v + 2), "trace": dirty(2 * v)}
         ws = dirty(int(lib.tgnn_tree_sweep_workspace_bytes(k)) // 4)
         i32 = lambda a: torch.from_numpy(np.asarray(a, dtype=np.int32)).to(DEV)
         args = (self.n, self.tile_of_node if self.geometry else None, self.nbr_ptr, self.nbr_idx, self.n_nbr, self.s, self.unlabelled,
@@ -89,6 +92,7 @@ class Harness:
             tree_sweep_call(torch.device(DEV), None, *args)
         torch.cuda.synchronize()
         res = {name: t.cpu().numpy() for name, t in out.items()}
+        self.guards_intact = all((res[name][v:].view(np.uint8) == fill).all() for name in ("accepted", "killed"))
         res["stats"], res["trace"], res["visit_ptr"] = res["stats"][:8 * k].reshape(k, 8), res["trace"][:2 * v].reshape(v, 2), visit_ptr
         res["accepted"], res["killed"], res["err"] = res["accepted"][:v], res["killed"][:v], res["err"][:k]
         return res
@@ -259,18 +263,26 @@ def test_nine_branches_in_one_call_are_nine_solo_calls_on_any_bytes(small):
 
 
 # ------------------------------------------------------------------------------------------------ either side of the LDS limit
+@functools.lru_cache(maxsize=None)
+def _grid(extra):
+    """The 96 x 64 grid of unit squares, and with `extra` the same grid with one more square far away: (tiles, graph)."""
+    w, h = 96, 64
+    x, y = [c.reshape(-1) for c in np.meshgrid(np.arange(w), np.arange(h))]
+    tiles = [hc.box(a, b, a + 1, b + 1) for a, b in zip(x, y)] + [hc.box(200, 0, 201, 1)] * extra
+    assert len(tiles) == 6144 + extra
+    return tiles, _made_up_graph(tiles)
+
+
 @pytest.mark.parametrize("extra", [0, 1])
 def test_graphs_either_side_of_the_lds_limit(extra):
     """The labels live in LDS for the walk on graphs of up to 6 144 tiles and in the slot's row beyond: the 96 x 64 grid of unit
     squares and the same grid with one more square far away.  By the reasoning of tests/test_hole_sweep_gpu.py: the left, right
     and lower neighbours of an interior cell enclose nothing, the upper one would close the ring around it (d holes +1: passed
     over), the cell itself fills the gap; in the next call the upper neighbour completes a solid plus."""
-    w, h = 96, 64
-    x, y = [c.reshape(-1) for c in np.meshgrid(np.arange(w), np.arange(h))]
-    tiles = [hc.box(a, b, a + 1, b + 1) for a, b in zip(x, y)] + [hc.box(200, 0, 201, 1)] * extra
+    w = 96
+    tiles, od = _grid(extra)
     n = len(tiles)
-    assert n == 6144 + extra
-    run = Harness(_made_up_graph(tiles), np.arange(n), np.zeros((2, 0)), 2)
+    run = Harness(od, np.arange(n), np.zeros((2, 0)), 2)
     cell = 40 * w + 50
     order = np.array([cell - 1, cell + 1, cell - w, cell + w, cell])
     first = run.call([0], [1], [order], [np.ones(5)], [np.zeros(5)])
@@ -287,6 +299,90 @@ def test_graphs_either_side_of_the_lds_limit(extra):
     assert second["err"][0] == 0 and second["trace"].tolist() == [[ACCEPTED, 0], [BREAK, 0]]
     assert second["stats"][0].tolist() == [2, 0, 1, 1, 0, 0, 0, 0]
     assert (run.state()[2][1][chosen + [cell + w]] == cell - w).all()
+
+
+# ------------------------------------------------------------------------------------------------ one acceptance for both entries
+def _collision_rows(n, col):
+    col = np.asarray(col).reshape(2, -1).astype(np.int64)
+    by_src = np.argsort(col[0], kind="stable")
+    return np.searchsorted(col[0][by_src], np.arange(n + 1)), col[1][by_src]
+
+
+def _walk_on_the_host(rings, col, order):
+    """The walk both entries make from the empty selection when every node that is not vetoed is accepted and the first labelled
+    node ends it, written out again with the loop-tracing oracle as the veto (as tests/hole_guard_restatement.py and
+    tests/tree_search_restatement.py write theirs).  -> trace [len(order), 2], accepted, killed, acceptances that merged components."""
+    starts, nbr = _collision_rows(len(rings), col)
+    unlabelled = np.ones(len(rings), dtype=bool)
+    trace, tiles, accepted, killed = np.zeros((len(order), 2), dtype=np.int32), [], [], []
+    components = merges = 0
+    for pos, node in enumerate(int(i) for i in order):
+        if not unlabelled[node]:
+            trace[pos] = BREAK, 0
+            break
+        now, holes = to.topology(tiles + [rings[node]])
+        if holes > 0:
+            trace[pos] = VETOED, holes
+            continue
+        trace[pos] = ACCEPTED, holes
+        merges += now < components                                          # it joined two components or more
+        components = now
+        tiles.append(rings[node])
+        unlabelled[node] = False
+        accepted.append(node)
+        for v in nbr[starts[node]:starts[node + 1]]:
+            if unlabelled[v]:
+                unlabelled[v] = False
+                killed.append(int(v))
+    return trace, accepted, killed, merges
+
+
+def _both_entries_walk_alike(od, rings, col, order):
+    """The hole entry with thr = 1, u = 0 and the tree entry with check_holes, p = 0, u = 1 on the same order from the empty
+    state: the same lists, trace and state bytes -- after the host has said that the order meets a veto, a merge and a kill."""
+    from tests.test_hole_sweep_gpu import Harness as HoleHarness
+    n, v = len(rings), len(order)
+    trace, accepted, killed, merges = _walk_on_the_host(rings, col, order)
+    assert (trace[:, 0] == VETOED).any() and merges > 0 and killed and (trace[:, 0] == BREAK).any()
+    hole, tree = HoleHarness(od, [(np.arange(n), col)]), Harness(od, np.arange(n), col, 1)
+    a = hole.call([order], [np.ones(v)], [np.zeros(v)])
+    b = tree.call([0], [0], [order], [np.zeros(v)], [np.ones(v)])
+    assert a["err"][0] == 0 and b["err"][0] == 0
+    assert (a["trace"] == b["trace"]).all() and (a["trace"] == trace).all()
+    assert a["stats"][0][[0, 1, 3, 4]].tolist() == b["stats"][0][[0, 1, 3, 4]].tolist()     # (the draws differ: one per test, one at the break)
+    assert a["accepted"][:v].tolist() == accepted + [-7] * (v - len(accepted)) and b["accepted"].tolist() == accepted + [-1] * (v - len(accepted))
+    assert a["killed"][:n].tolist() == killed + [-7] * (n - len(killed)) and b["killed"].tolist() == killed + [-1] * (v - len(killed))
+    assert tree.guards_intact
+    assert all(x.tobytes() == y.tobytes() for x, y in zip(hole.state(), tree.state()))      # unlabelled, tile_alive, label, chi_cache
+    return len(accepted), len(killed), int((trace[:, 0] == VETOED).sum()), merges
+
+
+@pytest.mark.parametrize("seed", range(3))
+def test_both_entries_run_the_same_acceptance_on_the_small_graph(small, seed):
+    """A seeded permutation of the nodes, those that an earlier node of it labels moved behind the others: the walk goes on until
+    most of the graph is labelled and then meets its break."""
+    fx = small
+    starts, nbr = _collision_rows(fx.n, fx.col)
+    free, front, back = np.ones(fx.n, dtype=bool), [], []
+    for node in np.random.default_rng(seed).permutation(fx.n):
+        (front if free[node] else back).append(int(node))
+        if free[node]:
+            free[node] = False
+            free[nbr[starts[node]:starts[node + 1]]] = False
+    counts = _both_entries_walk_alike(fx.on_device, fx.rings, fx.col, np.array(front + back))
+    print(f"\nboth entries, small graph seed {seed}: %d accepted, %d killed, %d vetoes, %d merges" % counts)
+
+
+@pytest.mark.parametrize("extra", [0, 1])
+def test_both_entries_run_the_same_acceptance_either_side_of_the_lds_limit(extra):
+    """Labels in LDS and in place: the plus of test_graphs_either_side_of_the_lds_limit -- the lower neighbour joins the left and
+    the right one, the upper one is vetoed -- with a far cell that the centre labels and the walk then meets."""
+    w = 96
+    tiles, od = _grid(extra)
+    cell, far = 40 * w + 50, 10 * w + 7
+    order = np.array([cell - 1, cell + 1, cell - w, cell + w, cell, 7, far, 9])
+    counts = _both_entries_walk_alike(od, tiles, np.array([[cell, far], [far, cell]]), order)
+    assert counts == (5, 1, 1, 1)
 
 
 # ------------------------------------------------------------------------------------------------ small cases
@@ -348,6 +444,19 @@ def test_error_bits_slot_node_tile_and_collision_entry():
     run.nbr_ptr[1] = 99                                                     # node 0's row ends outside the array
     out = run.call([0], [1], [[0]], [[1.0]], [[0.0]])
     assert out["err"][0] == 1 and run.state()[0][1].all()
+    # a collision row that ends behind the array, and one that ends before it begins, on the 3 x 3 set: met BEFORE the acceptance
+    # (csrc/hole_sweep_block.h: block_accept) -- the node stays unlabelled, its tile dead, and the lists end where they did
+    nine = _made_up_graph(hc.sets()["3x3 full"])
+    col = np.array([[2, 8, 8], [6, 0, 6]])                                  # node 2 labels 6; node 8, whose row is the last, 0 and 6
+    for end in (3 + 1, 0):
+        run = Harness(nine, np.arange(9), col, 2)
+        assert run.nbr_ptr.tolist() == [0, 0, 0, 1, 1, 1, 1, 1, 1, 3]
+        run.nbr_ptr[9] = end
+        out = run.call([0], [1], [[2, 8, 1, 3]], [[1.0] * 4], [[0.0] * 4])
+        assert out["err"][0] == 1 and run.guards_intact
+        assert out["accepted"].tolist() == [2, -1, -1, -1] and out["killed"].tolist() == [6, -1, -1, -1]
+        unl, alive, _, _ = run.state()
+        assert unl[1].tolist() == [1, 1, 0, 1, 1, 1, 0, 1, 1] and alive[1].tolist() == [0, 0, 1, 0, 0, 0, 0, 0, 0]
     # a visiting list shorter than what an acceptance labels: reported, the lists are not overrun
     out = Harness(od, np.arange(6), SIX_COL, 2).call([0], [1], [[0, 1]], [[1.0] * 2], [[0.0] * 2])
     assert out["err"][0] == 1

@@ -14,7 +14,8 @@
 //                          its tile enters tile_alive, the labels of the components it joins are rewritten in two strided
 //                          passes over the tiles (hole_sweep_step.h: mark, join, close) so that every label is again the lowest
 //                          alive tile of its component, and the node's unlabelled collision neighbours are cleared and appended
-//                          to the killed list in row order (a vote per wave gives each its place: the same list on every run).
+//                          to the killed list in row order (a vote per wave gives each its place: the same list on every run)
+//                          -- block_accept of hole_sweep_block.h, which the branch walk of tree_sweep.hip calls as well.
 //                          The labels live in LDS for the walk on graphs of up to kLabelLdsTiles tiles (copied in and out) and
 //                          in the caller's label array beyond; tile_alive and unlabelled are the caller's arrays throughout.
 //                          d chi of a visited tile is kept in the caller's chi_cache until a tile of its contact row is
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(kSwThreads) void hole_sweep_walk_kernel(SweepArgs a
     extern __shared__ int32_t label_lds[];
     __shared__ double arc_lo[topo::kMaxWedges][kSwThreads], arc_hi[topo::kMaxWedges][kSwThreads];
     __shared__ SweepShared sh;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int64_t k = layout0 + blockIdx.x;
     const int64_t n = a.g.n_tiles;
     const SweepLayout l = layout_of(a, k);
@@ -100,7 +101,8 @@ __global__ __launch_bounds__(kSwThreads) void hole_sweep_walk_kernel(SweepArgs a
     if (tid == 0) sh.err_all = 0;
     __syncthreads();
     LdsArcs<kSwThreads> arcs{arc_lo, arc_hi, tid};
-    int visited = 0, vetoes = 0, draws = 0, n_acc = 0, n_killed = 0;     // the same in every thread
+    SweepWalk w{a.nbr_ptr + l.n0, a.nbr_idx, a.n_nbr, l.n_nodes, unl, alive, lab, chi, a.accepted + l.v0, a.killed + l.n0, 0, 0};
+    int visited = 0, vetoes = 0, draws = 0;                  // the same in every thread
     int err = 0, terr = 0;                                   // err: uniform, ends the walk; terr: this thread's
     for (int64_t pos = 0; pos < l.n_visit; ++pos) {
         const int64_t node = a.visit_node[l.v0 + pos];
@@ -131,52 +133,8 @@ __global__ __launch_bounds__(kSwThreads) void hole_sweep_walk_kernel(SweepArgs a
         }
         if (tid == 0) trace[2 * pos] = code, trace[2 * pos + 1] = d;
         if (code != sweep::kAccepted) continue;
-        const bool fresh = alive[t] == 0;
-        if (tid == 0) {
-            unl[node] = 0;
-            a.accepted[l.v0 + n_acc] = (int32_t)node;
-        }
-        ++n_acc;
-        __syncthreads();
-        if (fresh) {
-            if (tid == 0) sh.merged = sweep::begin_merge(alive, lab, t);
-            __syncthreads();
-            for (int cc = a.g.touch_ptr[t] + tid; cc < a.g.touch_ptr[t + 1]; cc += kSwThreads) {
-                const int32_t root = sweep::mark_root(a.g, lab, t, cc, terr);
-                if (root < n) atomicMin(&sh.merged, root);
-                sweep::forget_chi(a.g, chi, cc, terr);
-            }
-            __syncthreads();
-            const int32_t m = sh.merged;
-            for (int64_t i = tid; i < n; i += kSwThreads) sweep::join_member(lab, n, i, m);
-            __syncthreads();
-            for (int64_t i = tid; i < n; i += kSwThreads) sweep::close_root(lab, i, m);
-            __syncthreads();
-        }
-        // label_collision_neighbor: the node's unlabelled collision neighbours, in row order
-        const int64_t r0 = a.nbr_ptr[l.n0 + node], r1 = a.nbr_ptr[l.n0 + node + 1];
-        if (r0 < 0 || r1 < r0 || r1 > a.n_nbr) {
-            err |= topo::kErrIndex;
-            break;
-        }
-        for (int64_t c0 = r0; c0 < r1; c0 += kSwThreads) {
-            const int64_t cc = c0 + tid;
-            const int32_t v = cc < r1 ? sweep::killed_by(a.nbr_idx, r0, cc, unl, l.n_nodes, terr) : -1;
-            const unsigned long long vote = __ballot(v >= 0);
-            if (lane == 0) sh.wave_kills[wave] = __popcll(vote);
-            __syncthreads();
-            int before = __popcll(vote & ((1ull << lane) - 1ull)), total = 0;
-            for (int w = 0; w < kSwWaves; ++w) {
-                before += w < wave ? sh.wave_kills[w] : 0;
-                total += sh.wave_kills[w];
-            }
-            if (v >= 0) {
-                a.killed[l.n0 + n_killed + before] = v;
-                unl[v] = 0;
-            }
-            n_killed += total;
-            __syncthreads();
-        }
+        err |= block_accept<true>(a.g, w, node, t, l.n_nodes, &sh, terr);  // (a layout's killed list holds every node of it)
+        if (err != 0) break;
     }
     __syncthreads();
     for (int64_t pos = visited + tid; pos < l.n_visit; pos += kSwThreads) trace[2 * pos] = sweep::kNotReached, trace[2 * pos + 1] = 0;
@@ -188,8 +146,8 @@ __global__ __launch_bounds__(kSwThreads) void hole_sweep_walk_kernel(SweepArgs a
         stats[sweep::kStatVisited] = visited;
         stats[sweep::kStatVetoes] = vetoes;
         stats[sweep::kStatDraws] = draws;
-        stats[sweep::kStatAccepted] = n_acc;
-        stats[sweep::kStatKilled] = n_killed;
+        stats[sweep::kStatAccepted] = w.n_accepted;
+        stats[sweep::kStatKilled] = w.n_killed;
         stats[sweep::kStatAllVetoed] = 1;                    // until hole_sweep_stop_kernel finds a node that is not
         stats[6] = stats[7] = 0;
         a.err[k] = err | sh.err_all;

@@ -1,5 +1,6 @@
 // What the walks over one complete graph share on the device (csrc/hole_sweep.hip: a block per layout; csrc/tree_sweep.hip: a
-// block per branch of a tree search): the block's size, its words of LDS and d holes of one tile by the whole block.  The
+// block per branch of a tree search): the block's size, its words of LDS, d holes of one tile by the whole block
+// (block_hole_delta) and the acceptance of a node by the whole block (block_accept), the only statement of it on the device.  The
 // per-visit steps themselves are hole_sweep_step.h.
 #pragma once
 #include "union_masks.h"
@@ -64,6 +65,77 @@ __device__ __forceinline__ int block_hole_delta(const topo::Tiles &g, const int3
     err_out |= sh->err;
     if (kStore && work && tid == 0 && sh->err == 0) chi_cache[t] = sh->dchi;
     return touching ? 1 - sh->distinct - (work ? sh->dchi : known) : 0;
+}
+
+// What the walk accepts into: a layout's or a slot's own rows and tables (node numbers local to them) and the walk's two lists.
+// n_accepted and n_killed are the same in every thread.
+struct SweepWalk {
+    const int32_t *nbr_ptr, *nbr_idx;        // the collision rows of the nodes: [n_nodes + 1], [n_nbr]
+    int64_t n_nbr, n_nodes;
+    int32_t *unl, *alive, *lab, *chi;        // unlabelled [n_nodes]; the tile rows [n_tiles] (not read without kTiles)
+    int32_t *accepted, *killed;
+    int n_accepted, n_killed;
+};
+
+// Accepts `node`, of tile t, by the whole block: the node leaves `unl` and enters the accepted list, its tile enters `alive` with
+// the labels of the component it joins rewritten (hole_sweep_step.h: mark, join, close) and d chi of its contact row forgotten,
+// and its unlabelled collision neighbours are cleared and appended to the killed list in row order (a vote per wave gives each
+// its place).  Begins and ends behind a barrier.  Returns error bits, the same in every thread: a collision row outside
+// [0, n_nbr] is met before anything is written, and so is a killed list without room; a row that outgrows `room` -- the nodes the
+// killed list may hold beside this acceptance -- ends the acceptance with the chunk unwritten.  terr gets this thread's own bits.
+// kTiles: false when there is no tile state; then t, g and the tile rows are not read.
+template <bool kTiles>
+__device__ __forceinline__ int block_accept(const topo::Tiles &g, SweepWalk &w, int64_t node, int64_t t, int64_t room, SweepShared *sh,
+                                            int &terr) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __syncthreads();                                         // every thread has read unl[node] and the words of the last vote
+    // label_collision_neighbor's row
+    const int64_t r0 = w.nbr_ptr[node], r1 = w.nbr_ptr[node + 1];
+    if (r0 < 0 || r1 < r0 || r1 > w.n_nbr || w.n_killed > room) return topo::kErrIndex;
+    const bool fresh = kTiles && w.alive[t] == 0;
+    if (tid == 0) {
+        w.unl[node] = 0;
+        w.accepted[w.n_accepted] = (int32_t)node;
+    }
+    ++w.n_accepted;
+    __syncthreads();
+    if (fresh) {
+        const int64_t n = g.n_tiles;
+        if (tid == 0) sh->merged = sweep::begin_merge(w.alive, w.lab, t);
+        __syncthreads();
+        for (int cc = g.touch_ptr[t] + tid; cc < g.touch_ptr[t + 1]; cc += kSwThreads) {
+            const int32_t root = sweep::mark_root(g, w.lab, t, cc, terr);
+            if (root < n) atomicMin(&sh->merged, root);
+            sweep::forget_chi(g, w.chi, cc, terr);
+        }
+        __syncthreads();
+        const int32_t m = sh->merged;
+        for (int64_t i = tid; i < n; i += kSwThreads) sweep::join_member(w.lab, n, i, m);
+        __syncthreads();
+        for (int64_t i = tid; i < n; i += kSwThreads) sweep::close_root(w.lab, i, m);
+        __syncthreads();
+    }
+    for (int64_t c0 = r0; c0 < r1; c0 += kSwThreads) {
+        const int64_t cc = c0 + tid;
+        const int32_t v = cc < r1 ? sweep::killed_by(w.nbr_idx, r0, cc, w.unl, w.n_nodes, terr) : -1;
+        const unsigned long long vote = __ballot(v >= 0);
+        if (lane == 0) sh->wave_kills[wave] = __popcll(vote);
+        __syncthreads();
+        int before = __popcll(vote & ((1ull << lane) - 1ull)), total = 0;
+        for (int wv = 0; wv < kSwWaves; ++wv) {
+            before += wv < wave ? sh->wave_kills[wv] : 0;
+            total += sh->wave_kills[wv];
+        }
+        const bool full = w.n_killed + total > room;         // (uniform: total is the block's)
+        if (v >= 0 && !full) {
+            w.killed[w.n_killed + before] = v;
+            w.unl[v] = 0;
+        }
+        __syncthreads();
+        if (full) return topo::kErrIndex;
+        w.n_killed += total;
+    }
+    return 0;
 }
 
 }  // namespace tgnn

@@ -12,11 +12,12 @@
 // tree_sweep_walk_kernel   ONE BLOCK of 128 threads per branch walks the branch's visiting order on its child slot.  Per
 //                          position: a node that is no longer unlabelled consumes the branch's next u -- u < p passes over it,
 //                          else the walk ends --; with check_holes, d holes of the node's tile under the slot's tile_alive, and
-//                          d holes > 0 passes over it, no draw; every other node is accepted, no draw: it leaves `unlabelled`,
-//                          its tile enters tile_alive, the labels are rewritten as in hole_sweep.hip (mark, join, close), the
-//                          cache forgets the tile's contact row, and the node's unlabelled collision neighbours are cleared and
-//                          appended to the killed list in row order (a vote per wave: the same list on every run).  The labels
-//                          live in LDS for the walk on graphs of up to kLabelLdsTiles tiles and in the slot's row beyond.
+//                          d holes > 0 passes over it, no draw; every other node is accepted, no draw, by block_accept of
+//                          hole_sweep_block.h, the acceptance of hole_sweep.hip: it leaves `unlabelled`, its tile enters
+//                          tile_alive, the labels are rewritten (mark, join, close), the cache forgets the tile's contact row,
+//                          and the node's unlabelled collision neighbours are cleared and appended to the killed list in row
+//                          order (a vote per wave: the same list on every run), as long as both lists fit the visiting list.
+//                          The labels live in LDS for the walk on graphs of up to kLabelLdsTiles tiles and in the slot's row beyond.
 //                          Without the geometry (check_holes == 0 only) the slot's three tile rows are never touched.
 //
 // Every loop is bounded by a list length: no spin, no grid barrier, no atomics on global memory.  Every output word of a branch
@@ -76,7 +77,7 @@ __global__ __launch_bounds__(kSwThreads) void tree_sweep_walk_kernel(TreeArgs a,
     extern __shared__ int32_t label_lds[];
     __shared__ double arc_lo[topo::kMaxWedges][kSwThreads], arc_hi[topo::kMaxWedges][kSwThreads];
     __shared__ SweepShared sh;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int64_t k = branch0 + blockIdx.x;
     const int64_t n = a.g.n_tiles;
     const int64_t v0 = a.visit_ptr[k], v1 = a.visit_ptr[k + 1];
@@ -98,7 +99,8 @@ __global__ __launch_bounds__(kSwThreads) void tree_sweep_walk_kernel(TreeArgs a,
     if (tid == 0) sh.err_all = 0;
     __syncthreads();
     LdsArcs<kSwThreads> arcs{arc_lo, arc_hi, tid};
-    int visited = 0, vetoes = 0, draws = 0, skipped = 0, n_acc = 0, n_killed = 0;     // the same in every thread
+    SweepWalk w{a.nbr_ptr, a.nbr_idx, a.n_nbr, a.n_nodes, unl, alive, lab, chi, accepted, killed, 0, 0};
+    int visited = 0, vetoes = 0, draws = 0, skipped = 0;     // the same in every thread
     int err = 0, terr = 0;                                   // err: uniform, ends the walk; terr: this thread's
     for (int64_t pos = 0; pos < n_visit; ++pos) {
         const int64_t node = a.visit_node[v0 + pos];
@@ -131,65 +133,14 @@ __global__ __launch_bounds__(kSwThreads) void tree_sweep_walk_kernel(TreeArgs a,
         skipped += code == tree::kSkipped;
         vetoes += code == sweep::kVetoed;
         if (code != sweep::kAccepted) continue;
-        // label_collision_neighbor's row, looked at before anything is written: a bad row ends the branch with its state as it was
-        const int64_t r0 = a.nbr_ptr[node], r1 = a.nbr_ptr[node + 1];
-        if (r0 < 0 || r1 < r0 || r1 > a.n_nbr || !tree::lists_fit(n_acc, n_killed, 1, n_visit)) {
-            err |= topo::kErrIndex;
-            break;
-        }
-        const bool fresh = kTiles && alive[t] == 0;
-        __syncthreads();                                     // (every thread has read unl[node] and alive[t])
-        if (tid == 0) {
-            unl[node] = 0;
-            accepted[n_acc] = (int32_t)node;
-        }
-        ++n_acc;
-        __syncthreads();
-        if (fresh) {
-            if (tid == 0) sh.merged = sweep::begin_merge(alive, lab, t);
-            __syncthreads();
-            for (int cc = a.g.touch_ptr[t] + tid; cc < a.g.touch_ptr[t + 1]; cc += kSwThreads) {
-                const int32_t root = sweep::mark_root(a.g, lab, t, cc, terr);
-                if (root < n) atomicMin(&sh.merged, root);
-                sweep::forget_chi(a.g, chi, cc, terr);
-            }
-            __syncthreads();
-            const int32_t m = sh.merged;
-            for (int64_t i = tid; i < n; i += kSwThreads) sweep::join_member(lab, n, i, m);
-            __syncthreads();
-            for (int64_t i = tid; i < n; i += kSwThreads) sweep::close_root(lab, i, m);
-            __syncthreads();
-        }
-        bool full = false;
-        for (int64_t c0 = r0; c0 < r1; c0 += kSwThreads) {
-            const int64_t cc = c0 + tid;
-            const int32_t v = cc < r1 ? sweep::killed_by(a.nbr_idx, r0, cc, unl, a.n_nodes, terr) : -1;
-            const unsigned long long vote = __ballot(v >= 0);
-            if (lane == 0) sh.wave_kills[wave] = __popcll(vote);
-            __syncthreads();
-            int before = __popcll(vote & ((1ull << lane) - 1ull)), total = 0;
-            for (int w = 0; w < kSwWaves; ++w) {
-                before += w < wave ? sh.wave_kills[w] : 0;
-                total += sh.wave_kills[w];
-            }
-            full = !tree::lists_fit(n_acc, n_killed, total, n_visit);        // (uniform: total is the block's)
-            if (v >= 0 && !full) {
-                killed[n_killed + before] = v;
-                unl[v] = 0;
-            }
-            __syncthreads();
-            if (full) break;
-            n_killed += total;
-        }
-        if (full) {
-            err |= topo::kErrIndex;
-            break;
-        }
+        // tree::lists_fit for this node and every chunk of its row: both lists together never exceed the visiting list
+        err |= block_accept<kTiles>(a.g, w, node, t, n_visit - w.n_accepted - 1, &sh, terr);
+        if (err != 0) break;
     }
     __syncthreads();
     for (int64_t pos = visited + tid; pos < n_visit; pos += kSwThreads) trace[2 * pos] = sweep::kNotReached, trace[2 * pos + 1] = 0;
-    for (int64_t i = n_acc + tid; i < n_visit; i += kSwThreads) accepted[i] = -1;
-    for (int64_t i = n_killed + tid; i < n_visit; i += kSwThreads) killed[i] = -1;
+    for (int64_t i = w.n_accepted + tid; i < n_visit; i += kSwThreads) accepted[i] = -1;
+    for (int64_t i = w.n_killed + tid; i < n_visit; i += kSwThreads) killed[i] = -1;
     if (kInLds)
         for (int64_t i = tid; i < n; i += kSwThreads) glab[i] = lab[i];
     if (terr != 0) atomicOr(&sh.err_all, terr);
@@ -198,8 +149,8 @@ __global__ __launch_bounds__(kSwThreads) void tree_sweep_walk_kernel(TreeArgs a,
         stats[tree::kStatVisited] = visited;
         stats[tree::kStatVetoes] = vetoes;
         stats[tree::kStatDraws] = draws;
-        stats[tree::kStatAccepted] = n_acc;
-        stats[tree::kStatKilled] = n_killed;
+        stats[tree::kStatAccepted] = w.n_accepted;
+        stats[tree::kStatKilled] = w.n_killed;
         stats[tree::kStatSkipped] = skipped;
         stats[6] = stats[7] = 0;
         a.err[k] = err | sh.err_all;

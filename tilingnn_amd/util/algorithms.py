@@ -163,6 +163,93 @@ class HostSweep:
         return killed
 
 
+def _tiles_of_nodes(inverse_index, n, n_tiles, who=""):
+    """inverse_index (node -> tile) of the n nodes of a layout as int64 tiles, every one inside the graph."""
+    tiles = np.fromiter((inverse_index[i] for i in range(n)), dtype=np.int64, count=n)
+    if n and (tiles.min() < 0 or tiles.max() >= n_tiles):
+        raise ValueError(f"{who}inverse_index names a tile outside [0, {n_tiles})")
+    return tiles
+
+
+class _AheadDraws:
+    """The RNG hand-over of a device walk: keeps the generator's state and draws n uniforms in one call (`u`); `settle(consumed)`,
+    once the walk has said how many it consumed, rewinds the generator and draws exactly those.  numpy's `uniform(size=n)` is n
+    scalar draws bit for bit, so the decisions AND the generator's state afterwards are those of scalar draws
+    (tests/test_hole_sweep_host.py and tests/test_tree_search_host.py pin both)."""
+
+    def __init__(self, rng, n):
+        self.rng, self.state = rng, rng.get_state()
+        self.u = rng.uniform(size=n)
+
+    def settle(self, consumed):
+        self.rng.set_state(self.state)                          # the stream moves by what the walk consumed, no more
+        self.rng.uniform(size=int(consumed))
+
+
+class _Staging:
+    """A device buffer and a pinned host buffer of int32 words per direction, cut into the same named fields.  fields_in,
+    fields_out: (name, int32 words, dtype) in buffer order -- f64 fields first, so that they stay 8-byte aligned.  `dev[name]`:
+    the device views; `host[name]`: numpy views of the pinned buffers; `send()` queues the ONE host-to-device copy, `fetch()` the
+    ONE device-to-host copy and waits for the stream."""
+
+    def __init__(self, device, fields_in, fields_out):
+        self.device, self.dev, self.host = device, {}, {}
+        self._in, self._out = self._cut(fields_in), self._cut(fields_out)
+
+    def _cut(self, fields):
+        words = sum(w for _, w, _ in fields) + 1
+        dev = torch.zeros(words, dtype=torch.int32, device=self.device)
+        host = torch.zeros(words, dtype=torch.int32, pin_memory=True)
+        at = 0
+        for name, w, dtype in fields:
+            self.dev[name], self.host[name] = dev[at:at + w].view(dtype), host[at:at + w].view(dtype).numpy()
+            at += w
+        return dev, host
+
+    def send(self):
+        self._in[0].copy_(self._in[1], non_blocking=True)
+
+    def fetch(self):
+        self._out[1].copy_(self._out[0], non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+
+
+class _SweepStaging(_Staging):
+    """What a call of a device walk over K visiting lists of V positions in all sends -- rate [V] f64 (thr or prob_m by position)
+    | u [V] f64 | visit_node [V] | visit_ptr [K + 1] | one [K] table per name of `tables` -- and brings back -- stats [K][8] |
+    err [K] | accepted [V] | killed [V] | trace [V][2].  `v`: the positions listed so far."""
+
+    def __init__(self, device, K, V, tables):
+        f64, i32 = torch.float64, torch.int32
+        super().__init__(device, [("rate", 2 * V, f64), ("u", 2 * V, f64), ("visit_node", V, i32), ("visit_ptr", K + 1, i32)]
+                         + [(name, K, i32) for name in tables],
+                         [("stats", 8 * K, i32), ("err", K, i32), ("accepted", V, i32), ("killed", V, i32), ("trace", 2 * V, i32)])
+
+    def begin(self):
+        self.v, self.ahead = 0, {}
+        self.host["visit_ptr"][0] = 0
+
+    def add(self, k, nodes, rate, rng):
+        """List k of the call (in order of k): `nodes` in visiting order, `rate` by position, a uniform per position from rng."""
+        h, v, n = self.host, self.v, len(nodes)
+        self.ahead[k] = _AheadDraws(rng, n)
+        h["visit_node"][v:v + n], h["rate"][v:v + n], h["u"][v:v + n] = nodes, rate, self.ahead[k].u
+        self.v = v + n
+
+    def result(self, k, entry, killed_at=None):
+        """Of list k, after fetch(): its error bits raised as `entry`'s, else its generator settled and (stats row [8], accepted
+        nodes, killed nodes) as numpy copies.  killed_at: where its killed list starts (default: where its visiting list does)."""
+        h = self.host
+        if h["err"][k]:
+            from .data_util import _TOPOLOGY_ERROR_BITS, _raise_device_error
+            _raise_device_error(entry, int(h["err"][k]), _TOPOLOGY_ERROR_BITS)
+        row = h["stats"][8 * k:8 * k + 8].copy()
+        self.ahead[k].settle(row[2])
+        v0 = int(h["visit_ptr"][k])
+        k0 = v0 if killed_at is None else killed_at
+        return row, h["accepted"][v0:v0 + int(row[3])].astype(np.int64), h["killed"][k0:k0 + int(row[4])].astype(np.int64)
+
+
 class HoleGuard:
     """The hole veto of the reference's assembly (algorithms.py:150-152, check_holes -> exist_hole: refuse a tile whose union
     with the selection has an interior ring) for the sweep of `HostSweep`: holds, per node of the layout, what adding its tile
@@ -176,9 +263,7 @@ class HoleGuard:
         from .data_util import graph_on_device
         self.on_device = graph_on_device(complete_graph, device)
         dev, n_tiles = self.on_device.device, self.on_device.n_tiles
-        self.tiles = np.fromiter((inverse_index[i] for i in range(n)), dtype=np.int64, count=n)
-        if n and (self.tiles.min() < 0 or self.tiles.max() >= n_tiles):
-            raise ValueError(f"inverse_index names a tile outside [0, {n_tiles})")
+        self.tiles = _tiles_of_nodes(inverse_index, n, n_tiles)
         self._alive = torch.zeros(n_tiles, dtype=torch.int32, device=dev)
         self._out = torch.zeros(3 * n_tiles + 1, dtype=torch.int32, device=dev)          # delta [n_tiles][2] | state [n_tiles] | error word
         self._host = torch.empty(3 * n_tiles + 1, dtype=torch.int32, pin_memory=True)
@@ -220,9 +305,8 @@ class DeviceHoleSweep:
     thresholds, the uniforms), one call -- a block per layout walks its order and computes a node's d holes when it gets there --
     and ONE device-to-host copy (counters, accepted and killed nodes, the trace).  The decisions are the host sweep's, one for one.
     layouts: (n nodes, collide_edge_index as numpy, inverse_index) per layout; rngs: per layout what draws its uniforms,
-    `np.random` itself or a `RandomState`.  A round draws n_sub uniforms in one call and, once the walk has said how many it
-    consumed, rewinds the generator and draws exactly those: numpy's `uniform(size=n)` is n scalar draws bit for bit, so the
-    selection AND the generator's state afterwards are the host sweep's (tests/test_hole_sweep_host.py pins both).
+    `np.random` itself or a `RandomState`, handed over per round by `_AheadDraws`: the selection AND the generator's state
+    afterwards are the host sweep's.
     State per layout as `HostSweep` keeps it (`sweeps[k]`: prob_saved, unlabelled, selection, order, round_cnt) and on the device
     `unlabelled` [N] int32 (the alive mask the sub-layout compaction reads), `tile_alive`, `label`, `chi_cache` [K, n_tiles].
     `vetoes`, `launches` [K]: per layout the vetoes counted and the rounds it was active in; `calls`: sweep calls queued;
@@ -246,9 +330,7 @@ class DeviceHoleSweep:
         nbr_ptr, nbr_idx = np.zeros(N + 1, dtype=np.int64), []
         for k, ((n, _, inverse), sw) in enumerate(zip(layouts, self.sweeps)):
             n0 = int(self.node_ptr_h[k])
-            tiles[n0:n0 + n] = np.fromiter((inverse[i] for i in range(n)), dtype=np.int64, count=n)
-            if n and (tiles[n0:n0 + n].min() < 0 or tiles[n0:n0 + n].max() >= n_tiles):
-                raise ValueError(f"layout {k}: inverse_index names a tile outside [0, {n_tiles})")
+            tiles[n0:n0 + n] = _tiles_of_nodes(inverse, n, n_tiles, f"layout {k}: ")
             if sw.has_col:                                      # the rows HostSweep walks (edge order), local numbers
                 nbr_ptr[n0 + 1:n0 + n + 1] = nbr_ptr[n0] + sw.starts[1:]
                 nbr_idx.append(sw.nbr)
@@ -266,22 +348,8 @@ class DeviceHoleSweep:
         self.tile_alive = torch.zeros(max(K, 1), n_tiles, dtype=i32, device=dev)
         self.label = torch.full((max(K, 1), n_tiles), -1, dtype=i32, device=dev)
         self.chi_cache = torch.full((max(K, 1), n_tiles), -2 ** 31, dtype=i32, device=dev)     # TGNN_SWEEP_CHI_UNKNOWN
-        # what a round sends: thr [N] f64 | u [N] f64 | visit_node [N] | visit_ptr [K + 1] | active [K]   (int32 words)
-        words_in = 5 * N + 2 * K + 2
-        self._in = torch.zeros(words_in, dtype=i32, device=dev)
-        self._in_h = torch.zeros(words_in, dtype=i32, pin_memory=True)
-        cut = lambda buf: (buf[:2 * N].view(torch.float64), buf[2 * N:4 * N].view(torch.float64), buf[4 * N:5 * N],
-                           buf[5 * N:5 * N + K + 1], buf[5 * N + K + 1:5 * N + 2 * K + 1])
-        self._in_parts = cut(self._in)
-        self._thr_h, self._u_h, self._visit_node_h, self._visit_ptr_h, self._active_h = (t.numpy() for t in cut(self._in_h))
-        # what a round brings back: stats [K][8] | err [K] | accepted [N] | killed [N] | trace [N][2]
-        words_out = 9 * K + 4 * N + 1
-        self._out = torch.zeros(words_out, dtype=i32, device=dev)
-        self._out_h = torch.zeros(words_out, dtype=i32, pin_memory=True)
-        cut = lambda buf: (buf[:8 * K], buf[8 * K:9 * K], buf[9 * K:9 * K + N], buf[9 * K + N:9 * K + 2 * N],
-                           buf[9 * K + 2 * N:9 * K + 4 * N])
-        self._out_parts = cut(self._out)
-        self._stats_h, self._err_h, self._accepted_h, self._killed_h, self._trace_h = (t.numpy() for t in cut(self._out_h))
+        self._staging = _SweepStaging(dev, K, N, ("active",))
+        self._stats_h = self._staging.host["stats"]             # (the last round's stats rows; tests read them)
         self._ws = torch.empty(max(K, 1), dtype=i32, device=dev)
         self.vetoes, self.launches = np.zeros(K, dtype=np.int64), np.zeros(K, dtype=np.int64)
         self.calls = 0
@@ -295,62 +363,45 @@ class DeviceHoleSweep:
         `sweeps[k].ids()`.  Returns per layout the original numbers of the nodes labelled in this round (None where it did not
         run).  A layout all of whose remaining nodes are vetoed afterwards is finished: its `unlabelled` is cleared on the host."""
         K, N, od = self.k, self.n, self.on_device
-        ran, states, all_ids = [], {}, {}
-        v = 0
-        self._visit_ptr_h[0] = 0
+        st = self._staging
+        h, d = st.host, st.dev
+        ran = []
+        st.begin()
         for k, (sw, prob) in enumerate(zip(self.sweeps, probs)):
             ids = sw.ids() if prob is not None else ()
-            self._active_h[k] = int(len(ids) > 0)
+            h["active"][k] = int(len(ids) > 0)
             if len(ids):
                 prob = np.asarray(prob, dtype=np.float64).reshape(-1)
                 per_node = np.power(np.power(sw.prob_saved[ids], sw.round_cnt - 1) * prob, 1 / sw.round_cnt)     # (HostSweep.round)
                 sw.prob_saved[ids] = per_node
                 order = np.argsort(-per_node)
-                n_sub = order.shape[0]
-                self._visit_node_h[v:v + n_sub] = ids[order]
-                self._thr_h[v:v + n_sub] = np.exp((per_node[order] - 1) * 1.0)
-                states[k] = self.rngs[k].get_state()
-                self._u_h[v:v + n_sub] = self.rngs[k].uniform(size=n_sub)
-                all_ids[k] = ids
+                st.add(k, ids[order], np.exp((per_node[order] - 1) * 1.0), self.rngs[k])
                 ran.append(k)
-                v += n_sub
             elif prob is not None:
                 sw.round_cnt += 1                               # (a round over no node: HostSweep.round counts it)
-            self._visit_ptr_h[k + 1] = v
+            h["visit_ptr"][k + 1] = st.v
         out = [None if p is None else [] for p in probs]
         if not ran:
             return out
-        dev = od.device
-        self._in.copy_(self._in_h, non_blocking=True)
-        thr, u, visit_node, visit_ptr, active = self._in_parts
-        stats, err, accepted, killed, trace = self._out_parts
+        st.send()
         od.hole_sweep_into(K, self.node_ptr, N, self.tile_of_node, self.nbr_ptr, self.nbr_idx, self.n_nbr, self.unlabelled,
-                           self.tile_alive, self.label, self.chi_cache, active, visit_ptr, visit_node, thr, u, v, stats, accepted, killed, trace,
-                           err, self._ws)
-        self._out_h.copy_(self._out, non_blocking=True)
-        torch.cuda.current_stream(dev).synchronize()
+                           self.tile_alive, self.label, self.chi_cache, d["active"], d["visit_ptr"], d["visit_node"], d["rate"], d["u"],
+                           st.v, d["stats"], d["accepted"], d["killed"], d["trace"], d["err"], self._ws)
+        st.fetch()
         self.calls += 1
-        self.trace, self.visit_ptr, self.visit_node = self._trace_h.reshape(-1, 2), self._visit_ptr_h, self._visit_node_h
+        self.trace, self.visit_ptr, self.visit_node = h["trace"].reshape(-1, 2), h["visit_ptr"], h["visit_node"]
         for k in ran:
-            sw, rng = self.sweeps[k], self.rngs[k]
-            if self._err_h[k]:
-                from .data_util import _TOPOLOGY_ERROR_BITS, _raise_device_error
-                _raise_device_error(f"tgnn_hole_sweep_many (layout {k})", int(self._err_h[k]), _TOPOLOGY_ERROR_BITS)
-            _, vetoes, draws, n_acc, n_killed, all_vetoed = (int(w) for w in self._stats_h[8 * k:8 * k + 6])
-            rng.set_state(states[k])                            # the stream moves by what the walk consumed, no more
-            rng.uniform(size=draws)
-            v0, n0 = int(self._visit_ptr_h[k]), int(self.node_ptr_h[k])
-            acc = self._accepted_h[v0:v0 + n_acc].astype(np.int64)
-            gone = self._killed_h[n0:n0 + n_killed].astype(np.int64)
+            sw = self.sweeps[k]
+            row, acc, gone = st.result(k, f"tgnn_hole_sweep_many (layout {k})", int(self.node_ptr_h[k]))
             sw.unlabelled[acc] = False
             sw.unlabelled[gone] = False
             sw.selection[acc] = 1
             sw.order.extend(int(i) for i in acc)
             sw.round_cnt += 1
-            self.vetoes[k] += vetoes
+            self.vetoes[k] += row[1]
             self.launches[k] += 1
             out[k] = [int(i) for i in acc] + [int(i) for i in gone]
-            if all_vetoed:                                      # nothing can change any more (solve_by_probablistic_greedy)
+            if row[5]:                                          # all vetoed: nothing can change any more (solve_by_probablistic_greedy)
                 sw.unlabelled[:] = False
         return out
 
@@ -982,9 +1033,8 @@ class DeviceTreeSweep:
     `reset(slot)` makes it the empty selection.
     `sweep(branches)`: branches = (parent slot, child slot, nodes in visiting order, prob_m by position, rng) each.  The slot
     contract of include/tgnn.h is checked here, on the host tables, before anything is copied.  The RNG hand-over is
-    `DeviceHoleSweep`'s, per branch: the generator's state is kept, n_sub uniforms are drawn in one call, and once the walk has
-    said how many it consumed the generator is rewound and draws exactly those (tests/test_tree_search_host.py pins that this is
-    n scalar draws).  Returns per branch (stats row [8], accepted nodes, killed nodes) as numpy copies.
+    `DeviceHoleSweep`'s, per branch (`_AheadDraws`).  Returns per branch (stats row [8], accepted nodes, killed nodes) as numpy
+    copies.
     geometry: keep the tile state (needed by check_holes; default: only with check_holes).  `calls`, `branches`, `vetoes` count
     the sweep calls queued, the branches swept and the vetoes met; `trace`, `visit_ptr`, `visit_node` are the last call's (views
     of the staging buffers, valid until the next call)."""
@@ -1005,9 +1055,7 @@ class DeviceTreeSweep:
             from .data_util import graph_on_device
             self.on_device = graph_on_device(complete_graph, device)
             device, self.n_tiles = self.on_device.device, self.on_device.n_tiles
-            tiles = np.fromiter((inverse_index[i] for i in range(n)), dtype=np.int64, count=n)
-            if n and (tiles.min() < 0 or tiles.max() >= self.n_tiles):
-                raise ValueError(f"inverse_index names a tile outside [0, {self.n_tiles})")
+            tiles = _tiles_of_nodes(inverse_index, n, self.n_tiles)
         self.device = dev = torch.device(device)
         if max(n, self.n_nbr, self.n_tiles) >= 2 ** 31 - 1:
             raise ValueError("DeviceTreeSweep: more than 2^31 nodes or collision entries")
@@ -1076,74 +1124,41 @@ class DeviceTreeSweep:
     def _stage(self, k, v):
         if k <= self._cap_k and v <= self._cap_v:
             return
-        K, V = max(k, 2 * self._cap_k), max(v, 2 * self._cap_v)
-        self._cap_k, self._cap_v = K, V
-        i32, dev = torch.int32, self.device
-        # what a call sends: p [V] f64 | u [V] f64 | visit_node [V] | visit_ptr [K + 1] | parent [K] | slot [K]   (int32 words)
-        words_in = 5 * V + 3 * K + 2
-        self._in = torch.zeros(words_in, dtype=i32, device=dev)
-        self._in_h = torch.zeros(words_in, dtype=i32, pin_memory=True)
-        cut = lambda buf: (buf[:2 * V].view(torch.float64), buf[2 * V:4 * V].view(torch.float64), buf[4 * V:5 * V],
-                           buf[5 * V:5 * V + K + 1], buf[5 * V + K + 1:5 * V + 2 * K + 1], buf[5 * V + 2 * K + 1:5 * V + 3 * K + 1])
-        self._in_parts = cut(self._in)
-        self._p_h, self._u_h, self._visit_node_h, self._visit_ptr_h, self._parent_h, self._slot_h = (t.numpy() for t in cut(self._in_h))
-        # what a call brings back: stats [K][8] | err [K] | accepted [V] | killed [V] | trace [V][2]
-        words_out = 9 * K + 4 * V + 1
-        self._out = torch.zeros(words_out, dtype=i32, device=dev)
-        self._out_h = torch.zeros(words_out, dtype=i32, pin_memory=True)
-        cut = lambda buf: (buf[:8 * K], buf[8 * K:9 * K], buf[9 * K:9 * K + V], buf[9 * K + V:9 * K + 2 * V],
-                           buf[9 * K + 2 * V:9 * K + 4 * V])
-        self._out_parts = cut(self._out)
-        self._stats_h, self._err_h, self._accepted_h, self._killed_h, self._trace_h = (t.numpy() for t in cut(self._out_h))
-        self._ws = torch.empty(K, dtype=i32, device=dev)
+        self._cap_k, self._cap_v = max(k, 2 * self._cap_k), max(v, 2 * self._cap_v)
+        self._staging = _SweepStaging(self.device, self._cap_k, self._cap_v, ("parent", "slot"))
+        self._ws = torch.empty(self._cap_k, dtype=torch.int32, device=self.device)
 
     def sweep(self, branches) -> list:
-        from .data_util import _TOPOLOGY_ERROR_BITS, _raise_device_error, tree_sweep_call
+        from .data_util import tree_sweep_call
         branches = list(branches)
         K = len(branches)
         if K == 0:
             return []
         self.check_slots([b[0] for b in branches], [b[1] for b in branches], self.n_slots)
         self._stage(K, sum(len(b[2]) for b in branches))
-        states, v = [], 0
-        self._visit_ptr_h[0] = 0
+        st = self._staging
+        h, d = st.host, st.dev
+        st.begin()
         for k, (parent, child, nodes, prob_m, rng) in enumerate(branches):
-            n_sub = len(nodes)
-            self._parent_h[k], self._slot_h[k] = parent, child
-            self._visit_node_h[v:v + n_sub] = nodes
-            self._p_h[v:v + n_sub] = prob_m
-            states.append(rng.get_state())
-            self._u_h[v:v + n_sub] = rng.uniform(size=n_sub)
-            v += n_sub
-            self._visit_ptr_h[k + 1] = v
-        if v == 0:
+            h["parent"][k], h["slot"][k] = parent, child
+            st.add(k, nodes, prob_m, rng)
+            h["visit_ptr"][k + 1] = st.v
+        if st.v == 0:
             return [(np.zeros(8, dtype=np.int32), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64))] * K
-        dev = self.device
-        self._in.copy_(self._in_h, non_blocking=True)
-        p, u, visit_node, visit_ptr, parent, slot = self._in_parts
-        stats, err, accepted, killed, trace = self._out_parts
+        st.send()
         args = (self.n, self.tile_of_node, self.nbr_ptr, self.nbr_idx, self.n_nbr, self.n_slots, self.unlabelled, self.tile_alive,
-                self.label, self.chi_cache, K, parent, slot, visit_ptr, visit_node, p, u, v, self.check_holes, stats, accepted, killed,
-                trace, err, self._ws)
+                self.label, self.chi_cache, K, d["parent"], d["slot"], d["visit_ptr"], d["visit_node"], d["rate"], d["u"], st.v,
+                self.check_holes, d["stats"], d["accepted"], d["killed"], d["trace"], d["err"], self._ws)
         if self.geometry:
             self.on_device.tree_sweep_into(*args)
         else:
-            tree_sweep_call(dev, None, *args)
-        self._out_h.copy_(self._out, non_blocking=True)
-        torch.cuda.current_stream(dev).synchronize()
+            tree_sweep_call(self.device, None, *args)
+        st.fetch()
         self.calls += 1
         self.branches += K
-        self.trace, self.visit_ptr, self.visit_node = self._trace_h.reshape(-1, 2), self._visit_ptr_h, self._visit_node_h
-        out = []
-        for k, (_, _, nodes, _, rng) in enumerate(branches):
-            if self._err_h[k]:
-                _raise_device_error(f"tgnn_tree_sweep_many (branch {k})", int(self._err_h[k]), _TOPOLOGY_ERROR_BITS)
-            row = self._stats_h[8 * k:8 * k + 8].copy()
-            rng.set_state(states[k])                            # the stream moves by what the walk consumed, no more
-            rng.uniform(size=int(row[2]))
-            v0 = int(self._visit_ptr_h[k])
-            out.append((row, self._accepted_h[v0:v0 + int(row[3])].astype(np.int64), self._killed_h[v0:v0 + int(row[4])].astype(np.int64)))
-            self.vetoes += int(row[1])
+        self.trace, self.visit_ptr, self.visit_node = h["trace"].reshape(-1, 2), h["visit_ptr"], h["visit_node"]
+        out = [st.result(k, f"tgnn_tree_sweep_many (branch {k})") for k in range(K)]
+        self.vetoes += sum(int(row[1]) for row, _, _ in out)
         return out
 
 

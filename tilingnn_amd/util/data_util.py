@@ -402,22 +402,27 @@ class CompleteGraphOnDevice:
                                         ptr(touch_idx), ptr(alive), k, UNION_TOL, dir_x, dir_y, ptr(delta), ptr(state),
                                         ptr(err), ptr(ws), ws_bytes, _lib.current_stream(self.device)))
 
+    def _sweep_geometry(self):
+        """The eight leading arguments of `tgnn_hole_sweep_many` and `tgnn_tree_sweep_many`: the rings, the contact rows, the
+        tolerance and the sweep direction."""
+        _, _, _, _, ptr, UNION_TOL = _union_api()
+        ring_xy, ring_ptr, _, _ = self._union_geometry()
+        touch_ptr, touch_idx, dir_x, dir_y = self._topology_geometry()
+        return ptr(ring_xy), ptr(ring_ptr), self.n_tiles, ptr(touch_ptr), ptr(touch_idx), UNION_TOL, dir_x, dir_y
+
     def hole_sweep_into(self, k, node_ptr, n_nodes, tile_of_node, nbr_ptr, nbr_idx, n_nbr, unlabelled, tile_alive, label, chi_cache,
                         active, visit_ptr, visit_node, thr, u, n_visit, stats, accepted, killed, trace, err, ws=None):
         """One round of the hole-free greedy sweep of K layouts of this graph, queued on the current stream with nothing read
         back: the raw call of `tgnn_hole_sweep_many` (include/tgnn.h has the argument contract; csrc/hole_sweep.hip).  Every
         argument but the counts is a contiguous tensor on this device: int32, `thr` / `u` float64; `ws` int32 of at least K
         words (made here when None).  `util.algorithms.DeviceHoleSweep` keeps the state, the staging buffers and the RNG."""
-        torch, _lib, check, lib, ptr, UNION_TOL = _union_api()
-        ring_xy, ring_ptr, _, _ = self._union_geometry()
-        touch_ptr, touch_idx, dir_x, dir_y = self._topology_geometry()
+        torch, _lib, check, lib, ptr, _ = _union_api()
         ws_bytes = int(lib.tgnn_hole_sweep_workspace_bytes(k))
         if ws is None:
             ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
-            check(lib.tgnn_hole_sweep_many(ptr(ring_xy), ptr(ring_ptr), self.n_tiles, ptr(touch_ptr), ptr(touch_idx), UNION_TOL,
-                                           dir_x, dir_y, k, ptr(node_ptr), n_nodes, ptr(tile_of_node), ptr(nbr_ptr), ptr(nbr_idx),
-                                           n_nbr, ptr(unlabelled), ptr(tile_alive), ptr(label), ptr(chi_cache), ptr(active), ptr(visit_ptr),
+            check(lib.tgnn_hole_sweep_many(*self._sweep_geometry(), k, ptr(node_ptr), n_nodes, ptr(tile_of_node), ptr(nbr_ptr),
+                                           ptr(nbr_idx), n_nbr, ptr(unlabelled), ptr(tile_alive), ptr(label), ptr(chi_cache), ptr(active), ptr(visit_ptr),
                                            ptr(visit_node), ptr(thr), ptr(u), n_visit, ptr(stats), ptr(accepted), ptr(killed),
                                            ptr(trace), ptr(err), ptr(ws), 4 * int(ws.numel()),
                                            _lib.current_stream(self.device)))
@@ -432,14 +437,8 @@ class CompleteGraphOnDevice:
         geometry=False (check_holes == 0 only): the graph's rings and contact rows are not handed over and no tile state is
         kept -- `tile_of_node` and the three tile rows may be None.  `util.algorithms.DeviceTreeSweep` keeps the pool, the
         staging buffers and the RNGs."""
-        torch, _lib, check, lib, ptr, UNION_TOL = _union_api()
-        geo = None
-        if geometry:
-            ring_xy, ring_ptr, _, _ = self._union_geometry()
-            touch_ptr, touch_idx, dir_x, dir_y = self._topology_geometry()
-            geo = (ptr(ring_xy), ptr(ring_ptr), self.n_tiles, ptr(touch_ptr), ptr(touch_idx), UNION_TOL, dir_x, dir_y)
-        tree_sweep_call(self.device, geo, n_nodes, tile_of_node, nbr_ptr, nbr_idx, n_nbr, n_slots, unlabelled, tile_alive, label,
-                        chi_cache, k, parent_slot, slot, visit_ptr, visit_node, p, u, n_visit, check_holes, stats, accepted, killed,
+        tree_sweep_call(self.device, self._sweep_geometry() if geometry else None, n_nodes, tile_of_node, nbr_ptr, nbr_idx, n_nbr,
+                        n_slots, unlabelled, tile_alive, label, chi_cache, k, parent_slot, slot, visit_ptr, visit_node, p, u, n_visit, check_holes, stats, accepted, killed,
                         trace, err, ws)
 
     # -------------------------------------------------------------------------- the outline of a union of tiles
