@@ -109,6 +109,31 @@ class reference_ops:
         return False
 
 
+def batch_norm_eval(v: Tensor, sd: SD, prefix: str, update_running: bool = False) -> Tensor:
+    """nn.BatchNorm1d in EVAL mode: y = gamma * (v - running_mean) / sqrt(running_var + eps) + beta, per row -- any row count,
+    one row included.  No buffer is written whatever `update_running` says (torch: the buffers are state of train mode only)."""
+    return (v - sd[prefix + ".running_mean"]) / torch.sqrt(sd[prefix + ".running_var"] + BN_EPS) * sd[prefix + ".weight"] \
+        + sd[prefix + ".bias"]
+
+
+class running_statistics:
+    """Context: every BatchNorm of the functions below is `batch_norm_eval` -- the network after `.eval()`, which the reference's
+    solver never calls (ml_solver.py:129-131) and tilingnn_amd.TilinGNN honours like torch (tgnn_forward with use_running_stats).
+    The decomposed, dtype-generic form; pinned against torch.nn.BatchNorm1d(...).eval() and against the reference's own modules
+    in .eval() (tests/test_eval_cases_host.py, tests/golden/generate_eval_golden.py).  Not to be nested with `reference_ops`
+    (that one puts train-mode BatchNorm back)."""
+
+    def __enter__(self):
+        g = globals()
+        self._saved = g["batch_norm_train"]
+        g["batch_norm_train"] = batch_norm_eval
+        return self
+
+    def __exit__(self, *exc):
+        globals()["batch_norm_train"] = self._saved
+        return False
+
+
 def linear(v: Tensor, sd: SD, prefix: str) -> Tensor:
     return v @ sd[prefix + ".weight"].t() + sd[prefix + ".bias"]
 

@@ -586,6 +586,10 @@ class FusedShardForward:
     def step(self) -> Tensor:
         """Graph preparation + forward of this shard; returns probs of the owned rows."""
         C, _lib, ops, sh, net = self._C, self._lib, self._ops, self.shard, self.net
+        if not net.training:
+            # (tgnn_forward_sharded sums batch statistics over the shards and has no running-statistics mode: an eval() network
+            #  would silently be normalised like a train() one)
+            raise ValueError("the sharded forward runs train-mode BatchNorm only; the network is in eval mode")
         inp = self.inputs
         graph = ops.prepare_graph(sh.n_own, inp["adj"], inp["attr"], inp["col"], n_src_nodes=sh.n_rows)
         if not self.fused or _lib.lib.tgnn_set_split_precision(-1) == 0:

@@ -262,6 +262,9 @@ def forward_train(net, x: Tensor, adj_e_index: Tensor, adj_e_features: Tensor, c
     n = int(x.shape[0])
     if n < 2:
         raise ValueError("Expected more than 1 value per channel when training")
+    if not net.training:
+        # (tgnn_forward_train has no running-statistics mode: an eval() network would silently be normalised like a train() one)
+        raise ValueError("the training forward runs train-mode BatchNorm only; the network is in eval mode")
     table, dev = net._param_table()
     xf, ea = ops._f32c(x, "x"), ops._f32c(adj_e_features, "adj_e_features")
     tg = _train_graph(net, n, adj_e_index, adj_e_features, col_e_idx)
